@@ -2,7 +2,7 @@
 """bench.py -- temporal edges/sec embedded by the T-PPR + top-k aggregate +
 memory-update path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of the synthetic stream
 (eval-mode protocol of reference model/tgn_model.py:124-174): streaming (or
@@ -288,6 +288,42 @@ def launch_ranks(n, argv):
 CRIT_SECTION_NS = 970.0    # the hub chain's critical section: 2280 core clocks (median, tools/crit_profile.py)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def last_step_outputs(tgn, emb, src_b, dst_b, bs):
+    """What one eval-mode step returns to its caller, as host arrays: the source / destination / negative embeddings of
+    its batch (compute_temporal_embeddings) and the memory rows and last-update times of the batch's endpoints, which the
+    step's GRU update has just written (node ids beside them)."""
+    import torch
+    e = emb.detach().float().cpu().numpy()
+    ids = np.unique(np.concatenate([src_b, dst_b])).astype(np.int64)
+    ids_d = torch.from_numpy(ids).to(tgn.device)
+    mem = tgn.memory
+    return {"source_embedding": e[:bs], "destination_embedding": e[bs:2 * bs], "negative_embedding": e[2 * bs:3 * bs],
+            "memory_node_ids": ids.astype(np.float64),
+            "memory": mem.memory.index_select(0, ids_d).float().cpu().numpy(),
+            "memory_last_update": mem.last_update.index_select(0, ids_d).double().cpu().numpy()}
+
+
+def write_outputs(d, arrays):
+    """DIR/<name>.npy for every array (float32 stays float32, anything else becomes float64).  Over DUMP_BYTES_MAX in
+    all, every array keeps the same share of its rows, picked by a fixed seed (sorted), and the kept row numbers go to
+    DIR/<name>_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {n: (x if x.dtype == np.float32 else x.astype(np.float64)) for n, x in arrays.items()}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        total += sum(8 * len(x) for x in arrays.values())          # (the _rows files)
+    frac = min(1.0, 0.99 * DUMP_BYTES_MAX / max(1, total))
+    for i, (n, x) in enumerate(sorted(arrays.items())):
+        if frac < 1.0 and len(x):
+            keep = np.sort(np.random.default_rng(1000 + i).choice(len(x), max(1, int(len(x) * frac)), replace=False))
+            np.save(os.path.join(d, n + "_rows.npy"), keep.astype(np.float64))
+            x = x[keep]
+        np.save(os.path.join(d, n + ".npy"), np.ascontiguousarray(x))
+
+
 def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edges, steady=0):
     """One workload: build the model, prefill, warm up, time `steps` steps, read the per-kernel events, run the CPU leg
     (world == 1).  Returns the dict of the JSON line (headline) or of a `workloads` entry."""
@@ -393,12 +429,17 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
                 if (b0, nb) not in prepared:
                     prep(b0, nb)
                 tgn.run_device(prepared[(b0, nb)], out=keep, look=state["look"])
+                if a.dump_outputs:         # the last step's [3 bs, H] embeddings: its block of `keep`, or the buffer every step overwrites
+                    H = tgn.embedding_dimension * (M + 1)
+                    state["last_emb"] = keep[nb - 1] if keep is not None else tgn._run_scratch[: 3 * bs * H].view(3 * bs, H)
                 return
             for b in range(b0, b0 + nb):
                 ahead = [] if no_pipeline else batches[b + 1: min(b + 1 + state["look"], b0 + nb)]
                 e = step(*batches[b], ahead=ahead)
                 if keep is not None:
                     keep[b - b0].copy_(e)
+            if a.dump_outputs:
+                state["last_emb"] = e
 
     lib = _capi.lib()
     if os.environ.get("ZT_DUMP_MAPS") and rank == 0:
@@ -470,6 +511,12 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     sys.stderr.write("[bench] %s: host enqueue %.3f ms/step, wall %.3f ms/step\n" % (name, 1e3 * t_host / steps, 1e3 * dt / steps))
+    # --dump-outputs: host copies of what the timed region's last step handed its caller, taken before a later region
+    # overwrites them (written to disk after the JSON line)
+    dump = None
+    if a.dump_outputs and headline:
+        e0_last = (prefill + warmup + steps - 1) * bs
+        dump = last_step_outputs(tgn, state["last_emb"], src[e0_last:e0_last + bs], dst[e0_last:e0_last + bs], bs)
     chain_stats = tgn.embedding_module.tppr_finder.chain_stats() if wl["strategy"] == "streaming" else None
     lib.zt_profile_enable(0)
     # parity_in_run: the state right behind the timed region (T-PPR rows, memory rows of every node the warm-up and timed
@@ -789,6 +836,8 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
         "kernels": kern,
     }
     out["algorithmic"]["executed_mfma_frac_at_value"] = out["algorithmic"]["executed_flops_per_edge"] * value / 1e12 / MFMA_F32_PEAK_TF
+    if dump is not None:
+        out["_dump"] = dump
     return out
 
 
@@ -969,10 +1018,15 @@ def main():
     ap.add_argument("--perm-seed", type=int, default=7,
                     help="shuffle which node id carries which popularity rank (hot rows of the per-node tables are then "
                          "scattered, not contiguous); -1 = id == rank as in rounds 1-2")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed (embeddings, "
+                         "memory rows of its endpoints) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only (gloo, no GPU): checks that --gpus N really starts N ranks")
     a = ap.parse_args()
 
+    if a.dump_outputs and a.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (a rank holds a shard of the rows)")
     # ---- --gpus N without a launcher: this process becomes the parent of N ranks and never touches the GPU ----
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -1019,6 +1073,7 @@ def main():
     cpu_default = {"c5": 48 * 4096, "c3": 40 * 600, "c2": 60 * 200, "c1": 60 * 200, "c4": 20 * 1000}
     ce = a.cpu_edges if a.cpu_edges >= 0 else cpu_default[a.workload]
     out = run_workload(a, a.workload, a.steps, a.warmup, world, rank, device, True, ce, steady=a.steady_steps)
+    dump = out.pop("_dump", None) if out is not None else None
     legs = a.legs
     if legs == "default":
         legs = "c2,c3,c2_train,c4" if a.workload == "c5" else "none"
@@ -1042,6 +1097,9 @@ def main():
         if res:
             out["workloads"] = res
         print(json.dumps(out))
+        sys.stdout.flush()
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     if world > 1:
         dist.destroy_process_group()
 

@@ -1,13 +1,14 @@
 import sys, os, ctypes as C
-sys.path.insert(0, '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import _capi
-_capi.LIB_PATH = '/root/repo/tools/out/libzebra_aggstamp.so'
+_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_aggstamp.so')
 sys.argv = ['bench.py', '--steps', '20', '--warmup', '3', '--prefill-steps', '60', '--no-pipeline', '--cpu-edges', '0', '--workload', sys.argv[1] if len(sys.argv) > 1 else 'c5']
 import runpy
 lib = _capi.lib()
 try:
-    runpy.run_path('/root/repo/bench.py', run_name='__main__')
+    runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='__main__')
 except SystemExit:
     pass
 a = np.zeros(8, np.uint64)

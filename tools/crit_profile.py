@@ -1,9 +1,11 @@
 # Length of the critical section of a hub hop in core clocks (register-held readings, -DZT_CRIT build).
 import sys, ctypes as C
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import _capi
-_capi.LIB_PATH = '/root/repo/tools/out/libzebra_crit.so'
+_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_crit.so')
 from zebra_amd import tppr, synth
 lib = _capi.lib()
 WL = sys.argv[2] if len(sys.argv) > 2 else "c5"        # crit_profile.py [batches] [workload] [batches per launch]

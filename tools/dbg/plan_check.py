@@ -1,6 +1,8 @@
 # debug: dump the plan of one launch and check it against a numpy restatement
 import sys, ctypes as C
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests'); sys.path.insert(0, '/root/repo/tests/golden')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests/golden'))
 import numpy as np, torch
 import inputs as I
 from zebra_amd import _capi

@@ -4,12 +4,13 @@
 import os, sys, runpy, ctypes as C
 os.environ["ZT_CRIT_MULTI"] = "1"
 import numpy as np
-sys.path.insert(0, '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 from zebra_amd import _capi
-_capi.LIB_PATH = '/root/repo/tools/out/libzebra_crit.so'
+_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_crit.so')
 sys.argv = ['bench.py'] + sys.argv[1:]
 try:
-    runpy.run_path('/root/repo/bench.py', run_name='__main__')
+    runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='__main__')
 except SystemExit:
     pass
 lib = _capi.lib()

@@ -5,7 +5,9 @@
 # after the later of its two rows + VIS.  The in-order queue is taken as never behind (it is ~1000 edges ahead on C3).
 #   python tools/exp/chain_dag.py [workload] [batches per launch] [launch index]
 import sys
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np
 from zebra_amd import synth
 WL = sys.argv[1] if len(sys.argv) > 1 else "c3"

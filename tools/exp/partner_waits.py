@@ -4,10 +4,12 @@
 # the last publication.  T-PPR alone, warm state.
 #   python tools/exp/partner_waits.py [launches] [workload] [batches per launch] [v]
 import sys, ctypes as C
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import _capi
-_capi.LIB_PATH = '/root/repo/tools/out/libzebra_stamp.so'
+_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_stamp.so')
 from zebra_amd import tppr, synth
 lib = _capi.lib()
 NB = int(sys.argv[1]) if len(sys.argv) > 1 else 100

@@ -2,10 +2,12 @@
 # 100 MHz clock at dequeue, rows ready, first row stored, end.)  T-PPR alone, C5's stream, warm state.
 #   python tools/exp/task_phases.py [batches]
 import sys, ctypes as C
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import _capi
-_capi.LIB_PATH = '/root/repo/tools/out/libzebra_stamp.so'
+_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_stamp.so')
 from zebra_amd import tppr, synth
 lib = _capi.lib()
 wl = synth.WORKLOADS["c5"]; B = 4096; NB = int(sys.argv[1]) if len(sys.argv) > 1 else 120

@@ -1,6 +1,8 @@
 # C5's T-PPR update alone (product library), NB batches after a short warm-up: for counter collection on k_stream
 import sys, ctypes as C
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import _capi, tppr, synth
 lib = _capi.lib()

@@ -1,7 +1,7 @@
 // The dependency prepass of a big launch as ONE cooperative kernel (round 5): built, bit-exact, NOT faster than the eleven
 // launches -- with fences it costs the aggregation beside it, without them it is slower itself --
 // and therefore not part of the product library: compiled only into variant builds
-//     tools/build_variant.sh prepasscoop "-DZT_PREPASS_COOP_VARIANT -I/root/repo/tools/exp/variants" tppr_prepass.hip
+//     tools/build_variant.sh prepasscoop "-DZT_PREPASS_COOP_VARIANT" tppr_prepass.hip
 // (tppr_prepass.hip includes it inside its anonymous namespace).
 #pragma once
 

@@ -1,7 +1,9 @@
 # Cost of the wide streaming path (csrc/tppr_wide.hpp: one wavefront per model, edges in order) per edge and model, rows full:
 #   python tools/exp/wide_k_cost.py
 import sys, time
-sys.path.insert(0, '/root/repo')
+import os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 from zebra_amd import tppr, synth
 for k in (20, 63, 64, 100, 255):
