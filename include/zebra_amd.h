@@ -70,13 +70,11 @@ int zt_stream_destroy(void *stream);
 #define ZT_CHOICE_GRU 2         /* zt_gru_update: ZT_GRU_TILE, ZT_GRU_SPLIT */
 #define ZT_CHOICE_MESSAGES 3    /* zt_store_messages: ZT_MSG_ONE, ZT_MSG_TWO (batch positions per wavefront) */
 #define ZT_CHOICE_TPPR_CHAIN 4  /* hub chains of zt_tppr_stream: ZT_CHAIN_SINGLE (one position per critical section: the
-                                 * library's pick).  ZT_CHAIN_PAIRED / _SPINE / _DUO were built, are bit-exact and were measured
-                                 * SLOWER: they are compiled into variant builds only
-                                 * (tools/build_variant.sh, sources under tools/exp/variants/); the product library answers
-                                 * ZT_ERR_UNSUPPORTED */
+                                 * library's one mode).  ZT_CHAIN_PAIRED / _SPINE / _DUO were built, bit-exact and measured
+                                 * SLOWER, and were removed: the library answers ZT_ERR_UNSUPPORTED */
 #define ZT_CHOICE_TPPR_PREPASS 5 /* dependency prepass of a launch of more than 4 096 accesses: ZT_PREPASS_LAUNCHES (one kernel per step,
-                                 * eleven launches: the library's pick); ZT_PREPASS_COOP (one cooperative kernel with grid barriers:
-                                 * not faster) likewise in variant builds only */
+                                 * eleven launches: the library's one form); ZT_PREPASS_COOP (one cooperative kernel with grid
+                                 * barriers: not faster) was removed likewise */
 #define ZT_CHOICE_GROUP_RELEASE 6 /* zt_pipeline_*: when the aggregation of a batch may start whose streaming T-PPR update shares a launch
                                  * with other batches.  ZT_RELEASE_MEMBER: as soon as that batch's rows are written (a counter per batch
                                  * inside the launch: the library's pick); ZT_RELEASE_LAUNCH: when the whole launch has ended (an event;
@@ -91,11 +89,11 @@ int zt_stream_destroy(void *stream);
 #define ZT_GRU_TILE 1
 #define ZT_GRU_SPLIT 2
 #define ZT_CHAIN_SINGLE 1
-#define ZT_CHAIN_PAIRED 2
-#define ZT_CHAIN_SPINE 3   /* one wave per chain runs every critical section with the hub's row in registers (tools/exp/variants/tppr_spine.hpp) */
-#define ZT_CHAIN_DUO 4     /* spine mode with the weights' recurrence (network + lane shift) on a wave of its own, ahead of the spine */
+#define ZT_CHAIN_PAIRED 2  /* removed; see DESIGN.md section 5 (two chain positions per critical section) */
+#define ZT_CHAIN_SPINE 3   /* removed; see DESIGN.md section 5 (one wave per chain runs every critical section) */
+#define ZT_CHAIN_DUO 4     /* removed; see DESIGN.md section 5 (spine mode with the weights on a wave of their own) */
 #define ZT_PREPASS_LAUNCHES 1
-#define ZT_PREPASS_COOP 2
+#define ZT_PREPASS_COOP 2  /* removed; see DESIGN.md section 5 */
 #define ZT_RELEASE_MEMBER 1
 #define ZT_RELEASE_LAUNCH 2
 #define ZT_RELEASE_LAUNCH_FULL 3
@@ -131,12 +129,9 @@ int zt_tppr_destroy(zt_tppr *h);
  * together, and runs without hub chains, whose workgroups wait for one another.  New work; the reference
  * is one process on one device (train.py:145-146). */
 int zt_tppr_set_device_share(zt_tppr *h, int32_t n_processes);
-/* Statistics of the hub chains since the last call (synchronises `stream`, clears the counters): out5[0] pairs of
- * consecutive chain positions claimed by one wavefront, [1] pairs applied in ONE critical section, [2] / [3] pairs left
- * to the single hop before / inside the section (a precondition failed), [4] positions taken singly.
- * ZT_CHAIN_SPINE / ZT_CHAIN_DUO: [1] = sections the spine ran, [3] = positions it left to their helpers.
- * All zero in the product library, whose one chain mode keeps no statistics on its hot path (variant builds:
- * tools/exp/variants/tppr_pair.hpp, tppr_spine.hpp; the reference applies the edges one by one, utils/util.py:495-574.) */
+/* Statistics of the hub chains: synchronises `stream` and writes five zeros to out5.  The counters belonged to the
+ * paired / spine / duo chain modes, which were removed; the one chain mode keeps no statistics on
+ * its hot path.  Kept for its callers.  (The reference applies the edges one by one, utils/util.py:495-574.) */
 int zt_tppr_chain_stats(zt_tppr *h, int64_t *out5, void *stream);
 
 /* tppr_finder.reset_tppr (utils/util.py:419-434). */

@@ -62,7 +62,27 @@ def test_round5_entry_points_validate_their_arguments(capi):
     assert lib.zt_exchange_destroy(None) == capi.ZT_OK
 
 
-def test_k_stream_leaves_room_for_the_message_kernels(capi, tmp_path):
+def test_removed_tppr_alternatives_are_refused(capi):
+    """The paired / spine / duo chain modes and the cooperative prepass were removed: asking for one
+    is refused with ZT_ERR_UNSUPPORTED instead of silently running the library's pick; 0 and the one remaining form are
+    accepted."""
+    lib = capi.lib()
+    try:
+        for v in (capi.CHAIN_PAIRED, capi.CHAIN_SPINE, capi.CHAIN_DUO):
+            assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_CHAIN), C.c_int32(v)) == capi.ZT_ERR_UNSUPPORTED, v
+        assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_PREPASS), C.c_int32(capi.PREPASS_COOP)) == capi.ZT_ERR_UNSUPPORTED
+        for v in (0, capi.CHAIN_SINGLE):
+            assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_CHAIN), C.c_int32(v)) == capi.ZT_OK, v
+        for v in (0, capi.PREPASS_LAUNCHES):
+            assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_PREPASS), C.c_int32(v)) == capi.ZT_OK, v
+        with pytest.raises(ValueError):
+            capi.set_kernel_choice(capi.CHOICE_TPPR_CHAIN, capi.CHAIN_PAIRED)
+    finally:
+        assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_CHAIN), C.c_int32(0)) == capi.ZT_OK
+        assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_PREPASS), C.c_int32(0)) == capi.ZT_OK
+
+
+def test_k_stream_register_count_leaves_room_for_the_message_kernels(capi, tmp_path):
     """k_stream's workgroups sit two waves to a SIMD on the T-PPR stream's compute units and the message kernels of the
     step (k_last_pos, k_build_messages2: <= 64 registers) run BESIDE them: that needs 2 x (k_stream's registers, in
     granules of 8) + 64 <= 512, i.e. k_stream <= 224 vector registers.  At 225 (round 6, a replay-server experiment) the message
@@ -79,7 +99,7 @@ def test_k_stream_leaves_room_for_the_message_kernels(capi, tmp_path):
     subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o",
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co], check=True)
     notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    m = re.search(r"\.name:\s+\S*k_streamILi0E\S*.*?\.vgpr_count:\s+(\d+)", notes, re.S)
-    assert m, "k_stream<0> not found in the code object's metadata"
+    m = re.search(r"\.name:\s+\S*8k_streamE\S*.*?\.vgpr_count:\s+(\d+)", notes, re.S)
+    assert m, "k_stream not found in the code object's metadata"
     vgprs = int(m.group(1))
-    assert vgprs <= 224, "k_stream<0> needs %d vector registers: the message kernels no longer fit beside it" % vgprs
+    assert vgprs <= 224, "k_stream needs %d vector registers: the message kernels no longer fit beside it" % vgprs

@@ -12,17 +12,6 @@ from conftest import golden
 pytestmark = pytest.mark.gpu
 
 
-def _variant_choice(which, value):
-    """The chain modes / prepass forms that were measured slower than the library's pick are compiled into VARIANT builds only
-    (tools/build_variant.sh, sources under tools/exp/variants/): the product library refuses them, and their tests run with
-    ZT_TEST_LIB=tools/out/<variant>/libzebra_amd.so (tests/conftest.py)."""
-    from zebra_amd import _capi
-    try:
-        _capi.set_kernel_choice(which, value)
-    except ValueError as exc:
-        pytest.skip("variant build only: %s" % exc)
-
-
 @pytest.fixture(scope="module")
 def zt():
     import torch
@@ -61,132 +50,6 @@ def test_streaming_golden(zt, name):
         st = f.export_state(m)
         gs = {kk: g["state%d_%s" % (m, kk)] for kk in st}
         _cmp_state(st, gs, "model %d" % m)
-
-
-@pytest.mark.parametrize("name", [n for n in I.STREAM_CASES if I.STREAM_CASES[n][5] <= 20])
-def test_streaming_golden_paired_hops(zt, name):
-    """The same goldens with hub chains taking TWO positions per critical section where the preconditions hold
-    (csrc/tppr_pair.hpp; zt_set_kernel_choice(ZT_CHOICE_TPPR_CHAIN, ZT_CHAIN_PAIRED); k <= 20): outputs and state equal the
-    reference's bit for bit -- the hub-tie stream included --, and on the streams with a hub pairs do form."""
-    from zebra_amd import _capi
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_PAIRED)
-    try:
-        test_streaming_golden(zt, name)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
-
-
-@pytest.mark.parametrize("name", list(I.STREAM_CASES))
-def test_streaming_golden_duo(zt, name):
-    """... and in duo mode (ZT_CHAIN_DUO: the weights' recurrence on a wave of its own, running ahead of the spine on the
-    assumption that every test of the lean section passes; the spine voids its records whenever one does not)."""
-    from zebra_amd import _capi
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_DUO)
-    try:
-        test_streaming_golden(zt, name)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
-
-
-@pytest.mark.parametrize("name", list(I.STREAM_CASES))
-def test_streaming_golden_spine(zt, name):
-    """The same goldens with hub chains in spine mode (csrc/tppr_chain.hpp: one wave per chain runs every critical section
-    with the hub's row in registers, the others prepare and finish; ZT_CHAIN_SPINE): bit for bit the reference's."""
-    from zebra_amd import _capi
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_SPINE)
-    try:
-        test_streaming_golden(zt, name)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
-
-
-def test_duo_dense_hub_and_soak(zt, oracle):
-    """Duo mode on the dense-hub graphs and a slice of the randomised soak (restarts of the weights wave: every position the
-    spine leaves to a helper voids its records)."""
-    from zebra_amd import _capi
-    import soak_tppr
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_DUO)
-    try:
-        for seed in (1, 2):
-            test_dense_hub_graph_vs_oracle(zt, oracle, seed)
-        for seed in range(54000, 54040):
-            err = soak_tppr.one(seed, zt, oracle)
-            assert err is None, err
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
-
-
-def test_spine_dense_hub_and_soak(zt, oracle):
-    """Spine mode on the dense-hub graphs (long chains, hub-hub edges, exact ties), a slice of the randomised soak and a hub
-    stream long enough for chains, against the oracle; the chain statistics show the spine running the sections."""
-    from zebra_amd import _capi
-    import soak_tppr
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_SPINE)
-    try:
-        for seed in (1, 2):
-            test_dense_hub_graph_vs_oracle(zt, oracle, seed)
-        for seed in range(53000, 53040):
-            err = soak_tppr.one(seed, zt, oracle)
-            assert err is None, err
-        N, E, k, bs = 400, 8000, 20, 2000
-        rng = np.random.RandomState(5)
-        src = np.where(rng.rand(E) < 0.2, 7, rng.randint(1, N, E)).astype(np.int32)
-        dst = rng.randint(1, N, E).astype(np.int32)
-        neg = rng.randint(1, N, E).astype(np.int32)
-        ts = np.cumsum(rng.rand(E) * 10.0)
-        eidx = np.arange(1, E + 1, dtype=np.int64)
-        f = zt.tppr_finder(N, k, 2, [0.1, 0.1], [0.5, 0.95])
-        o = oracle.TpprOracle(N, k, 2, [0.1, 0.1], [0.5, 0.95])
-        f.chain_stats()
-        for s in range(0, E, bs):
-            nodes = np.concatenate([src[s:s + bs], dst[s:s + bs], neg[s:s + bs]])
-            a = f.streaming_topk(nodes, ts[s:s + bs], eidx[s:s + bs])
-            b = o.streaming_topk(nodes, ts[s:s + bs], eidx[s:s + bs])
-            for x, y in zip(a, b):
-                assert np.array_equal(np.stack(x), np.stack(y))
-        st = f.chain_stats()
-        assert st["pairs_done"] > st["pairs_left_in_section"] > 0, st      # (spine mode: sections run by the spine / left to helpers)
-        for m in range(2):
-            _cmp_state(f.export_state(m), o.export(m), "model %d" % m)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
-
-
-def test_paired_hops_dense_hub_and_soak(zt, oracle):
-    """Paired chain hops on the dense-hub graphs (every edge touches one of a few hubs: long chains, hub-hub edges, exact
-    ties) and a slice of the randomised soak, against the oracle; the chain statistics show pairs completing."""
-    from zebra_amd import _capi
-    import soak_tppr
-    _variant_choice(_capi.CHOICE_TPPR_CHAIN, _capi.CHAIN_PAIRED)
-    try:
-        for seed in (1, 2):
-            test_dense_hub_graph_vs_oracle(zt, oracle, seed)
-        for seed in range(52000, 52040):
-            err = soak_tppr.one(seed, zt, oracle)
-            assert err is None, err
-        # a hub stream long enough for chains: pairs must actually form
-        N, E, k, bs = 400, 8000, 20, 2000
-        rng = np.random.RandomState(5)
-        src = np.where(rng.rand(E) < 0.2, 7, rng.randint(1, N, E)).astype(np.int32)
-        dst = rng.randint(1, N, E).astype(np.int32)
-        neg = rng.randint(1, N, E).astype(np.int32)
-        ts = np.cumsum(rng.rand(E) * 10.0)
-        eidx = np.arange(1, E + 1, dtype=np.int64)
-        f = zt.tppr_finder(N, k, 2, [0.1, 0.1], [0.5, 0.95])
-        o = oracle.TpprOracle(N, k, 2, [0.1, 0.1], [0.5, 0.95])
-        f.chain_stats()
-        for s in range(0, E, bs):
-            nodes = np.concatenate([src[s:s + bs], dst[s:s + bs], neg[s:s + bs]])
-            a = f.streaming_topk(nodes, ts[s:s + bs], eidx[s:s + bs])
-            b = o.streaming_topk(nodes, ts[s:s + bs], eidx[s:s + bs])
-            for x, y in zip(a, b):
-                assert np.array_equal(np.stack(x), np.stack(y))
-        st = f.chain_stats()
-        assert st["pairs_done"] > 0, st
-        for m in range(2):
-            _cmp_state(f.export_state(m), o.export(m), "model %d" % m)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_CHAIN, 0)
 
 
 def test_streaming_variants_golden(zt):
@@ -881,21 +744,6 @@ def test_dependency_plan_matches_restatement(zt, name, batch):
             own_ref[i] = chain_of[b]
     assert np.array_equal(hv, hv_ref) and np.array_equal(own, own_ref)
     f.stream_device(nd, torch.from_numpy(ts[s0:s1].astype(np.float64)).cuda(), ed, 3, True, -1, plan_token=tok)
-
-
-@pytest.mark.parametrize("shape", ["many_big_groups", "one_huge_group", "big_list_overflow"])
-def test_dependency_plan_cooperative_kernel(zt, oracle, shape):
-    """The same plans from k_prepass_coop (ZT_PREPASS_COOP: the ten steps in ONE kernel of 24 workgroups, grid barriers
-    without fences -- the steps hand their arrays over through write-through stores and sc1 loads), and the goldens' state
-    after streaming with it."""
-    from zebra_amd import _capi
-    _variant_choice(_capi.CHOICE_TPPR_PREPASS, _capi.PREPASS_COOP)
-    try:
-        test_dependency_plan_of_large_launches(zt, shape)
-        if shape == "many_big_groups":
-            test_large_single_call_and_epoch_wrap(zt, oracle)
-    finally:
-        _capi.set_kernel_choice(_capi.CHOICE_TPPR_PREPASS, 0)
 
 
 @pytest.mark.parametrize("shape", ["many_big_groups", "one_huge_group", "big_list_overflow", "small_fused"])

@@ -36,8 +36,8 @@ SYMBOLS = [
 CHOICE_AGGREGATE, CHOICE_EMBED_OUT, CHOICE_GRU, CHOICE_MESSAGES, CHOICE_TPPR_CHAIN, CHOICE_TPPR_PREPASS = 0, 1, 2, 3, 4, 5
 CHOICE_GROUP_RELEASE = 6
 RELEASE_MEMBER, RELEASE_LAUNCH, RELEASE_LAUNCH_FULL = 1, 2, 3
-PREPASS_LAUNCHES, PREPASS_COOP = 1, 2
-CHAIN_SINGLE, CHAIN_PAIRED, CHAIN_SPINE, CHAIN_DUO = 1, 2, 3, 4
+PREPASS_LAUNCHES, PREPASS_COOP = 1, 2                          # PREPASS_COOP: removed; see DESIGN.md section 5
+CHAIN_SINGLE, CHAIN_PAIRED, CHAIN_SPINE, CHAIN_DUO = 1, 2, 3, 4   # PAIRED / SPINE / DUO: removed; see DESIGN.md section 5
 AGG_GENERIC = 1
 OUT_TILED, OUT_LATENCY, OUT_PERSIST = 1, 2, 3
 GRU_TILE, GRU_SPLIT = 1, 2

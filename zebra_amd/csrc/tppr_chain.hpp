@@ -6,18 +6,6 @@
 
 namespace {
 
-// chain statistics (ctl[6 ..], zt_tppr_chain_stats): pairs claimed / completed in one section / left to the single hop in
-// preparation / in the section; hops taken singly.  Spine mode counts the sections the spine ran under ST_PAIR_DONE and the
-// positions it left to their helpers under ST_PAIR_BAIL_CRIT.
-#ifdef ZT_PAIR_STAT
-__device__ long long g_pstat[16];      // diagnostic build: clocks in preparation / critical sections / waiting / off-chain halves, pairs
-#endif
-enum { ST_PAIR_CLAIM = 6, ST_PAIR_DONE = 7, ST_PAIR_BAIL_PREP = 8, ST_PAIR_BAIL_CRIT = 9, ST_SINGLE = 10 };
-__device__ __forceinline__ void chain_stat(int *ctl, int lane, int which, int n = 1)
-{
-    if (lane == 0) __hip_atomic_fetch_add(ctl + which, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // One hop of a hub chain, the common case, as a function of its own: the hub's row comes through the mailbox from the
 // chain's previous edge, the partner is another node.  The chain applies the HUB's update only (the rest of the edge is
 // process_chain_partner's), so this is process_edge's mailbox path with everything else taken out -- no row selection by
@@ -34,15 +22,9 @@ struct HopRec {
                        // row is version wo_p there and that chain applies its update --, else -1
 };
 
-#ifdef ZT_CHAIN_VARIANTS
-// spine / duo mode (one wave runs every critical section; the weights' recurrence on a wave of its own): measured slower,
-// kept out of the product -- tools/exp/variants/tppr_spine.hpp, variant builds only
-#include "tppr_spine.hpp"
-#endif
-
 __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h, const StreamArgs &A, WaveLds &L, int lane, int i, int mo, Mail *mail,
                                  long long hub, int prev_edge, int next_edge, int tpos, ChainHint *hint, int chain_idx,
-                                 const HopRec &rec, const bool spine = false)
+                                 const HopRec &rec)
 {
     if (prev_edge < 0 || h.k > REG_K_MAX) return false;
     const int k = h.k;
@@ -70,7 +52,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     MailSlot *in_slot = &mail->slot[(tpos - 1) % MAIL_R], *out_slot = &mail->slot[tpos % MAIL_R];
     PreScale pre_scale;
     pre_scale.valid = false;
-#ifndef ZT_CHAIN_VARIANTS
     // the norm the hub's row will arrive with and the scale factors that follow from it: worked out for every position when
     // the workgroup started (zt_tppr::hubscale, k_stream) -- four doubles, on their way beside the partner's row; the lean
     // section still holds the norm that ARRIVES against this one, bit for bit
@@ -80,37 +61,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
         pre_scale.norm = sn; pre_scale.norm_next = sn1; pre_scale.scale_s1 = s1; pre_scale.scale_s2 = s2;
         pre_scale.valid = sn != 0.0;
     }
-#else
-    // (the two float64 divisions of the scale factors: while the partner's row is on its way)
-    // the norm the hub's row will arrive with: norm <- norm * beta + beta from hop to hop, starting from this wave's own
-    // last hop or, if that is long ago (or never was), from the latest kept set in the ring
-    double pn = 0.0;
-    int psteps = -1;
-    if (hint->tpos >= 0 && tpos - hint->tpos <= 24) { pn = hint->norm_out; psteps = tpos - hint->tpos - 1; }
-    else {
-        for (int d = 2; d < MAIL_R && tpos - d >= 0; ++d) {       // (the slot of position tpos - d is not rewritten before my hop)
-            const MailSlot *sl = &mail->slot[(tpos - d) % MAIL_R];
-            if (lds_load_seq(&sl->seq_set) == tpos - d + 1) {
-                double hn; int a0, a1, a2, a3; unsigned a4;
-                mail_hdr_read(sl, hn, a0, a4, a1, a2, a3);
-                pn = hn; psteps = d - 1;
-                break;
-            }
-        }
-    }
-    auto set_scale = [&]() {
-        for (int q = 0; q < psteps; ++q) pn = pn * beta + beta;
-        if (pn != 0.0) {
-            const double nn = pn * beta + beta;
-            pre_scale.norm = pn;
-            pre_scale.norm_next = nn;
-            pre_scale.scale_s1 = pn / nn * beta;
-            pre_scale.scale_s2 = beta / nn * (1.0 - alpha);
-            pre_scale.valid = true;
-        }
-    };
-    if (psteps >= 0) set_scale();
-#endif
     if (row_from_raw(praw, k, lane, psrc.expect, rp) != psrc.expect && psrc.polled)
         if (!load_row_wait_at(psrc.base, k, lane, psrc.expect, rp, h.ctl + 2, (int)pnode, psrc.aux(m), psrc.version)) wl_fail |= 2;
     // ---- while the hub's row is on its way: everything that depends on the partner only ----
@@ -151,46 +101,8 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     crit_t[9] = !pre_scale.valid ? 7 : (pre_hash == 2 ? 8 : (!pre_b.ok ? 9 : 0));     // why the partner's side is not prepared
     crit_t[13] = (long long)ld_agent(h.ctl + 1) * 100000 + i;    // head of the general queue (task index) when this hop was ready, and its edge
 #endif
-    // ---- spine mode: the prepared side goes to the spine wave, which runs the critical section with the hub's row in its
-    // ---- registers (chain_spine) and says so -- or leaves the hop to this wave, the old way ----
-    PrepHdr *P = &mail->prep[tpos % PREP_R];
-#ifdef ZT_CHAIN_VARIANTS
-    bool by_spine = false;
-    if (spine) {
-        if (!pre_scale.valid && pre_hash != 2) {
-            // no norm to start from (this wave's first hop of the launch): the latest kept set within the ring's reach --
-            // positions before mine are published without me, the spine cannot pass mine
-            unsigned spins = 0;
-            bool found = false;
-            while (!found) {
-                for (int d = 1; d < MAIL_R && tpos - d >= 0; ++d) {
-                    const MailSlot *sl = &mail->slot[(tpos - d) % MAIL_R];
-                    if (lds_load_seq(&sl->seq_set) == tpos - d + 1) {
-                        double hn; int a0, a1, a2, a3; unsigned a4;
-                        mail_hdr_read(sl, hn, a0, a4, a1, a2, a3);
-                        pn = hn; psteps = d - 1; found = true;
-                        break;
-                    }
-                }
-                if (found) break;
-                __builtin_amdgcn_s_sleep(4);
-                if ((++spins & 1023u) == 0 && launch_failed(h.ctl + 2)) break;
-            }
-            if (found) {
-                set_scale();
-                if (pre_scale.valid) prepare_b(lane, k, alpha, rp, nkey, tnow, pre_scale, pre_b, h2slot);
-            }
-        }
-        spine_post(P, L, lane, tpos, pre_b, pre_scale, nkey, tnow, lenp, pre_hash);
-        by_spine = spine_wait_res(&P->res, tpos, h.ctl + 2, i) == tpos + 1;
-
-    }
-#else
-    constexpr bool by_spine = false;                 // (spine / duo mode: variant builds only, tools/exp/variants/tppr_spine.hpp)
-    (void)spine;
-#endif
     // waves whose turn is two or more hops away doze (see process_edge)
-    if (!by_spine && tpos >= 2) {
+    if (tpos >= 2) {
         const int *far = &mail->slot[(tpos - 2) % MAIL_R].seq_set;
         unsigned spins = 0;
         while (lds_load_seq(far) != tpos - 1 && lds_load_seq(&in_slot->seq_set) != tpos) {
@@ -198,24 +110,8 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             if ((++spins & 1023u) == 0 && launch_failed(h.ctl + 2)) break;
         }
     }
-    // (a wave's first hop of a launch has no norm to start from until somebody has published: the kept set two positions
-    //  back is out now -- its successor is in its critical section --, which leaves time to prepare the partner's side)
-#ifdef ZT_CHAIN_VARIANTS
-    if (!spine && !pre_scale.valid && tpos >= 2 && pre_hash != 2) {
-        const MailSlot *sl = &mail->slot[(tpos - 2) % MAIL_R];
-        if (lds_load_seq(&sl->seq_set) == tpos - 1) {
-            double hn; int a0, a1, a2, a3; unsigned a4;
-            mail_hdr_read(sl, hn, a0, a4, a1, a2, a3);
-            pn = hn; psteps = 1;
-            set_scale();
-            if (pre_scale.valid) prepare_b(lane, k, alpha, rp, nkey, tnow, pre_scale, pre_b, h2slot);
-        }
-    }
-#endif
-    if (!by_spine) {
-        if (!wait_seq(&in_slot->seq_set, tpos, h.ctl + 2, i, prev_edge, true)) wl_fail |= 16;
-        __builtin_amdgcn_s_setprio(3);
-    }
+    if (!wait_seq(&in_slot->seq_set, tpos, h.ctl + 2, i, prev_edge, true)) wl_fail |= 16;
+    __builtin_amdgcn_s_setprio(3);
     CRIT(0);
     HSTAMP(2);
     Row rh;
@@ -271,8 +167,7 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
 #define LEANC(c) do { } while (0)
 #endif
     bool lean_done = false;
-#ifndef ZT_NO_LEAN
-    if (pre_b.ok && (by_spine || !spine)) {          // (a hop the spine left to this wave failed one of the section's tests already)
+    if (pre_b.ok) {
         lean_done = [&]() -> bool {
             // the header: one 16-byte LDS word, its four words straight to scalar registers (the fields come apart on the scalar unit)
             const mail_v4u hdr = *reinterpret_cast<const mail_v4u *>(&in_slot->norm);
@@ -280,28 +175,18 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             u64 ckey = pre_b.cb_key;
             double cts = pre_b.cb_ts, cw = pre_b.cb_w, hw = 0.0;
             if (low) { ckey = in_slot->key[lane]; cts = in_slot->ts[lane]; hw = in_slot->w[lane]; }
-            const int fs = by_spine ? 0 : lds_load_seq(&out_slot->seq_free);
+            const int fs = lds_load_seq(&out_slot->seq_free);
             const unsigned hz = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.z);
             const unsigned hunc = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.w);
             const int n1 = (int)(hz & 0xffu), munc = (int)((hz >> 8) & 0xffu), nalt = (int)((hz >> 16) & 0xffu);
-            if (!by_spine) {   // sorted arrangement, predicted norm (bit patterns on the scalar unit: both are finite and positive)
-                const unsigned h0 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.x), h1 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.y);
-                if ((hz >> 24) == 0u || h0 != pn0 || h1 != pn1 || (h0 | h1) == 0u) { LEANC(1); return false; }
-            }
+            // sorted arrangement, predicted norm (bit patterns on the scalar unit: both are finite and positive)
+            const unsigned h0 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.x), h1 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.y);
+            if ((hz >> 24) == 0u || h0 != pn0 || h1 != pn1 || (h0 | h1) == 0u) { LEANC(1); return false; }
             const int nb = pre_b.nb, n = n1 + nb, drop = n - k;
-            if (!by_spine && (n1 <= 0 || drop <= 0)) { LEANC(2); return false; }
+            if (n1 <= 0 || drop <= 0) { LEANC(2); return false; }
             const bool table = lenp > 0;
             u64 S;
             int both;
-            if (by_spine) {
-                // the spine ran the section on exactly these inputs (its tests passed): the candidates as they stood, and its
-                // ranks -- the rest of this hop is the off-chain half
-                if (low) cw = hw * pre_scale.scale_s1;
-                const u64 sv = P->S;
-                S = ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sv >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sv);
-                const int sp_ = L.sort.r[lane];                    // (sorted position; the rank is the start of its run)
-                both = (63 - __builtin_clzll(S & (((u64)2 << sp_) - 1ull))) | (sp_ << 8);
-            } else {
             if (munc > 0) {
                 // members of a straddling run that were not picked may turn out to be in the row (see below)
                 const u64 alt = in_slot->alt_key[lane & 31];
@@ -339,7 +224,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
                 bad = bad || (in1 && cand >= 0 && kj == ckey && tj == cts);
             }
             if (__ballot(bad) != 0ull) { LEANC(4); return false; }
-            }   // (!by_spine)
             CRIT(1);
             const int lt = both & 0xff, sp = both >> 8;
             const bool full = (S >> drop) & 1ull;               // the cut falls on a run start: exactly k candidates are kept
@@ -348,7 +232,7 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             const int mode = full ? (claimed == kmask ? FR_RANKS : FR_TIES) : FR_STRADDLE;
             const u64 lowdrop = ((u64)2 << drop) - 1ull;        // positions 0 .. drop
             const int rsG = 63 - __builtin_clzll(S & lowdrop);  // start of the run that holds position `drop`
-            if (!by_spine && munc > 0) {
+            if (munc > 0) {
                 // a picked member of the previous hop's straddling run that is kept here (or ties with the cut) needs the
                 // previous hop's replay first: the general code waits for it
                 const int thr = full ? drop : rsG;
@@ -368,7 +252,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             const bool kept = (unsigned)ps < (unsigned)k;       // (padding lanes sort behind position n-1)
             const double nn = pre_scale.norm_next;
             const bool fin = mode == FR_RANKS;                   // (then uo == 0: all kept weights distinct)
-            if (!by_spine) {
             if (tpos >= MAIL_R && fs != tpos - MAIL_R + 1) {
                 if (!wait_seq(&out_slot->seq_free, tpos - MAIL_R + 1, h.ctl + 2, i, -1)) wl_fail |= 64;
             }
@@ -383,7 +266,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             CRIT(3);
             HSTAMP(4);
             __builtin_amdgcn_s_setprio(0);                       // the rest of this hop is off the chain
-            }
             // ---- what the tail needs ----
             if (table && lane < lenp) L.htab[pre_b.h2] = -1;     // the table is clean again
             hub_unc = hunc; hub_munc = munc; hub_nalt = nalt;
@@ -406,7 +288,6 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             return true;
         }();
     }
-#endif
     if (!lean_done) {
     // ---- the hub's row: one batch of LDS reads ----
     mail_hdr_read(in_slot, rh.norm, rh.len, hub_unc, hub_munc, hub_nalt, hub_sorted);

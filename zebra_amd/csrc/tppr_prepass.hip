@@ -17,14 +17,11 @@ namespace {
 // K0: a set is planned afresh: the status of the launch it last served is history (the handle's latch keeps it)
 __global__ void k_plan_begin(int *ctl) { if (threadIdx.x == 0) { ctl[2] = 0; ctl[13] = 0; } }
 
-// Accesses to the arrays one prepass step leaves for the next.  SC = false: plain (the steps are kernels of their own, or
-// one workgroup).  SC = true (k_prepass_coop): relaxed agent-scope accesses -- write-through stores, loads that do not
-// trust this compute unit's L1 or a remote XCD's copy -- so that a grid barrier needs no fence: a thread's stores have
-// been acknowledged when it arrives (s_waitcnt vmcnt(0)), and what it loads afterwards comes from where they went.
-template <bool SC> __device__ __forceinline__ int pre_ld(const int *p) { return SC ? ld_agent(p) : *p; }
-template <bool SC> __device__ __forceinline__ void pre_st(int *p, int v) { if (SC) st_agent(p, v); else *p = v; }
+// Accesses to the arrays one prepass step leaves for the next (the steps are kernels of their own, or one workgroup:
+// plain loads and stores).  Kept as calls: written as direct indexing the same steps compile to other branch layouts.
+__device__ __forceinline__ int pre_ld(const int *p) { return *p; }
+__device__ __forceinline__ void pre_st(int *p, int v) { *p = v; }
 
-template <bool SC = false>
 __device__ __forceinline__ void d_count(int a, const int *__restrict__ nodes, const long long *__restrict__ eidx,
                                         long long role_stride, int B, int n_roles, long long N, int *cnt, int *slot,
                                         int *ctl, int *latch)
@@ -40,14 +37,14 @@ __device__ __forceinline__ void d_count(int a, const int *__restrict__ nodes, co
     if (!ok) {
         atomicExch(&ctl[2], ZT_ERR_RANGE);
         latch_failure(latch, ZT_ERR_RANGE);
-        pre_st<SC>(slot + a, -1);
+        pre_st(slot + a, -1);
         return;
     }
     bool shadow = false;
     if (r >= 1) shadow = nodes[i] == x;                                    // same as the source
     if (r == 2) shadow = shadow || nodes[role_stride + i] == x;           // same as the destination
-    if (shadow) { pre_st<SC>(slot + a, -2); return; }
-    pre_st<SC>(slot + a, atomicAdd(&cnt[x], 1));
+    if (shadow) { pre_st(slot + a, -2); return; }
+    pre_st(slot + a, atomicAdd(&cnt[x], 1));
 }
 
 __global__ void k_count(const int *__restrict__ nodes, const long long *__restrict__ eidx, long long role_stride,
@@ -57,23 +54,22 @@ __global__ void k_count(const int *__restrict__ nodes, const long long *__restri
 }
 
 // K2: the first access of each node reserves a contiguous range of `list`.
-template <bool SC = false>
 __device__ __forceinline__ void d_reserve(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                           const int *cnt, int *off, const int *slot, int *ctl, int *hot_node, int *hot_cnt,
                                           int big_min)
 {
     if (a >= B * n_roles) return;
-    if (pre_ld<SC>(slot + a) == 0) {
+    if (pre_ld(slot + a) == 0) {
         const int x = nodes[(long long)(a / B) * role_stride + a % B];
-        const int c = pre_ld<SC>(cnt + x);
-        pre_st<SC>(off + x, atomicAdd(&ctl[0], c));
+        const int c = pre_ld(cnt + x);
+        pre_st(off + x, atomicAdd(&ctl[0], c));
         if (c >= big_min && c <= DEPS_SORT_MAX) {  // a big group: its dependencies come from a sort (d_deps_group)
             const int bi = atomicAdd(&ctl[5], 1);
-            if (bi < MAX_BIG) pre_st<SC>(hot_node + MAX_HOT + bi, x);
+            if (bi < MAX_BIG) pre_st(hot_node + MAX_HOT + bi, x);
         }
         if (c >= HOT_MIN) {                        // hub candidate
             const int hi = atomicAdd(&ctl[3], 1);
-            if (hi < MAX_HOT) { pre_st<SC>(hot_node + hi, x); pre_st<SC>(hot_cnt + hi, c); }
+            if (hi < MAX_HOT) { pre_st(hot_node + hi, x); pre_st(hot_cnt + hi, c); }
         }
     }
 }
@@ -101,30 +97,29 @@ __device__ __forceinline__ int d_chain_budget(int top, int grid, int tasks, int 
 }
 
 // K2b (one wavefront pair): keep the MAX_CHAINS most-touched candidates as chains.
-template <bool SC = false>
 __device__ __forceinline__ void d_hot_select(int t, int *ctl, const int *hot_node, const int *hot_cnt, int *chain_of,
                                              int *chain_node, int *chain_len, int max_chains, int grid, int tasks, int n_models)
 {
     if (t >= MAX_HOT) return;                      // MAX_HOT threads take part
-    int nh = pre_ld<SC>(ctl + 3);
+    int nh = pre_ld(ctl + 3);
     nh = nh < MAX_HOT ? nh : MAX_HOT;
     {   // the chain budget of this launch (every thread works it out alike: at most MAX_HOT reads)
         int top = 0;
-        for (int q = 0; q < nh; ++q) { const int cq = pre_ld<SC>(hot_cnt + q); top = cq > top ? cq : top; }
+        for (int q = 0; q < nh; ++q) { const int cq = pre_ld(hot_cnt + q); top = cq > top ? cq : top; }
         max_chains = d_chain_budget(top, grid, tasks, n_models, max_chains);
     }
-    if (t < MAX_CHAINS) pre_st<SC>(chain_len + t, 0);
-    if (pre_ld<SC>(ctl + 2) == ZT_ERR_RANGE) { if (t == 0) pre_st<SC>(ctl + 4, 0); return; }
+    if (t < MAX_CHAINS) pre_st(chain_len + t, 0);
+    if (pre_ld(ctl + 2) == ZT_ERR_RANGE) { if (t == 0) pre_st(ctl + 4, 0); return; }
     int rank = 0;
     if (t < nh) {
-        const int c = pre_ld<SC>(hot_cnt + t), x = pre_ld<SC>(hot_node + t);
+        const int c = pre_ld(hot_cnt + t), x = pre_ld(hot_node + t);
         for (int q = 0; q < nh; ++q) {
-            const int cq = pre_ld<SC>(hot_cnt + q);
-            rank += (cq > c || (cq == c && pre_ld<SC>(hot_node + q) < x)) ? 1 : 0;
+            const int cq = pre_ld(hot_cnt + q);
+            rank += (cq > c || (cq == c && pre_ld(hot_node + q) < x)) ? 1 : 0;
         }
-        if (rank < max_chains) { pre_st<SC>(chain_of + x, rank); pre_st<SC>(chain_node + rank, x); }
+        if (rank < max_chains) { pre_st(chain_of + x, rank); pre_st(chain_node + rank, x); }
     }
-    if (t == 0) pre_st<SC>(ctl + 4, nh < max_chains ? nh : max_chains);
+    if (t == 0) pre_st(ctl + 4, nh < max_chains ? nh : max_chains);
 }
 
 
@@ -140,21 +135,20 @@ __global__ void k_hot_select(int *ctl, const int *hot_node, const int *hot_cnt, 
 // chains -- each chain applies its own hub's update and takes the other hub's row from the other chain's versions; the
 // chain of the more-touched hub is the edge's OWNER: its partner task in the general queue emits the edge's rows.
 // A chain holds CH_MAX edges; a hub's later edges go through the general queue and the row in `rows`.
-template <bool SC = false>
 __device__ __forceinline__ void d_own(int i, const int *__restrict__ nodes, long long role_stride, int B, const int *cnt,
                                       const int *slot, const int *wo, const int *chain_of, int *chain_len, int *chain_edges,
                                       int *owner_of)
 {
     if (i >= B) return;
     int owner = -1;
-    if (pre_ld<SC>(slot + i) >= 0 && pre_ld<SC>(slot + B + i) != -1) {        // valid edge
+    if (pre_ld(slot + i) >= 0 && pre_ld(slot + B + i) != -1) {        // valid edge
         const int u = nodes[i], v = nodes[role_stride + i];
-        const int cu = pre_ld<SC>(chain_of + u), cv = v != u ? pre_ld<SC>(chain_of + v) : -1;
-        const int pu = pre_ld<SC>(wo + i), pv = pre_ld<SC>(wo + B + i);
+        const int cu = pre_ld(chain_of + u), cv = v != u ? pre_ld(chain_of + v) : -1;
+        const int pu = pre_ld(wo + i), pv = pre_ld(wo + B + i);
         const bool in_u = cu >= 0 && pu < CH_MAX, in_v = cv >= 0 && pv < CH_MAX;
         if (in_u) { chain_edges[cu * CH_MAX + pu] = i; atomicMax(&chain_len[cu], pu + 1); }
         if (in_v) { chain_edges[cv * CH_MAX + pv] = i; atomicMax(&chain_len[cv], pv + 1); }
-        if (in_u && (!in_v || pre_ld<SC>(cnt + u) >= pre_ld<SC>(cnt + v))) owner = cu;
+        if (in_u && (!in_v || pre_ld(cnt + u) >= pre_ld(cnt + v))) owner = cu;
         else if (in_v) owner = cv;
     }
     owner_of[i] = owner;
@@ -168,17 +162,16 @@ __global__ void k_own(const int *__restrict__ nodes, long long role_stride, int 
 
 // K2d: per access, the chain that holds the node's row by version (zt_tppr::hv): a writer access that is a chain position,
 // a reader access (negative sample) up to the chain's last version.  (After K2c: chain_len is final.)
-template <bool SC = false>
 __device__ __forceinline__ void d_hubacc(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                          const int *slot, const int *wo, const int *chain_of, const int *chain_len, int *hv)
 {
     if (a >= B * n_roles) return;
     int c = -1;
-    if (pre_ld<SC>(slot + a) >= 0) {
+    if (pre_ld(slot + a) >= 0) {
         const int r = a / B;
-        const int cc = pre_ld<SC>(chain_of + nodes[(long long)r * role_stride + a % B]);
+        const int cc = pre_ld(chain_of + nodes[(long long)r * role_stride + a % B]);
         if (cc >= 0) {
-            const int len = pre_ld<SC>(chain_len + cc), w = pre_ld<SC>(wo + a);
+            const int len = pre_ld(chain_len + cc), w = pre_ld(wo + a);
             if (len > 0 && (r < 2 ? w < CH_MAX : w <= len)) c = cc;
         }
     }
@@ -192,14 +185,13 @@ __global__ void k_hubacc(const int *__restrict__ nodes, long long role_stride, i
 }
 
 // K3: scatter accesses into their node's range, encoded (edge << 2) | role.
-template <bool SC = false>
 __device__ __forceinline__ void d_fill(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                        const int *off, const int *slot, int *list)
 {
     if (a >= B * n_roles) return;
-    const int s = pre_ld<SC>(slot + a);
+    const int s = pre_ld(slot + a);
     if (s < 0) return;
-    pre_st<SC>(list + pre_ld<SC>(off + nodes[(long long)(a / B) * role_stride + a % B]) + s, ((a % B) << 2) | (a / B));   // (edge << 2) | role
+    pre_st(list + pre_ld(off + nodes[(long long)(a / B) * role_stride + a % B]) + s, ((a % B) << 2) | (a / B));   // (edge << 2) | role
 }
 
 __global__ void k_fill(const int *__restrict__ nodes, long long role_stride, int B, int n_roles, const int *off,
@@ -212,15 +204,14 @@ __global__ void k_fill(const int *__restrict__ nodes, long long role_stride, int
 //   wo    = number of writer accesses by earlier edges  (= ordinal of the last earlier writer)
 //   pflag = the latest earlier edge touching the node, if that access was a reader, else -1
 //   nxt   = how many later edges touch the node (the length of the chain waiting for this access)
-template <bool SC = false>
 __device__ __forceinline__ void d_deps(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                        const int *cnt, const int *off, const int *slot, const int *list, int *wo,
                                        int *pflag, int *nxt, int n_big, int big_min)
 {
     if (a >= B * n_roles) return;
-    if (pre_ld<SC>(slot + a) < 0) { pre_st<SC>(wo + a, 0); pre_st<SC>(pflag + a, -1); pre_st<SC>(nxt + a, 0); return; }
+    if (pre_ld(slot + a) < 0) { pre_st(wo + a, 0); pre_st(pflag + a, -1); pre_st(nxt + a, 0); return; }
     const int x = nodes[(long long)(a / B) * role_stride + a % B];
-    const int o = pre_ld<SC>(off + x), c = pre_ld<SC>(cnt + x);
+    const int o = pre_ld(off + x), c = pre_ld(cnt + x);
     if (c >= big_min && c <= DEPS_SORT_MAX && n_big <= MAX_BIG) return;    // d_deps_group's (every big group is on the list)
     const int me = a % B;
     int best = -1, best_role = 0, writers = 0, nx = 0;
@@ -229,7 +220,7 @@ __device__ __forceinline__ void d_deps(int a, const int *__restrict__ nodes, lon
     for (int p0 = 0; p0 < c; p0 += 16) {
         int b[16];
 #pragma unroll
-        for (int t = 0; t < 16; ++t) b[t] = pre_ld<SC>(list + o + ((p0 + t) < c ? (p0 + t) : (c - 1)));
+        for (int t = 0; t < 16; ++t) b[t] = pre_ld(list + o + ((p0 + t) < c ? (p0 + t) : (c - 1)));
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             if (p0 + t >= c) break;
@@ -242,9 +233,9 @@ __device__ __forceinline__ void d_deps(int a, const int *__restrict__ nodes, lon
             }
         }
     }
-    pre_st<SC>(wo + a, writers);
-    pre_st<SC>(nxt + a, nx);
-    pre_st<SC>(pflag + a, (best >= 0 && best_role == 2) ? best : -1);
+    pre_st(wo + a, writers);
+    pre_st(nxt + a, nx);
+    pre_st(pflag + a, (best >= 0 && best_role == 2) ? best : -1);
 }
 
 __global__ void k_deps(const int *__restrict__ nodes, long long role_stride, int B, int n_roles, const int *cnt,
@@ -261,14 +252,13 @@ __global__ void k_deps(const int *__restrict__ nodes, long long role_stride, int
 // after a sort by value the member at position p has exactly p earlier edges: wo = writers among [0, p) (a prefix
 // count), the latest earlier access is the member at p - 1, nxt = c - 1 - p.  One workgroup sorts the group in LDS
 // (bitonic, padded to a power of two) and scans the writer flags.  `s` holds DEPS_SORT_MAX ints, `t` two per thread.
-template <bool SC = false>
 __device__ __forceinline__ void d_deps_group(int tid, int nthr, int x, int B, const int *cnt, const int *off, const int *list,
                                              int *wo, int *pflag, int *nxt, int *s, int *t)
 {
-    const int c = pre_ld<SC>(cnt + x), o = pre_ld<SC>(off + x);
+    const int c = pre_ld(cnt + x), o = pre_ld(off + x);
     int P = 64;
     while (P < c) P <<= 1;
-    for (int i = tid; i < P; i += nthr) s[i] = i < c ? pre_ld<SC>(list + o + i) : 0x7fffffff;
+    for (int i = tid; i < P; i += nthr) s[i] = i < c ? pre_ld(list + o + i) : 0x7fffffff;
     __syncthreads();
     for (int k2 = 2; k2 <= P; k2 <<= 1)
         for (int j = k2 >> 1; j > 0; j >>= 1) {
@@ -299,10 +289,10 @@ __device__ __forceinline__ void d_deps_group(int tid, int nthr, int x, int B, co
         const int p = b0 + q;
         if (p >= c) break;
         const int v = s[p], e = v >> 2, r = v & 3, a = r * B + e;
-        pre_st<SC>(wo + a, run);
+        pre_st(wo + a, run);
         run += r < 2 ? 1 : 0;
-        pre_st<SC>(nxt + a, c - 1 - p);
-        pre_st<SC>(pflag + a, (p > 0 && (s[p - 1] & 3) == 2) ? (s[p - 1] >> 2) : -1);
+        pre_st(nxt + a, c - 1 - p);
+        pre_st(pflag + a, (p > 0 && (s[p - 1] & 3) == 2) ? (s[p - 1] >> 2) : -1);
     }
     __syncthreads();                                   // (the arrays are reused for the next group)
 }
@@ -319,13 +309,12 @@ __global__ __launch_bounds__(DEPS_BIG_THREADS) void k_deps_big(int B, const int 
 }
 
 // K5: restore the per-node counters and the control words for the next call.
-template <bool SC = false>
 __device__ __forceinline__ void d_cleanup(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                           const int *slot, int *cnt, int *ctl, const int *hot_node, int *chain_of)
 {
-    if (a < MAX_HOT && a < pre_ld<SC>(ctl + 3)) pre_st<SC>(chain_of + pre_ld<SC>(hot_node + a), -1);
+    if (a < MAX_HOT && a < pre_ld(ctl + 3)) pre_st(chain_of + pre_ld(hot_node + a), -1);
     if (a >= B * n_roles) return;
-    if (pre_ld<SC>(slot + a) == 0) pre_st<SC>(cnt + nodes[(long long)(a / B) * role_stride + a % B], 0);
+    if (pre_ld(slot + a) == 0) pre_st(cnt + nodes[(long long)(a / B) * role_stride + a % B], 0);
 }
 
 __global__ void k_cleanup(const int *__restrict__ nodes, long long role_stride, int B, int n_roles, const int *slot,
@@ -378,22 +367,7 @@ __global__ __launch_bounds__(PRE_THREADS) void k_prepass_fused(
     if (tid < 6 && tid != 2 && tid != 4) ctl[tid] = 0;                           // k_reset_ctl
 }
 
-
-#ifdef ZT_PREPASS_COOP_VARIANT
-// the whole prepass as ONE cooperative kernel: measured no faster, kept out of the product (tools/exp/variants/tppr_prepass_coop.hpp)
-#include "tppr_prepass_coop.hpp"
-#endif
-
 }  // namespace
-
-bool zt::tppr_prepass_coop_compiled()
-{
-#ifdef ZT_PREPASS_COOP_VARIANT
-    return true;
-#else
-    return false;
-#endif
-}
 
 // CUs a stream may use (CU-masked streams: the size of the mask)
 int zt::tppr_stream_cus(const zt_tppr *h, hipStream_t s)
@@ -470,16 +444,6 @@ int zt::tppr_plan_chunk(zt_tppr *h, int q, const int32_t *nodes, const long long
                                                   h->chain_of, h->chain_node, h->chain_len, h->chain_edges, h->owner_of,
                                                   h->hv, max_chains, big_min, budget_grid, n_models);
         ZT_PROF_END(s, P_PREPASS);
-#ifdef ZT_PREPASS_COOP_VARIANT
-    } else if (zt::kernel_choice(ZT_CHOICE_TPPR_PREPASS) == ZT_PREPASS_COOP) {       // (measured no faster, and its fences cost the aggregation: on request)
-        ZT_PROF_BEGIN(s, P_PREPASS);
-        k_prepass_coop<<<COOP_WGS, COOP_THREADS, 0, s>>>(nodes, eidx, role_stride, B, n_roles, h->N, h->cnt, h->slot, h->off, h->list,
-                                                         h->wo, h->pflag, h->nxt, h->ctl, h->latch_dev, h->hot_node, h->hot_cnt,
-                                                         h->chain_of, h->chain_node, h->chain_len, h->chain_edges, h->owner_of,
-                                                         h->hv, max_chains, big_min, budget_grid, n_models, P.bar_base);
-        P.bar_base += (unsigned)COOP_BARRIERS * COOP_WGS;
-        ZT_PROF_END(s, P_PREPASS);
-#endif
     } else {
         ZT_PROF_BEGIN(s, P_PREPASS);
         k_plan_begin<<<1, 64, 0, s>>>(h->ctl);

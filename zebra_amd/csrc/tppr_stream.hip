@@ -42,11 +42,7 @@
 //     quicksort replay on the ranks when ties decide, LDS / sequential replays
 //     for more than 64 candidates (numba_sort.hpp).
 #include "numba_sort.hpp"
-#ifdef ZT_CHAIN_VARIANTS                 // variant builds only (tools/build_variant.sh): the chain modes that were measured slower
-#include "tppr_pair.hpp"                 // (tools/exp/variants/: two positions per critical section; spine / duo via tppr_chain.hpp)
-#else
 #include "tppr_chain.hpp"
-#endif
 
 #include "tppr_wide.hpp"                 // ZT_MAX_K < k <= ZT_MAX_K_WIDE: one wavefront per model, edges in order
 
@@ -60,18 +56,8 @@ namespace {
 #ifndef ZT_STREAM_BOUNDS
 #define ZT_STREAM_BOUNDS (WAVE * WAVES_PER_WG)      // (tools/exp/bounds_exp.sh: 768 = three waves per SIMD, 168 VGPRs)
 #endif
-// (variant builds, -DZT_CHAIN_VARIANTS, instantiate MODE 1 .. 3 as well; the product library has MODE 0 alone)
-// PAIRS: the instantiation whose chain waves may take two positions per critical section (tppr_pair.hpp).  A kernel of its
-// own: the paired hop is a real call that needs all 256 registers a wave may have at two waves per SIMD, and a k_stream of
-// 256 registers leaves the message kernels no room beside its workgroups on the T-PPR stream's CUs (round 5: with the call
-// merely PRESENT in the one kernel, k_last_pos waited 270 us per launch for a free register file and the driver-timed C5
-// step went from 0.38 to 0.54 ms).
-// MODE 2 (spine, tppr_chain.hpp): one wave of a chain workgroup runs every critical section, the others prepare and finish.
-template <int MODE>
 __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamArgs A)
 {
-    constexpr bool PAIRS = MODE == 1;
-    (void)PAIRS;
     __shared__ WaveLds lds[WAVES_PER_WG];
     __shared__ Mail mail;
     __shared__ int ch_edge[CH_MAX], ch_partner[CH_MAX], ch_wop[CH_MAX], ch_pch[CH_MAX];   // chain workgroups: HopRec
@@ -99,8 +85,6 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
     __builtin_amdgcn_s_setprio(3);                     // chain hops must not queue behind throughput kernels
     if (threadIdx.x < MAIL_R) { mail.slot[threadIdx.x].seq_set = 0; mail.slot[threadIdx.x].seq_ord = 0; mail.slot[threadIdx.x].seq_free = 0; }
     if (threadIdx.x == 0) mail.head = 0;
-    if (MODE >= 2 && threadIdx.x < PREP_R) { mail.prep[threadIdx.x].seq = 0; mail.prep[threadIdx.x].res = 0; mail.prep[threadIdx.x].a_seq = 0; }
-    if (MODE >= 2 && threadIdx.x == 0) { mail.a_gen = 0; mail.a_restart = 0; }
 #ifdef ZT_CRIT
     if (threadIdx.x == 0) mail.t_start = (long long)__builtin_readcyclecounter();
 #endif
@@ -163,13 +147,6 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
         // partner's update, the emission -- runs elsewhere (process_chain_partner), but a hop's preparation and its
         // off-chain half (replay, order, stores) still add up to ~5 hop periods of one wave's time.
         if ((int)(threadIdx.x / WAVE) >= A.chain_waves) return;
-#ifdef ZT_CHAIN_VARIANTS
-        const bool spine_on = MODE >= 2 && h.k <= REG_K_MAX && len > 0;
-        if (spine_on && threadIdx.x < WAVE) { chain_spine<MODE == 3>(h, lds, lane, &mail, len); return; }
-        if (spine_on && MODE == 3 && threadIdx.x < 2 * WAVE) { chain_weights(h, lds, lane, &mail, len); return; }
-#else
-        constexpr bool spine_on = false;
-#endif
         ChainHint hint;
         hint.norm_out = 0.0; hint.tpos = -1;
         // (Assigning hop t to wave t mod 8 statically -- so that the SIMD mate of the wave on the chain is the one four
@@ -181,49 +158,11 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
             if (t >= len) break;
             if (t == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(1);   // (the first hop has no mailbox to wait for)
 #define ZT_U(x) __builtin_amdgcn_readfirstlane(x)
-#ifdef ZT_CHAIN_VARIANTS
-            // ---- two positions in one critical section (tppr_pair.hpp): both edges have a partner other than the hub, not
-            // ---- the same one, and nobody has claimed position t + 1 yet ----
-            if (PAIRS && t >= 1 && t + 1 < len && h.k <= PAIR_K_MAX) {
-                const int pa = ZT_U(ch_partner[t]), pb = ZT_U(ch_partner[t + 1]);
-                if (pa >= 0 && pb >= 0 && pa != pb) {
-                    int old = 0;
-                    if (lane == 0) old = atomicCAS(&mail.head, t + 1, t + 2);
-                    old = ZT_U(old);
-                    if (old == t + 1) {
-                        chain_stat(h.ctl, lane, ST_PAIR_CLAIM);
-                        HopRec r1, r2;
-                        r1.partner = pa; r1.wo_p = ZT_U(ch_wop[t]); r1.pchain = ZT_U(ch_pch[t]);
-                        r2.partner = pb; r2.wo_p = ZT_U(ch_wop[t + 1]); r2.pchain = ZT_U(ch_pch[t + 1]);
-                        const int ea = ZT_U(ch_edge[t]), eb = ZT_U(ch_edge[t + 1]);
-                        const int e2 = t + 2 < len ? ZT_U(ch_edge[t + 2]) : -1, e0 = ZT_U(ch_edge[t - 1]);
-                        PairCtx X;
-                        X.rows = h.rows; X.hubver = h.hubver; X.cdone = h.cdone; X.ctl = h.ctl; X.tsv = A.tsv; X.eidx = A.eidx;
-                        X.N = h.N; X.m = A.m_lo + mo; X.alpha = h.alpha[X.m]; X.beta = h.beta[X.m]; X.epoch = A.epoch; X.k = h.k; X.rg = h.rg;
-                        const double nrm = chain_hop2(X, &L, lane, ea, eb, &mail, hub, e2, t, hint.norm_out, hint.tpos, c, r1, r2);
-                        if (nrm != 0.0) { hint.norm_out = nrm; hint.tpos = t + 1; continue; }
-                        // a precondition failed before anything was written: the two hops one after the other
-                        __builtin_amdgcn_s_setprio(1);
-                        if (!chain_hop(h, A, L, lane, ea, mo, &mail, hub, e0, eb, t, &hint, c, r1))
-                            process_edge(h, A, L, lane, ea, mo, &mail, hub, e0, eb, t, &hint, c);
-                        __builtin_amdgcn_s_setprio(1);
-                        if (!chain_hop(h, A, L, lane, eb, mo, &mail, hub, ea, e2, t + 1, &hint, c, r2))
-                            process_edge(h, A, L, lane, eb, mo, &mail, hub, ea, e2, t + 1, &hint, c);
-                        continue;
-                    }
-                }
-            }
-#endif
-            if (MODE != 0) chain_stat(h.ctl, lane, ST_SINGLE);      // (statistics of the alternative chain modes only: the default kernel's hot path
-                                                                    //  carries no atomic to a shared word that nobody reads -- round-5 advisor)
             const int pe = t > 0 ? ZT_U(ch_edge[t - 1]) : -1, ne = t + 1 < len ? ZT_U(ch_edge[t + 1]) : -1, ce = ZT_U(ch_edge[t]);
             HopRec rec;
             rec.partner = ZT_U(ch_partner[t]); rec.wo_p = ZT_U(ch_wop[t]); rec.pchain = ZT_U(ch_pch[t]);
 #undef ZT_U
-#ifdef ZT_CHAIN_VARIANTS
-            if (spine_on && (pe < 0 || rec.partner < 0)) spine_post_none(&mail, lane, t);      // (chain_hop does not take these)
-#endif
-            if (!chain_hop(h, A, L, lane, ce, mo, &mail, hub, pe, ne, t, &hint, c, rec, spine_on))
+            if (!chain_hop(h, A, L, lane, ce, mo, &mail, hub, pe, ne, t, &hint, c, rec))
                 process_edge(h, A, L, lane, ce, mo, &mail, hub, pe, ne, t, &hint, c);
         }
         return;                                           // chain workgroups take no general tasks (letting them join the
@@ -340,7 +279,7 @@ extern "C" int zt_tppr_create(zt_tppr **out, int64_t num_nodes, int32_t k, int32
     // every workgroup of a k_stream grid that runs hub chains must be resident: ask the runtime how many
     // fit on a CU (LDS, registers) rather than estimating it
     int per_cu = 0;
-    ZT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream<0>, WAVE * WAVES_PER_WG, 0));
+    ZT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream, WAVE * WAVES_PER_WG, 0));
     h->wg_per_cu = per_cu;
     h->epoch = 0;
     h->share = 1;
@@ -379,36 +318,14 @@ extern "C" int zt_tppr_set_device_share(zt_tppr *h, int32_t n_processes)
     return ZT_OK;
 }
 
-// hub-chain statistics since the last call (summed over both plan sets, then cleared): out[0] pairs of positions claimed by
-// one wave, [1] pairs completed in ONE critical section, [2] pairs left to the single hop in preparation (norm not
-// predictable, a key shared between the partners' rows, a slot collision ...), [3] ... inside the section (a key of the hub's
-// row in a partner's, a tie that reaches across the first cut ...), [4] positions taken singly.
+// hub-chain statistics: five counters of the chain modes that were removed.
+// The single-hop chain counts nothing, so this waits for the stream and writes zeros; the entry point stays for callers.
 extern "C" int zt_tppr_chain_stats(zt_tppr *h, int64_t *out5, void *stream)
 {
     if (!h || !out5) return ZT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     ZT_HIP(hipStreamSynchronize(s));
     for (int q = 0; q < 5; ++q) out5[q] = 0;
-#ifdef ZT_PAIR_STAT
-    {
-        long long g[16] = {0};
-        ZT_HIP(hipMemcpyFromSymbol(g, HIP_SYMBOL(g_pstat), sizeof(g)));
-        long long z[16] = {0};
-        ZT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_pstat), z, sizeof(z)));
-        if (g[4] > 0)
-            fprintf(stderr, "[pair-stat] %lld pairs: preparation %.0f clocks, waiting for the turn %.0f, critical section %.0f, off-chain halves %.0f\n",
-                    g[4], (double)g[0] / g[4], (double)g[2] / g[4], (double)g[1] / g[4], (double)g[3] / g[4]);
-        if (g[4] > 0)
-            fprintf(stderr, "[pair-stat]   section: row + checks %.0f, network %.0f, masks + tests + slots %.0f, ring slot %.0f\n",
-                    (double)g[5] / g[4], (double)g[6] / g[4], (double)g[7] / g[4], (double)g[8] / g[4]);
-    }
-#endif
-    for (int q = 0; q < 2; ++q) {
-        int c[5] = {0, 0, 0, 0, 0};
-        ZT_HIP(hipMemcpy(c, h->set[q].ctl + ST_PAIR_CLAIM, sizeof(c), hipMemcpyDeviceToHost));
-        ZT_HIP(hipMemset(h->set[q].ctl + ST_PAIR_CLAIM, 0, sizeof(c)));
-        for (int j = 0; j < 5; ++j) out5[j] += c[j];
-    }
     return ZT_OK;
 }
 
@@ -484,10 +401,6 @@ static int run_chunk(zt_tppr *h, int q, const int32_t *nodes, const double *ts, 
     sa.out_nodes = on; sa.out_eidx = oe; sa.out_dt = od; sa.out_w = ow; sa.epoch = h->epoch;
     sa.sub_B = sub_B;
     sa.member_done = (emit && sub_B > 0) ? member_done : nullptr;
-    // two chain positions per critical section (tppr_pair.hpp): bit-exact, 79 % of C5's chain positions pair up -- and slower
-    // (the section 4.0-4.4 k clocks against 2 x 2.3 k, its preparation 25 k per pair: DESIGN.md section 5): on request only
-    const int chain_choice = zt::kernel_choice(ZT_CHOICE_TPPR_CHAIN);
-    sa.pairs = chain_choice == ZT_CHAIN_PAIRED ? 1 : 0;
     sa.chain_waves = WAVES_PER_WG;             // (4 / 6 / 8 waves per chain: 1874 / 1557 / 1432 us per four-batch C5 launch, round 3)
 #ifdef ZT_CRIT
     static const int crit_multi_env = getenv("ZT_CRIT_MULTI") ? atoi(getenv("ZT_CRIT_MULTI")) : 0;    // (diagnostic build only)
@@ -504,13 +417,7 @@ static int run_chunk(zt_tppr *h, int q, const int32_t *nodes, const double *ts, 
     }
 #endif
     ZT_PROF_BEGIN(s, P_STREAM);
-#ifdef ZT_CHAIN_VARIANTS
-    if (sa.pairs) k_stream<1><<<grid, WAVE * WAVES_PER_WG, 0, s>>>(*h, sa);
-    else if (chain_choice == ZT_CHAIN_SPINE) k_stream<2><<<grid, WAVE * WAVES_PER_WG, 0, s>>>(*h, sa);
-    else if (chain_choice == ZT_CHAIN_DUO) k_stream<3><<<grid, WAVE * WAVES_PER_WG, 0, s>>>(*h, sa);
-    else
-#endif
-    k_stream<0><<<grid, WAVE * WAVES_PER_WG, 0, s>>>(*h, sa);      // (zt_set_kernel_choice refuses the other modes in a build without them)
+    k_stream<<<grid, WAVE * WAVES_PER_WG, 0, s>>>(*h, sa);
     ZT_PROF_END(s, P_STREAM);
     ZT_LAUNCH_CHECK();
     ZT_HIP(hipEventRecord(P.consumed, s));
@@ -520,16 +427,6 @@ static int run_chunk(zt_tppr *h, int q, const int32_t *nodes, const double *ts, 
     return ZT_OK;
 }
 
-
-// which values of ZT_CHOICE_TPPR_CHAIN this build of the library can run (runtime.hip: zt_set_kernel_choice)
-bool zt::tppr_chain_mode_compiled(int mode)
-{
-#ifdef ZT_CHAIN_VARIANTS
-    return mode >= 0 && mode <= ZT_CHAIN_DUO;
-#else
-    return mode == 0 || mode == ZT_CHAIN_SINGLE;
-#endif
-}
 
 // zt_tppr_stream with two extras for callers inside the library (pipeline.hip): plan_ordered = `stream` already
 // waits for the stream that made the plan (no second wait packet); *done_out = the event recorded behind the
