@@ -42,8 +42,9 @@ extern "C" {
 #define ZT_MAX_K_WIDE 255       /* streaming T-PPR accepts k up to here (the reference's --topk is unbounded, train.py:46): beyond
                                  * ZT_MAX_K a correct-first path takes over -- one wavefront per model applies the edges in order
                                  * (csrc/tppr_wide.hpp), same state layout, same results as the oracle bit for bit, not tuned.  zt_embed
-                                 * takes such rows through the generic kernel's 16-tile instantiation (k <= 80 in any case; up to 255
-                                 * over the projected table, where a query row's tile fits LDS); the training kernels k <= 80; the
+                                 * takes such rows through the generic kernel's 16-tile instantiation where a query row's tile fits LDS,
+                                 * and through the row-split kernel (the row's neighbours in chunks of 80, csrc/aggregate_split.hip)
+                                 * where none does; the training kernels any k up to here (the same row split beyond 80); the
                                  * pruning query any k up to here (its kept set strides over the lanes; the selection beyond
                                  * ZT_MAX_K is the generic replay of numba_sort.hpp) */
 
@@ -329,6 +330,9 @@ int zt_project_memory(const float *memory_dev, int64_t num_nodes, int32_t D,
  * drop_p > 0: the reference's training dropout of the hidden layer (nn.Dropout(0.1) between fc1's ReLU and fc2,
  *   modules/embedding_module.py:89,323-326) inside the kernels: the keep-mask is a hash of (drop_seed, element),
  *   regenerated by the backward from the same seed -- pass the forward's values.
+ * Shapes: D <= 128, k <= ZT_MAX_K_WIDE.  A query row of up to 80 neighbours is one tile of the fused kernels; a wider one
+ *   is split into chunks of neighbours (forward: one workgroup per query row walks its chunks, H the same from run to run;
+ *   backward: one tile per chunk), so F = 172 trains at any k up to ZT_MAX_K_WIDE as well.
  * workspaces: zt_embed_workspace_bytes(N, ...) / zt_agg_backward_workspace_bytes(D, F, T). */
 int zt_agg_train_forward(const float *memory_dev, const float *overlay_dev, const int32_t *row_map_dev,
                          const float *efeat_dev, int64_t num_nodes, int64_t num_edges, int32_t D,

@@ -26,6 +26,7 @@ SOURCES = {
     "tppr_prune.hip": ["-ffp-contract=off"],
     "aggregate.hip": [],
     "aggregate_wide.hip": [],
+    "aggregate_split.hip": [],
     "aggregate_bwd.hip": [],
     "memory_update.hip": [],
     "train_ops.hip": [],

@@ -1255,6 +1255,10 @@ struct EmbedPlan {
     size_t off_w1p, off_H, off_S, off_fc2t, off_fc1st, off_fc2st, off_w1t, off_wm, off_wl, off_wfrag, total;
     int hg;                                     // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
     bool big;                                   // k > 80: the MAX_MT_BIG instantiation of the generic kernel (mt = 0: that path's tile does not fit)
+    // the third choice, row split (aggregate_split.hip): gathered rows per chunk, 0 = unavailable.  Offered where no tile
+    // holds a query row with its memory columns (mt = 0) and for k > 80 (the training forward); zt_embed takes it only
+    // where neither the full nor the table path can run
+    int cr;
 };
 
 // tile shape for a contraction over Kp columns: as many whole query rows as fit MAX_MT tiles / the LDS budget
@@ -1286,14 +1290,13 @@ bool make_plan(int64_t N, int D, int F, int T, int M, int k, EmbedPlan &p)
     p.big = k > MAX_MT * 16;
     const int max_mt = p.big ? MAX_MT_BIG : MAX_MT;
     const bool full_ok = tile_shape(p.K1p, p.Dp, k, T, &p.lda, &p.mt, &p.rq, &p.lds, max_mt);
-    if (!full_ok) {
-        if (!p.big) return false;
-        p.mt = 0; p.rq = 1; p.lda = p.K1p + 4; p.lds = 0;       // (wide k: only the table path's narrower tile may fit)
-    }
+    // no tile for a query row with its memory columns: the table path's narrower tile (wide k), or the row split
+    if (!full_ok) { p.mt = 0; p.rq = 1; p.lda = p.K1p + 4; p.lds = 0; }
     p.K2p = round_up(F + T, 16);
     p.mt2 = 0;                                  // table path unavailable (e.g. F + T < D: the staging would not fit)
-    if (!tile_shape(p.K2p, p.Dp, k, T, &p.lda2, &p.mt2, &p.rq2, &p.lds2, max_mt)) p.mt2 = 0;
-    if (p.mt == 0 && p.mt2 == 0) return false;
+    if (!(full_ok || p.big) || !tile_shape(p.K2p, p.Dp, k, T, &p.lda2, &p.mt2, &p.rq2, &p.lds2, max_mt)) p.mt2 = 0;
+    p.cr = ((p.mt == 0 || p.big) && k <= ZT_MAX_K_WIDE) ? fc1_agg_split_rows(D, F, T) : 0;
+    if (p.mt == 0 && p.mt2 == 0 && p.cr == 0) return false;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
     // padded weights first: their offsets depend on (D, F, T) only, so a workspace prepared once serves every N
@@ -1441,8 +1444,11 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
     const bool tab = proj_table_dev != nullptr && p.mt2 > 0;
     const size_t lds = tab ? p.lds2 : p.lds;
     static size_t attr_lds[2] = {0, 0};
-    if (!tab && p.mt == 0) {
-        set_error("zt_embed: k=%d needs the projected table (a query row's [memory | ef | time] tile does not fit %d KB of LDS)", k, LDS_BUDGET / 1024);
+    // no tile holds a query row with its memory columns and the table path is not taken: the row-split kernel
+    const bool split = !tab && p.mt == 0;
+    if (split && p.cr == 0) {
+        set_error("zt_embed: k=%d needs the projected table (a query row's [memory | ef | time] tile does not fit %d KB of LDS, "
+                  "nor does a chunk of it)", k, LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     if (lds > 48 * 1024 && lds > attr_lds[tab ? 1 : 0]) {
@@ -1530,6 +1536,11 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
             k_fc1_agg<true><<<grid, AGG_THREADS, lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, p.Dp, F,
                                                            T, N, k, p.rq2, p.mt2, p.lda2, nbr_dev, eix_dev, dt_dev, w_dev, W1t,
                                                            p.K2p, wt->fc1_b, H, S, status_dev, D, nullptr, nullptr);
+    } else if (split) {
+        const int rc = fc1_agg_split_launch(memory_dev, nullptr, nullptr, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
+                                            M, k, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b, H, S, status_dev, 0.f,
+                                            0ull, s);
+        if (rc != ZT_OK) return rc;
     } else {
         dim3 grid((unsigned)((N + p.rq - 1) / p.rq), (unsigned)M);
         if (p.big)
@@ -1717,12 +1728,19 @@ extern "C" int zt_agg_train_forward(const float *memory_dev, const float *overla
         set_error("zt_agg_train_forward: unsupported shape");
         return ZT_ERR_UNSUPPORTED;
     }
-    if (p.big) {
-        set_error("zt_agg_train_forward: k=%d: the training kernels hold a query row of at most %d neighbours", k, MAX_MT * 16);
-        return ZT_ERR_UNSUPPORTED;
-    }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
+    if (p.big || p.mt == 0) {
+        // a query row wider than the 80-row tile: the row-split kernel (aggregate_split.hip), chunks of that tile
+        if (p.cr == 0) {
+            set_error("zt_agg_train_forward: D=%d F=%d T=%d k=%d: no 16-row chunk fits %d KB of LDS", D, F, T, k, LDS_BUDGET / 1024);
+            return ZT_ERR_UNSUPPORTED;
+        }
+        embed_prepare(wt, D, F, T, p, ws, s);
+        return fc1_agg_split_launch(memory_dev, overlay_dev, row_map_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
+                                    M, k, nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_w1p),
+                                    p.K1p, wt->fc1_b, H_dev, S_dev, status_dev, drop_p, drop_seed, s);
+    }
     embed_prepare(wt, D, F, T, p, ws, s);          // the weights change every optimizer step
     static size_t attr_lds = 0;
     if (p.lds > 48 * 1024 && p.lds > attr_lds) {

@@ -12,6 +12,8 @@
 //        dW1 += dpre^T x,   db1 += sum dpre,   d_overlay[row_map[nbr]] += dpre W_m      with dpre = w_k dH 1[pre > 0]
 //     on f32 MFMA: three products per tile (the recompute and the two gradients), the [D, K1] weight gradient
 //     held in registers across the tiles of a persistent workgroup and added to HBM once at the end.
+//   A query row wider than one tile (k > 80, or F = 172 past k = 64) is split: a tile is then one chunk of one row's
+//   neighbours, (m, n, chunk), and re-reads the row's k weights for the normaliser (forward: aggregate_split.hip).
 #include "common.hpp"
 
 using namespace zt;
@@ -40,8 +42,9 @@ struct BwdArgs {
     const float *b1;
     const float *dH;                   // [M][N][D]
     float *dW1, *db1, *d_overlay;      // [D][K1], [D], [U][D]  (accumulated with atomics)
-    long long n_tiles;                 // tiles of rq query rows per model
+    long long n_tiles;                 // tiles of rq query rows per model (row split: N * nch)
     int mt;                            // 16-row tiles per step (<= BW_MT)
+    int nch;                           // row split: chunks of mt * 16 gathered rows per query row (rq = 1); 0: whole rows
     int kt_lo, kt_hi;                  // this launch accumulates dW1 column tiles [kt_lo, kt_hi)
     int first;                         // 1: this launch also accumulates db1 and d_overlay
     unsigned drop_lo, drop_hi, drop_thr;   // training dropout of the hidden layer (common.hpp: drop_scale); thr = 0: none
@@ -74,10 +77,16 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
     const long long total = a.n_tiles * a.M;
     for (long long tile = blockIdx.x; tile < total; tile += gridDim.x) {
         const int m = (int)(tile / a.n_tiles);
-        const long long q0 = (tile % a.n_tiles) * a.rq;
+        long long q0 = (tile % a.n_tiles) * a.rq;
+        int j0 = 0;                                             // (row split: tile = (m, n, chunk), rows j0 .. j0 + rows of row q0)
+        if (a.nch > 0) {
+            const long long r = tile % a.n_tiles;
+            q0 = r / a.nch;
+            j0 = (int)(r - q0 * a.nch) * rows_p;
+        }
         const int nq = (int)((a.N - q0) < a.rq ? (a.N - q0) : a.rq);
-        const int rows = nq * k;
-        const size_t mb = ((size_t)m * a.N + q0) * k;
+        const int rows = a.nch > 0 ? (k - j0 < rows_p ? k - j0 : rows_p) : nq * k;
+        const size_t mb = ((size_t)m * a.N + q0) * k + j0;     // first gathered row of this tile in [M][N][k]
         __syncthreads();                                        // previous tile fully consumed
         for (int g = tid; g < rows_p; g += BW_THREADS) {
             int src = 0, ei = 0;
@@ -91,11 +100,22 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
             }
             g_src[g] = src; g_ei[g] = ei; g_dt[g] = d; wn[g] = wv;
         }
+        // row split: the normaliser needs all k weights of the row (checked the same way), staged in the P region
+        float *wrow = P;
+        if (a.nch > 0 && tid < k) {
+            const size_t e = mb - j0 + tid;
+            const int nb = a.nbr[e], ei = a.eix[e];
+            wrow[tid] = (nb < 0 || nb >= a.num_nodes || ei < 0 || ei >= a.num_edges) ? 0.f : a.w[e];
+        }
         __syncthreads();
         float my_sum = 0.f;
         if (tid < rows) {
-            const int q = tid / k;
-            for (int j = 0; j < k; ++j) my_sum += wn[q * k + j];
+            if (a.nch > 0) {
+                for (int j = 0; j < k; ++j) my_sum += wrow[j];
+            } else {
+                const int q = tid / k;
+                for (int j = 0; j < k; ++j) my_sum += wn[q * k + j];
+            }
         }
         __syncthreads();
         if (tid < rows) wn[tid] = (my_sum == 0.f) ? 0.f : wn[tid] / my_sum;
@@ -159,8 +179,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
                     if (g < rows && col < D && acc[x][b][j] + bias > 0.f) {
                         dp = wn[g] * a.dH[((size_t)m * a.N + q0 + g / k) * D + col];
                         if (a.drop_thr != 0u)
-                            dp *= drop_scale(a.drop_lo, a.drop_hi, a.drop_thr, a.drop_inv,
-                                             (unsigned long long)(((size_t)m * a.N + q0) * k + g) * D + col);
+                            dp *= drop_scale(a.drop_lo, a.drop_hi, a.drop_thr, a.drop_inv, (unsigned long long)(mb + g) * D + col);
                     }
                     P[(size_t)g * ldp + col] = dp;
                 }
@@ -281,11 +300,19 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     while (mt > 1 && lds_of(mt) > 150 * 1024) --mt;
     int rq = (mt * 16) / k;
     if (rq < 1) { mt = (k + 15) / 16; rq = 1; }
+    int nch = 0;
+    if (D <= 128 && (mt > BW_MT || lds_of(mt) > 150 * 1024) && k <= ZT_MAX_K_WIDE) {
+        // a query row does not fit one tile: row split, tiles of one chunk of BW_MT (or as many as fit) 16-row tiles
+        mt = BW_MT;
+        while (mt > 1 && lds_of(mt) > 150 * 1024) --mt;
+        rq = 1;
+        nch = (k + mt * 16 - 1) / (mt * 16);
+    }
     if (D > 128 || mt > BW_MT || lds_of(mt) > 150 * 1024) {
         set_error("zt_agg_train_backward: D=%d F=%d T=%d k=%d outside the supported shapes", D, F, T, k);
         return ZT_ERR_UNSUPPORTED;
     }
-    mt = (rq * k + 15) / 16;
+    if (nch == 0) mt = (rq * k + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
     float *W1p = reinterpret_cast<float *>(workspace_dev);
     k_pad<<<(Dp * K1p + 255) / 256, 256, 0, s>>>(fc1_w_dev, D, K1, W1p, Dp, K1p);
@@ -298,8 +325,9 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     a.D = D; a.F = F; a.T = T; a.k = k; a.M = M; a.rq = rq; a.lda = K1p + 4; a.ldp = Dp + 4; a.K1p = K1p; a.Dp = Dp;
     a.nbr = nbr_dev; a.eix = eix_dev; a.dt = dt_dev; a.w = w_dev; a.W1p = W1p; a.b1 = fc1_b_dev; a.dH = dH_dev;
     a.dW1 = dW1_dev; a.db1 = db1_dev; a.d_overlay = d_overlay_dev;
-    a.n_tiles = (N + rq - 1) / rq;
+    a.n_tiles = nch > 0 ? N * nch : (N + rq - 1) / rq;
     a.mt = mt;
+    a.nch = nch;
     const size_t lds = lds_of(mt);
     static size_t attr_lds = 0;
     if (lds > 48 * 1024 && lds > attr_lds) {

@@ -94,6 +94,15 @@ int fc1_agg_wide_launch(const float *P, const float *efeat, const float *time_w,
                         long long N, int M, int k, const int *nbr, const int *eix, const float *dt, const float *w,
                         const float *packed, const float *b1, float *G, float *S, int *status, int cus, hipStream_t s,
                         const member_gate *gate = nullptr);
+// the row-split aggregation (aggregate_split.hip): one workgroup per (model, query row), the k gathered rows in chunks --
+// zt_agg_train_forward beyond one tile and zt_embed where no tile holds a query row.  rows: 0 = unsupported widths
+int fc1_agg_split_rows(int D, int F, int T);
+size_t fc1_agg_split_lds(int D, int F, int T);
+int fc1_agg_split_launch(const float *memory, const float *overlay, const int *row_map, const float *efeat,
+                         const float *time_w, long long num_nodes, long long num_edges, int D, int F, int T, long long N,
+                         int M, int k, const int *nbr, const int *eix, const float *dt, const float *w, const float *W1p,
+                         int K1p, const float *b1, float *H, float *S, int *status, float drop_p,
+                         unsigned long long drop_seed, hipStream_t s);
 int pruned_topk_multi_fill(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
                            int32_t depth, int32_t n_models, const double *alpha_host, const double *beta_host, int32_t k,
                            int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev,
