@@ -1246,19 +1246,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_project_rows(const float *__res
     }
 }
 
+// The embed workspace for (N, D, F, T, M, k) and the tiles of k_fc1_agg (plan_kernels below picks the kernel)
 struct EmbedPlan {
-    int Dp, K1p, lda, mt, rq;
+    int Dp, K1p, lda, mt, rq;                   // the [memory | ef | time] tile (mt = 0: none holds a query row)
     size_t lds;
-    // table path (k_fc1_agg<true>): the tile holds only [ef | cos]
-    int K2p, lda2, mt2, rq2;
+    int K2p, lda2, mt2, rq2;                    // the projected table's [ef | time] tile (mt2 = 0: none)
     size_t lds2;
     size_t off_w1p, off_H, off_S, off_fc2t, off_fc1st, off_fc2st, off_w1t, off_wm, off_wl, off_wfrag, total;
     int hg;                                     // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
-    bool big;                                   // k > 80: the MAX_MT_BIG instantiation of the generic kernel (mt = 0: that path's tile does not fit)
-    // the third choice, row split (aggregate_split.hip): gathered rows per chunk, 0 = unavailable.  Offered where no tile
-    // holds a query row with its memory columns (mt = 0) and for k > 80 (the training forward); zt_embed takes it only
-    // where neither the full nor the table path can run
-    int cr;
 };
 
 // tile shape for a contraction over Kp columns: as many whole query rows as fit MAX_MT tiles / the LDS budget
@@ -1282,21 +1277,23 @@ bool tile_shape(int Kp, int Dp, int k, int T, int *lda_out, int *mt_out, int *rq
     return true;
 }
 
+// the row split (aggregate_split.hip) takes a query row in chunks where no tile holds one
+bool split_fits(int D, int F, int T, int k) { return k <= ZT_MAX_K_WIDE && fc1_agg_split_rows(D, F, T) > 0; }
+
 bool make_plan(int64_t N, int D, int F, int T, int M, int k, EmbedPlan &p)
 {
     const int K1 = D + F + T;
     p.Dp = round_up(D, 16);
     p.K1p = round_up(K1, 16);
-    p.big = k > MAX_MT * 16;
-    const int max_mt = p.big ? MAX_MT_BIG : MAX_MT;
+    const bool big = k > MAX_MT * 16;           // the MAX_MT_BIG instantiation
+    const int max_mt = big ? MAX_MT_BIG : MAX_MT;
     const bool full_ok = tile_shape(p.K1p, p.Dp, k, T, &p.lda, &p.mt, &p.rq, &p.lds, max_mt);
     // no tile for a query row with its memory columns: the table path's narrower tile (wide k), or the row split
     if (!full_ok) { p.mt = 0; p.rq = 1; p.lda = p.K1p + 4; p.lds = 0; }
     p.K2p = round_up(F + T, 16);
     p.mt2 = 0;                                  // table path unavailable (e.g. F + T < D: the staging would not fit)
-    if (!(full_ok || p.big) || !tile_shape(p.K2p, p.Dp, k, T, &p.lda2, &p.mt2, &p.rq2, &p.lds2, max_mt)) p.mt2 = 0;
-    p.cr = ((p.mt == 0 || p.big) && k <= ZT_MAX_K_WIDE) ? fc1_agg_split_rows(D, F, T) : 0;
-    if (p.mt == 0 && p.mt2 == 0 && p.cr == 0) return false;
+    if (!(full_ok || big) || !tile_shape(p.K2p, p.Dp, k, T, &p.lda2, &p.mt2, &p.rq2, &p.lds2, max_mt)) p.mt2 = 0;
+    if (p.mt == 0 && p.mt2 == 0 && !split_fits(D, F, T, k)) return false;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
     // padded weights first: their offsets depend on (D, F, T) only, so a workspace prepared once serves every N
@@ -1315,7 +1312,64 @@ bool make_plan(int64_t N, int D, int F, int T, int M, int k, EmbedPlan &p)
     return true;
 }
 
+// embed_kernel_plan on the workspace layout p it makes
+KernelPlan plan_kernels(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
+                        int out_choice, EmbedPlan &p)
+{
+    KernelPlan kp{AggKernel::unsupported, OutForm::tiled, Refusal::shape, 0, 0, 0, 0, 1};
+    static_assert(16 * NTW * AGG_WAVES == 128, "the output layers' N-tiles cover D <= 128");
+    if (D > 128 || !make_plan(N, D, F, T, M, k, p)) return kp;
+    const bool big = k > MAX_MT * 16;
+    const bool tab = have_table && !training && p.mt2 > 0;
+    // the reference's default widths take the specialised kernels (zt_set_kernel_choice(ZT_CHOICE_AGGREGATE, ZT_AGG_GENERIC): the generic one)
+    const bool special = tab && agg_choice != ZT_AGG_GENERIC;
+    if (training ? (big || p.mt == 0) : (!tab && p.mt == 0)) {
+        // a query row wider than any tile (training: than the 80-row one): the row split
+        if (!split_fits(D, F, T, k)) { kp.refusal = Refusal::no_split; return kp; }
+        kp.agg = AggKernel::split;
+    } else if (special && p.hg > 1) {
+        kp.agg = AggKernel::wide;               // F = 172, D = T = 100, k in {20, 40}: weights resident in LDS
+    } else if (special && D == 100 && T == 100 && F <= 4 && (k == 20 || k == 40) && p.K2p == 112) {
+        kp.agg = AggKernel::reg;                // register-resident weights
+    } else if (special && D == 100 && T == 100 && p.mt2 == 5 && (k == 10 || k == 20 || k == 40)) {
+        kp.agg = AggKernel::d100;
+    } else if (tab) {
+        kp.agg = big ? AggKernel::tiled_table_big : AggKernel::tiled_table;
+    } else {
+        kp.agg = big ? AggKernel::tiled_full_big : AggKernel::tiled_full;
+    }
+    if (kp.agg == AggKernel::d100 || kp.agg == AggKernel::tiled_table || kp.agg == AggKernel::tiled_table_big) {
+        kp.lds = p.lds2; kp.rq = p.rq2; kp.mt = p.mt2; kp.lda = p.lda2;
+    } else if (kp.agg == AggKernel::tiled_full || kp.agg == AggKernel::tiled_full_big) {
+        kp.lds = p.lds; kp.rq = p.rq; kp.mt = p.mt; kp.lda = p.lda;
+    }
+    kp.hg = kp.agg == AggKernel::wide ? p.hg : 1;
+    if (kp.hg != 1 && kp.hg != 5 && kp.hg != 10) { kp.agg = AggKernel::unsupported; kp.refusal = Refusal::groups; return kp; }
+    kp.refusal = Refusal::none;
+    // small batches: the latency-organised kernel (one wave per tile, path and N-tile; 1 - 2 memory round trips); large ones:
+    // the persistent one (weights resident in LDS, a wave per 16 rows x all N-tiles); other widths: the tiled one (weights
+    // streamed from L2 per 32-row workgroup).  zt_set_kernel_choice(ZT_CHOICE_EMBED_OUT, ..) pins one; the three give the
+    // same results (tests/test_embed_gpu.py).
+    // (alone on the chip, tools/exp/p23_kernels.py: 12 288 rows persist 26 us / tiled 32 / latency 53 -- 29 / 38 / 66 on 192 CUs;
+    //  3 000 rows 17 / 18 / 23; 1 800 rows with partial-sum groups 19 / 17.5 / 22; 600 rows 16.5 / 17 / 12)
+    //  In the pipeline the persistent workgroups (130 KB of LDS, a whole register file per wave) do not fit beside another
+    //  stream's kernels: C4 (3 000 rows, no CU masks, k_pruned_topk running beside) 36 us against the tiled kernel's 20; C5
+    //  (12 288 rows, the main stream's CUs to itself) 29 against 38.  So: from 8 192 rows on.
+    if (D % 4 == 0 && (p.Dp == 112 || p.Dp == 128) && (out_choice == ZT_OUT_LATENCY || (out_choice == 0 && N <= 1024)))
+        kp.out = OutForm::latency;
+    else if (D % 4 == 0 && p.Dp == EO3_DP && (out_choice == ZT_OUT_PERSIST || (out_choice == 0 && N >= 8192)))
+        kp.out = OutForm::persist;
+    return kp;
+}
+
 }  // namespace
+
+KernelPlan zt::embed_kernel_plan(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
+                                 int out_choice)
+{
+    EmbedPlan p;
+    return plan_kernels(N, D, F, T, M, k, have_table, training, agg_choice, out_choice, p);
+}
 
 #ifdef ZT_AGG_STAMP
 extern "C" int zt_debug_agg(unsigned long long *host, int reset)
@@ -1421,215 +1475,114 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
         return ZT_ERR_ARG;
     }
     EmbedPlan p;
-    if (D > 16 * NTW * AGG_WAVES || D > 128 || !make_plan(N, D, F, T, M, k, p)) {
+    const KernelPlan kp = plan_kernels(N, D, F, T, M, k, proj_table_dev != nullptr, false, kernel_choice(ZT_CHOICE_AGGREGATE),
+                                       kernel_choice(ZT_CHOICE_EMBED_OUT), p);
+    if (kp.refusal == Refusal::shape) {
         set_error("zt_embed: D=%d F=%d T=%d k=%d outside the supported shapes (D<=128, one query row of k "
                   "neighbours must fit the %d KB LDS tile)", D, F, T, k, LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
-    float *W1p = reinterpret_cast<float *>(ws + p.off_w1p);
-    float *W1t = reinterpret_cast<float *>(ws + p.off_w1t);
-    const float *Wfrag = reinterpret_cast<const float *>(ws + p.off_wfrag);
     float *H = reinterpret_cast<float *>(ws + p.off_H);
     float *S = reinterpret_cast<float *>(ws + p.off_S);
-    float *fc2t = reinterpret_cast<float *>(ws + p.off_fc2t);
-    float *fc1st = reinterpret_cast<float *>(ws + p.off_fc1st);
-    float *fc2st = reinterpret_cast<float *>(ws + p.off_fc2st);
     if (!weights_ready) {
         ZT_PROF_BEGIN(s, P_EMBED_PREP);
         embed_prepare(wt, D, F, T, p, ws, s);
         ZT_PROF_END(s, P_EMBED_PREP);
     }
-    const bool tab = proj_table_dev != nullptr && p.mt2 > 0;
-    const size_t lds = tab ? p.lds2 : p.lds;
-    static size_t attr_lds[2] = {0, 0};
-    // no tile holds a query row with its memory columns and the table path is not taken: the row-split kernel
-    const bool split = !tab && p.mt == 0;
-    if (split && p.cr == 0) {
+    if (kp.refusal == Refusal::no_split) {
         set_error("zt_embed: k=%d needs the projected table (a query row's [memory | ef | time] tile does not fit %d KB of LDS, "
                   "nor does a chunk of it)", k, LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
-    if (lds > 48 * 1024 && lds > attr_lds[tab ? 1 : 0]) {
-        const void *fn = tab ? reinterpret_cast<const void *>(k_fc1_agg<true>) : reinterpret_cast<const void *>(k_fc1_agg<false>);
-        ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds[tab ? 1 : 0] = lds;
-    }
-    static size_t attr_big[2] = {0, 0};
-    if (p.big && lds > 48 * 1024 && lds > attr_big[tab ? 1 : 0]) {
-        const void *fn = tab ? reinterpret_cast<const void *>(k_fc1_agg<true, MAX_MT_BIG>) : reinterpret_cast<const void *>(k_fc1_agg<false, MAX_MT_BIG>);
-        ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_big[tab ? 1 : 0] = lds;
-    }
-    // the reference's default widths take the specialised kernels (zt_set_kernel_choice(ZT_CHOICE_AGGREGATE, ZT_AGG_GENERIC): the generic one)
-    const bool generic = zt::kernel_choice(ZT_CHOICE_AGGREGATE) == ZT_AGG_GENERIC;
-    const bool d100 = tab && D == 100 && T == 100 && p.mt2 == 5 && (k == 10 || k == 20 || k == 40) && !generic;
-    static size_t attr_fast[3] = {0, 0, 0};
-    if (d100 && lds > 48 * 1024) {
-        const int ki = k == 10 ? 0 : (k == 20 ? 1 : 2);
-        if (lds > attr_fast[ki]) {
-            const void *fn = k == 10 ? reinterpret_cast<const void *>(k_fc1_agg_d100<10>)
-                                     : (k == 20 ? reinterpret_cast<const void *>(k_fc1_agg_d100<20>)
-                                                : reinterpret_cast<const void *>(k_fc1_agg_d100<40>));
-            ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_fast[ki] = lds;
-        }
-    }
-    // register-resident kernel: D = T = 100, F + T <= 104, k in {20, 40}
-    const bool regk = tab && D == 100 && T == 100 && F <= 4 && (k == 20 || k == 40) && p.K2p == 112 && !generic;
-    // wide edge features (F = 172), D = T = 100, k in {20, 40}: weights resident in LDS (aggregate_wide.hip)
-    const bool widek = tab && p.hg > 1 && !generic;
+    if (kp.refusal == Refusal::groups) { set_error("zt_embed: %d partial-sum groups per row", kp.hg); return ZT_ERR_UNSUPPORTED; }
     // (a wait for this batch's T-PPR rows: inside the two persistent kernels, a one-wave kernel in front of the others)
-    if (gate != nullptr && gate->word != nullptr && !widek && !regk) {
+    const bool waits_inside = kp.agg == AggKernel::wide || kp.agg == AggKernel::reg;
+    if (gate != nullptr && gate->word != nullptr && !waits_inside) {
         const int rc = zt::member_gate_launch(*gate, status_dev, s);
         if (rc != ZT_OK) return rc;
     }
-    ZT_PROF_BEGIN(s, P_FC1_AGG);
-    if (widek) {
-        const int rc = fc1_agg_wide_launch(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, N, M, k, nbr_dev, eix_dev,
-                                           dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_wl), wt->fc1_b, H, S,
-                                           status_dev, stream_cu_count(s), s, gate);
-        if (rc != ZT_OK) return rc;
-    } else if (regk) {
+    const dim3 tile_grid((unsigned)(kp.rq > 0 ? (N + kp.rq - 1) / kp.rq : 0), (unsigned)M);
+    // k_fc1_agg over the plan's tile: `rows` is memory (row stride D) or the projected table (stride Dp)
+    auto tiled = [&](decltype(&k_fc1_agg<false>) fn, const float *rows, int ld, size_t w_off, int Kp) {
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), kp.lds));
+        fn<<<tile_grid, AGG_THREADS, kp.lds, s>>>(rows, efeat_dev, wt->time_w, num_nodes, num_edges, ld, F, T, N, k, kp.rq, kp.mt,
+                                                  kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + w_off),
+                                                  Kp, wt->fc1_b, H, S, status_dev, D, nullptr, nullptr, 0u, 0u, 0u, 1.f);
+        return ZT_OK;
+    };
+    // k_fc1_agg_reg: persistent, one workgroup (4 waves) per CU
+    auto reg = [&](decltype(&k_fc1_agg_reg<20>) fn) {
         const long long rq = 80 / k, tiles = ((N + rq - 1) / rq) * M;
         long long wgs = (tiles + AGG_WAVES - 1) / AGG_WAVES;
         const int cus = stream_cu_count(s);
-        if (wgs > cus) wgs = cus;                                      // persistent: one workgroup (4 waves) per CU
-        const size_t reg_lds = 0;
-        const int *gw = gate ? gate->word : nullptr;
-        const int gt = gate ? gate->target : 0;
-        int *gl = gate ? gate->latch : nullptr;
+        if (wgs > cus) wgs = cus;
+        fn<<<(unsigned)wgs, AGG_THREADS, 0, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, F, N, M, nbr_dev, eix_dev,
+                                                 dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_wfrag), wt->fc1_b, H, S,
+                                                 status_dev, gate ? gate->word : nullptr, gate ? gate->target : 0,
+                                                 gate ? gate->latch : nullptr);
+        return ZT_OK;
+    };
+    ZT_PROF_BEGIN(s, P_FC1_AGG);
+    int rc = ZT_OK;
+    switch (kp.agg) {
+    case AggKernel::wide:
+        rc = fc1_agg_wide_launch(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, N, M, k, nbr_dev, eix_dev, dt_dev,
+                                 w_dev, reinterpret_cast<const float *>(ws + p.off_wl), wt->fc1_b, H, S, status_dev,
+                                 stream_cu_count(s), s, gate);
+        break;
+    case AggKernel::reg:
 #ifdef ZT_DIAG
-        static const int dbg = getenv("ZT_AGG_DBG") ? atoi(getenv("ZT_AGG_DBG")) : 0;       // diagnostic (wrong results)
-#define ZT_REG_DBG(DB) k_fc1_agg_reg<20, DB><<<(unsigned)wgs, AGG_THREADS, reg_lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, \
-            num_edges, F, N, M, nbr_dev, eix_dev, dt_dev, w_dev, Wfrag, wt->fc1_b, H, S, status_dev, gw, gt, gl)
-        if (k == 20 && dbg == 1) ZT_REG_DBG(1);
-        else if (k == 20 && dbg == 2) ZT_REG_DBG(2);
-        else if (k == 20 && dbg == 6) ZT_REG_DBG(6);
-        else if (k == 20 && dbg == 7) ZT_REG_DBG(7);
-        else if (k == 20 && dbg == 8) ZT_REG_DBG(8);       // (all parts, with the per-wave clocks)
-#undef ZT_REG_DBG
-        else
+        {
+            // diagnostic variants of k = 20 (wrong results; 8: all parts, with the per-wave clocks)
+            static const int dbg = getenv("ZT_AGG_DBG") ? atoi(getenv("ZT_AGG_DBG")) : 0;
+            if (k == 20 && dispatch<1, 2, 6, 7, 8>(dbg, [&](auto DB) { return reg(k_fc1_agg_reg<20, DB>); }) == ZT_OK) break;
+        }
 #endif
-        if (k == 20)
-            k_fc1_agg_reg<20><<<(unsigned)wgs, AGG_THREADS, reg_lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, F, N,
-                                                                 M, nbr_dev, eix_dev, dt_dev, w_dev, Wfrag, wt->fc1_b, H, S, status_dev,
-                                                                 gw, gt, gl);
-        else
-            k_fc1_agg_reg<40><<<(unsigned)wgs, AGG_THREADS, reg_lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, F, N,
-                                                                 M, nbr_dev, eix_dev, dt_dev, w_dev, Wfrag, wt->fc1_b, H, S, status_dev,
-                                                                 gw, gt, gl);
-    } else if (d100) {
-        dim3 grid((unsigned)((N + p.rq2 - 1) / p.rq2), (unsigned)M);
-#define ZT_D100(KK) k_fc1_agg_d100<KK><<<grid, AGG_THREADS, lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes,     \
-            num_edges, F, N, p.lda2, nbr_dev, eix_dev, dt_dev, w_dev, W1t, p.K2p, wt->fc1_b, H, S, status_dev)
-        if (k == 10) ZT_D100(10); else if (k == 20) ZT_D100(20); else ZT_D100(40);
-#undef ZT_D100
-    } else if (tab) {
-        dim3 grid((unsigned)((N + p.rq2 - 1) / p.rq2), (unsigned)M);
-        if (p.big)
-            k_fc1_agg<true, MAX_MT_BIG><<<grid, AGG_THREADS, lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, p.Dp, F,
-                                                                   T, N, k, p.rq2, p.mt2, p.lda2, nbr_dev, eix_dev, dt_dev, w_dev, W1t,
-                                                                   p.K2p, wt->fc1_b, H, S, status_dev, D, nullptr, nullptr);
-        else
-            k_fc1_agg<true><<<grid, AGG_THREADS, lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, p.Dp, F,
-                                                           T, N, k, p.rq2, p.mt2, p.lda2, nbr_dev, eix_dev, dt_dev, w_dev, W1t,
-                                                           p.K2p, wt->fc1_b, H, S, status_dev, D, nullptr, nullptr);
-    } else if (split) {
-        const int rc = fc1_agg_split_launch(memory_dev, nullptr, nullptr, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
-                                            M, k, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b, H, S, status_dev, 0.f,
-                                            0ull, s);
-        if (rc != ZT_OK) return rc;
-    } else {
-        dim3 grid((unsigned)((N + p.rq - 1) / p.rq), (unsigned)M);
-        if (p.big)
-            k_fc1_agg<false, MAX_MT_BIG><<<grid, AGG_THREADS, lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
-                                                                    k, p.rq, p.mt, p.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p,
-                                                                    wt->fc1_b, H, S, status_dev, D, nullptr, nullptr);
-        else
-            k_fc1_agg<false><<<grid, AGG_THREADS, lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
-                                                            k, p.rq, p.mt, p.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p,
-                                                            wt->fc1_b, H, S, status_dev, D, nullptr, nullptr);
+        rc = dispatch<20, 40>(k, [&](auto KK) { return reg(k_fc1_agg_reg<KK>); });
+        break;
+    case AggKernel::d100:
+        rc = dispatch<10, 20, 40>(k, [&](auto KK) {
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_d100<KK>), kp.lds));
+            k_fc1_agg_d100<KK><<<tile_grid, AGG_THREADS, kp.lds, s>>>(proj_table_dev, efeat_dev, wt->time_w, num_nodes, num_edges, F, N,
+                                                                     kp.lda, nbr_dev, eix_dev, dt_dev, w_dev,
+                                                                     reinterpret_cast<const float *>(ws + p.off_w1t), p.K2p, wt->fc1_b,
+                                                                     H, S, status_dev);
+            return ZT_OK;
+        });
+        break;
+    case AggKernel::tiled_table: rc = tiled(k_fc1_agg<true>, proj_table_dev, p.Dp, p.off_w1t, p.K2p); break;
+    case AggKernel::tiled_table_big: rc = tiled(k_fc1_agg<true, MAX_MT_BIG>, proj_table_dev, p.Dp, p.off_w1t, p.K2p); break;
+    case AggKernel::tiled_full: rc = tiled(k_fc1_agg<false>, memory_dev, D, p.off_w1p, p.K1p); break;
+    case AggKernel::tiled_full_big: rc = tiled(k_fc1_agg<false, MAX_MT_BIG>, memory_dev, D, p.off_w1p, p.K1p); break;
+    case AggKernel::split:
+        rc = fc1_agg_split_launch(memory_dev, nullptr, nullptr, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, M, k,
+                                  nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_w1p), p.K1p,
+                                  wt->fc1_b, H, S, status_dev, 0.f, 0ull, s);
+        break;
+    case AggKernel::unsupported: break;               // (refused above)
     }
+    if (rc != ZT_OK) return rc;
     ZT_PROF_END(s, P_FC1_AGG);
     if (mid_wait != nullptr) ZT_HIP(hipStreamWaitEvent(s, mid_wait, 0));
-    const int hg = widek ? p.hg : 1;
-    // small batches: the latency-organised kernel (one wave per tile, path and N-tile; 1 - 2 memory round trips); large ones:
-    // the persistent one (weights resident in LDS, a wave per 16 rows x all N-tiles); other widths: the tiled one (weights
-    // streamed from L2 per 32-row workgroup).  zt_set_kernel_choice(ZT_CHOICE_EMBED_OUT, ..) pins one; the three give the
-    // same results (tests/test_embed_gpu.py).
-    const int oc = zt::kernel_choice(ZT_CHOICE_EMBED_OUT);
-    const bool hg_ok = hg == 1 || hg == 5 || hg == 10;
-    const bool can2 = D % 4 == 0 && (p.Dp == 112 || p.Dp == 128) && hg_ok;
-    const bool can3 = D % 4 == 0 && p.Dp == EO3_DP && hg_ok;
-    const bool use2 = can2 && (oc == ZT_OUT_LATENCY || (oc == 0 && N <= 1024));
-    // (alone on the chip, tools/exp/p23_kernels.py: 12 288 rows persist 26 us / tiled 32 / latency 53 -- 29 / 38 / 66 on 192 CUs;
-    //  3 000 rows 17 / 18 / 23; 1 800 rows with partial-sum groups 19 / 17.5 / 22; 600 rows 16.5 / 17 / 12)
-    //  In the pipeline the persistent workgroups (130 KB of LDS, a whole register file per wave) do not fit beside another
-    //  stream's kernels: C4 (3 000 rows, no CU masks, k_pruned_topk running beside) 36 us against the tiled kernel's 20; C5
-    //  (12 288 rows, the main stream's CUs to itself) 29 against 38.  So: from 8 192 rows on.
-    const bool use3 = can3 && !use2 && (oc == ZT_OUT_PERSIST || (oc == 0 && N >= 8192));
-    const bool held_back = defer != nullptr && !use3;                    // (launched by the caller, beside the GRU update)
-    if (!held_back) ZT_PROF_BEGIN(s, P_EMBED_OUT);
-    if (use2) {
-        // one wave per (16 rows, path, N-tile), striding over the row tiles with its weights in registers
-        const long long tiles = (N + 15) / 16;
-        zt::embed_out_deferred od;
-        od.valid = true; od.form = 2; od.gx = (int)(tiles < 256 ? tiles : 256);
-        od.memory = memory_dev; od.num_nodes = num_nodes; od.nodes = nodes_dev; od.N = N; od.D = D; od.M = M; od.hg = hg;
-        od.H = H; od.S = S; od.fc2_p = fc2t; od.fc2_b = wt->fc2_b; od.fc1s_p = fc1st; od.fc1s_b = wt->fc1s_b; od.fc2s_p = fc2st;
-        od.fc2s_b = wt->fc2s_b; od.out = out_dev; od.status = status_dev; od.latch = nullptr;
-        if (defer != nullptr) {
-            int *keep = defer->latch;
-            *defer = od;
-            defer->latch = keep;
-            ZT_LAUNCH_CHECK();
-            return ZT_OK;
-        }
-        const int rc = zt::embed_out_launch(od, s);
-        if (rc != ZT_OK) return rc;
-    } else if (use3) {
-        // one workgroup per CU of the stream; the source path's two layers are as many MFMAs per row as M models' fc2
-        const long long tiles = (N + 15) / 16;
-        long long wgs = zt::stream_cu_count(s);
-        const long long want = (tiles * (M + 2) + AGG_WAVES - 1) / AGG_WAVES;       // (units of 196 MFMAs) / waves
-        if (wgs > want) wgs = want;
-        if (wgs < 2) wgs = 2;
-        int n_src = (int)((2 * wgs + (M + 2) / 2) / (M + 2));
-        if (n_src < 1) n_src = 1;
-        if (n_src > wgs - 1) n_src = (int)wgs - 1;
-        const size_t lds3 = (size_t)(2 * EO3_FRAG + AGG_WAVES * 16 * EO3_LDY) * 4;
-        static bool attr3[3] = {false, false, false};
-        const int hi = hg == 1 ? 0 : (hg == 5 ? 1 : 2);
-        if (!attr3[hi]) {
-            const void *fn = hg == 1 ? reinterpret_cast<const void *>(k_embed_out3<1>)
-                                     : (hg == 5 ? reinterpret_cast<const void *>(k_embed_out3<5>) : reinterpret_cast<const void *>(k_embed_out3<10>));
-            ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-            attr3[hi] = true;
-        }
-#define ZT_EO3(HGV) k_embed_out3<HGV><<<(unsigned)wgs, AGG_THREADS, lds3, s>>>(memory_dev, num_nodes, nodes_dev, N, D, M, H, S, fc2t, \
-            wt->fc2_b, fc1st, wt->fc1s_b, fc2st, wt->fc2s_b, out_dev, status_dev, n_src)
-        if (hg == 1) ZT_EO3(1); else if (hg == 5) ZT_EO3(5); else ZT_EO3(10);
-#undef ZT_EO3
-    } else {
-        if (hg != 1 && hg != 5 && hg != 10) { set_error("zt_embed: %d partial-sum groups per row", hg); return ZT_ERR_UNSUPPORTED; }
-        zt::embed_out_deferred od;
-        od.valid = true; od.form = 1; od.gx = 0;
-        od.memory = memory_dev; od.num_nodes = num_nodes; od.nodes = nodes_dev; od.N = N; od.D = D; od.M = M; od.hg = hg;
-        od.H = H; od.S = S; od.fc2_p = fc2t; od.fc2_b = wt->fc2_b; od.fc1s_p = fc1st; od.fc1s_b = wt->fc1s_b; od.fc2s_p = fc2st;
-        od.fc2s_b = wt->fc2s_b; od.out = out_dev; od.status = status_dev; od.latch = nullptr;
-        if (defer != nullptr) {
-            // the caller launches them beside the GRU update (gru_update_ex) -- or by embed_out_launch
-            int *keep = defer->latch;
-            *defer = od;
-            defer->latch = keep;
-            ZT_LAUNCH_CHECK();
-            return ZT_OK;
-        }
-        const int rc = zt::embed_out_launch(od, s);
-        if (rc != ZT_OK) return rc;
+    const EmbedOutArgs E{memory_dev, num_nodes, nodes_dev, N, D, M, H, S,
+                         reinterpret_cast<const float *>(ws + p.off_fc2t), wt->fc2_b,
+                         reinterpret_cast<const float *>(ws + p.off_fc1st), wt->fc1s_b,
+                         reinterpret_cast<const float *>(ws + p.off_fc2st), wt->fc2s_b, out_dev, status_dev};
+    const long long tiles = (N + 15) / 16;
+    const zt::embed_out_deferred od{true, E, kp.hg, kp.out, kp.out == OutForm::latency ? (int)(tiles < 256 ? tiles : 256) : 0, nullptr};
+    if (defer != nullptr && kp.out != OutForm::persist) {
+        // held back: the caller launches them beside the GRU update (gru_update_ex) -- or by embed_out_launch
+        int *latch = defer->latch;
+        *defer = od;
+        defer->latch = latch;
+        ZT_LAUNCH_CHECK();
+        return ZT_OK;
     }
+    ZT_PROF_BEGIN(s, P_EMBED_OUT);
+    rc = zt::embed_out_launch(od, s);
+    if (rc != ZT_OK) return rc;
     ZT_PROF_END(s, P_EMBED_OUT);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
@@ -1648,26 +1601,40 @@ extern "C" int zt_embed(const float *memory_dev, const float *efeat_dev, int64_t
 int zt::embed_out_launch(const zt::embed_out_deferred &d, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const int Dp = round_up(d.D, 16);
-    const size_t lds2 = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
-    EmbedOutArgs E;
-    E.memory = d.memory; E.num_nodes = d.num_nodes; E.nodes = d.nodes; E.N = d.N; E.D = d.D; E.M = d.M; E.H = d.H; E.S = d.S;
-    E.fc2_p = d.fc2_p; E.fc2_b = d.fc2_b; E.fc1s_p = d.fc1s_p; E.fc1s_b = d.fc1s_b; E.fc2s_p = d.fc2s_p; E.fc2s_b = d.fc2s_b;
-    E.out = d.out; E.status = d.status;
-    if (d.form == 2) {
-        const dim3 grid2((unsigned)d.gx, (unsigned)(d.M + 1), (unsigned)(Dp / 16));
-#define ZT_EO2(NTV, HGV) k_embed_out2<NTV, HGV><<<grid2, 64, 0, s>>>(E)
-        if (Dp == 112) { if (d.hg == 1) ZT_EO2(7, 1); else if (d.hg == 5) ZT_EO2(7, 5); else ZT_EO2(7, 10); }
-        else           { if (d.hg == 1) ZT_EO2(8, 1); else if (d.hg == 5) ZT_EO2(8, 5); else ZT_EO2(8, 10); }
-#undef ZT_EO2
-        ZT_LAUNCH_CHECK();
-        return ZT_OK;
+    const EmbedOutArgs &E = d.args;
+    const int Dp = round_up(E.D, 16);
+    int rc;
+    if (d.form == OutForm::latency) {
+        // one wave per (16 rows, path, N-tile), striding over the row tiles with its weights in registers
+        const dim3 grid2((unsigned)d.gx, (unsigned)(E.M + 1), (unsigned)(Dp / 16));
+        rc = dispatch<7, 8>(Dp / 16, [&](auto NTV) {
+            return dispatch<1, 5, 10>(d.hg, [&](auto HGV) { k_embed_out2<NTV, HGV><<<grid2, 64, 0, s>>>(E); return ZT_OK; });
+        });
+    } else if (d.form == OutForm::persist) {
+        // one workgroup per CU of the stream; the source path's two layers are as many MFMAs per row as M models' fc2
+        const long long tiles = (E.N + 15) / 16;
+        long long wgs = zt::stream_cu_count(s);
+        const long long want = (tiles * (E.M + 2) + AGG_WAVES - 1) / AGG_WAVES;       // (units of 196 MFMAs) / waves
+        if (wgs > want) wgs = want;
+        if (wgs < 2) wgs = 2;
+        int n_src = (int)((2 * wgs + (E.M + 2) / 2) / (E.M + 2));
+        if (n_src < 1) n_src = 1;
+        if (n_src > wgs - 1) n_src = (int)wgs - 1;
+        const size_t lds3 = (size_t)(2 * EO3_FRAG + AGG_WAVES * 16 * EO3_LDY) * 4;
+        rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_out3<HGV>), lds3));
+            k_embed_out3<HGV><<<(unsigned)wgs, AGG_THREADS, lds3, s>>>(E.memory, E.num_nodes, E.nodes, E.N, E.D, E.M, E.H, E.S, E.fc2_p,
+                                                                      E.fc2_b, E.fc1s_p, E.fc1s_b, E.fc2s_p, E.fc2s_b, E.out, E.status,
+                                                                      n_src);
+            return ZT_OK;
+        });
+    } else {
+        const size_t lds2 = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
+        const dim3 grid((unsigned)((E.N + OUT_ROWS - 1) / OUT_ROWS), (unsigned)(E.M + 1));
+        rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) { k_embed_out<HGV><<<grid, AGG_THREADS, lds2, s>>>(E); return ZT_OK; });
     }
-    const dim3 grid((unsigned)((d.N + OUT_ROWS - 1) / OUT_ROWS), (unsigned)(d.M + 1));
-    if (d.hg == 1) k_embed_out<1><<<grid, AGG_THREADS, lds2, s>>>(E);
-    else if (d.hg == 5) k_embed_out<5><<<grid, AGG_THREADS, lds2, s>>>(E);
-    else if (d.hg == 10) k_embed_out<10><<<grid, AGG_THREADS, lds2, s>>>(E);
-    else { set_error("zt_embed: %d partial-sum groups per row", d.hg); return ZT_ERR_UNSUPPORTED; }
+    if (rc == ZT_ERR_UNSUPPORTED) set_error("zt_embed: %d partial-sum groups per row", d.hg);      // (no instantiation for it)
+    if (rc != ZT_OK) return rc;
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }
@@ -1724,37 +1691,29 @@ extern "C" int zt_agg_train_forward(const float *memory_dev, const float *overla
     }
     if (N == 0) return ZT_OK;
     EmbedPlan p;
-    if (D > 128 || !make_plan(N, D, F, T, M, k, p)) {
+    const KernelPlan kp = plan_kernels(N, D, F, T, M, k, false, true, 0, 0, p);
+    if (kp.refusal == Refusal::shape) {
         set_error("zt_agg_train_forward: unsupported shape");
+        return ZT_ERR_UNSUPPORTED;
+    }
+    if (kp.refusal == Refusal::no_split) {
+        set_error("zt_agg_train_forward: D=%d F=%d T=%d k=%d: no 16-row chunk fits %d KB of LDS", D, F, T, k, LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
-    if (p.big || p.mt == 0) {
-        // a query row wider than the 80-row tile: the row-split kernel (aggregate_split.hip), chunks of that tile
-        if (p.cr == 0) {
-            set_error("zt_agg_train_forward: D=%d F=%d T=%d k=%d: no 16-row chunk fits %d KB of LDS", D, F, T, k, LDS_BUDGET / 1024);
-            return ZT_ERR_UNSUPPORTED;
-        }
-        embed_prepare(wt, D, F, T, p, ws, s);
-        return fc1_agg_split_launch(memory_dev, overlay_dev, row_map_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
-                                    M, k, nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_w1p),
-                                    p.K1p, wt->fc1_b, H_dev, S_dev, status_dev, drop_p, drop_seed, s);
-    }
+    const float *W1p = reinterpret_cast<const float *>(ws + p.off_w1p);
     embed_prepare(wt, D, F, T, p, ws, s);          // the weights change every optimizer step
-    static size_t attr_lds = 0;
-    if (p.lds > 48 * 1024 && p.lds > attr_lds) {
-        ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fc1_agg<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-        attr_lds = p.lds;
-    }
-    dim3 grid((unsigned)((N + p.rq - 1) / p.rq), (unsigned)M);
-    k_fc1_agg<false><<<grid, AGG_THREADS, p.lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, k,
-                                                    p.rq, p.mt, p.lda, nbr_dev, eix_dev, dt_dev, w_dev,
-                                                    reinterpret_cast<const float *>(ws + p.off_w1p), p.K1p, wt->fc1_b, H_dev,
-                                                    S_dev, status_dev, D, row_map_dev, overlay_dev, (unsigned)drop_seed,
-                                                    (unsigned)(drop_seed >> 32), zt::drop_threshold(drop_p),
-                                                    1.f / (1.f - drop_p));
+    if (kp.agg == AggKernel::split)                // a query row wider than the 80-row tile: chunks of that tile
+        return fc1_agg_split_launch(memory_dev, overlay_dev, row_map_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
+                                    M, k, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b, H_dev, S_dev, status_dev, drop_p,
+                                    drop_seed, s);
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg<false>), kp.lds));
+    dim3 grid((unsigned)((N + kp.rq - 1) / kp.rq), (unsigned)M);
+    k_fc1_agg<false><<<grid, AGG_THREADS, kp.lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, k,
+                                                     kp.rq, kp.mt, kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b,
+                                                     H_dev, S_dev, status_dev, D, row_map_dev, overlay_dev, (unsigned)drop_seed,
+                                                     (unsigned)(drop_seed >> 32), zt::drop_threshold(drop_p), 1.f / (1.f - drop_p));
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

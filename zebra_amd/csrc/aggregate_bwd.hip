@@ -329,12 +329,7 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     a.mt = mt;
     a.nch = nch;
     const size_t lds = lds_of(mt);
-    static size_t attr_lds = 0;
-    if (lds > 48 * 1024 && lds > attr_lds) {
-        ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fc1_agg_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        attr_lds = lds;
-    }
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_bwd), lds));
     hipDeviceProp_t prop;
     int dev = 0;
     ZT_HIP(hipGetDevice(&dev));

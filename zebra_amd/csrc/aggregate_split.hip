@@ -229,12 +229,7 @@ int zt::fc1_agg_split_launch(const float *memory, const float *overlay, const in
     }
     if (N == 0) return ZT_OK;
     const size_t lds = fc1_agg_split_lds(D, F, T);
-    static size_t attr_lds = 0;
-    if (lds > 48 * 1024 && lds > attr_lds) {
-        ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fc1_agg_split), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        attr_lds = lds;
-    }
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_split), lds));
     const unsigned thr = drop_threshold(drop_p);
     dim3 grid((unsigned)N, (unsigned)M);
     k_fc1_agg_split<<<grid, AGG_THREADS, lds, s>>>(memory, overlay, row_map, efeat, time_w, num_nodes, num_edges, D, F, T, N, k,

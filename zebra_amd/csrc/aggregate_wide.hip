@@ -388,25 +388,17 @@ int fc1_agg_wide_launch(const float *P, const float *efeat, const float *time_w,
     const int gt = gate ? gate->target : 0;
     int *gl = gate ? gate->latch : nullptr;
     const size_t lds = (size_t)WLDS_PAD * 4;
-    static size_t attr[2] = {0, 0};
-    const int ki = k == 20 ? 0 : 1;
-    if (lds > attr[ki]) {
-        const void *fn = k == 20 ? reinterpret_cast<const void *>(k_fc1_agg_wide<20>) : reinterpret_cast<const void *>(k_fc1_agg_wide<40>);
-        ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr[ki] = lds;
-    }
     const long long tiles = ((N * k + 15) / 16) * M;
     if (N * k * M >= (1ll << 31)) { set_error("k_fc1_agg_wide: N k M = %lld does not fit the kernel's 32-bit tile arithmetic", N * k * M); return ZT_ERR_UNSUPPORTED; }
     long long wgs = (tiles + WIDE_WAVES - 1) / WIDE_WAVES;
     if (wgs > cus) wgs = cus;                                              // persistent: one workgroup (4 waves) per CU
     if (wgs < 1) wgs = 1;
-    if (k == 20)
-        k_fc1_agg_wide<20><<<(unsigned)wgs, WIDE_THREADS, lds, s>>>(P, efeat, time_w, num_nodes, num_edges, N, M, nbr, eix, dt, w,
+    return dispatch<20, 40>(k, [&](auto KK) {
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_wide<KK>), lds));
+        k_fc1_agg_wide<KK><<<(unsigned)wgs, WIDE_THREADS, lds, s>>>(P, efeat, time_w, num_nodes, num_edges, N, M, nbr, eix, dt, w,
                                                                     packed, b1, G, S, status, gw, gt, gl);
-    else
-        k_fc1_agg_wide<40><<<(unsigned)wgs, WIDE_THREADS, lds, s>>>(P, efeat, time_w, num_nodes, num_edges, N, M, nbr, eix, dt, w,
-                                                                    packed, b1, G, S, status, gw, gt, gl);
-    return ZT_OK;
+        return ZT_OK;
+    });
 }
 
 }  // namespace zt

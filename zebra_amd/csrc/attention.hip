@@ -290,12 +290,7 @@ extern "C" int zt_temporal_attention(const float *src_dev, const float *src_time
     pad(w->out_w, d.E, d.E, Wo, d.Ep, d.Ep);
     pad(w->m1_w, hidden, d.E + D, W1, d.Hp, d.E2p);
     pad(w->m2_w, out_dim, hidden, W2, d.Op, d.Hp);
-    static size_t attr_lds = 0;
-    if (lds > 48 * 1024 && lds > attr_lds) {
-        ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_temporal_attention),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_temporal_attention), lds));
     const unsigned grid = (unsigned)((N + d.rq - 1) / d.rq);
     k_temporal_attention<<<grid, ATT_THREADS, lds, s>>>(d, N, src_dev, src_time_dev, nbr_feat_dev, edge_feat_dev,
                                                         nbr_time_dev, mask_dev, Wq, Wk, Wv, w->in_b, Wo, w->out_b, W1,

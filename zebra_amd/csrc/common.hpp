@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/zebra_amd.h"
 
@@ -32,9 +33,39 @@ int tppr_stream_ex(zt_tppr *h, const int32_t *nodes_dev, const double *ts_dev, c
 // k_member_gate).  A launch that k_count rejected (ZT_ERR_RANGE) writes its empty rows and sets every word to INT_MAX.
 constexpr int TPPR_MAX_MEMBERS = 8;         // batches per launch that can be released one by one
 constexpr int TPPR_MEMBER_WORDS = TPPR_MAX_MEMBERS + 1;      // (the last word: workgroups of a rejected launch that are through)
-// zt_gru_update with the projected-table refresh folded into the GRU kernel (memory_update.hip); wm_p from embed_wm_ptr.
-// counter_zeroed: the row counter (first word of the workspace) is zero already; select_done: the row list and the counter
-// are filled (pipeline.hip: the message kernel hands its list of winners over), no compaction of flagged ids
+// The output layers' arguments (k_embed_out, k_embed_out2, k_out_gru, k_out_gru2 take it by value: a kernel argument, keep
+// the layout)
+struct EmbedOutArgs {
+    const float *memory;
+    long long num_nodes;
+    const int *nodes;
+    long long N;
+    int D, M;
+    const float *H, *S, *fc2_p, *fc2_b, *fc1s_p, *fc1s_b, *fc2s_p, *fc2s_b;
+    float *out;
+    int *status;
+};
+// The embedding's kernels for one shape (aggregate.hip: embed_kernel_plan).  The aggregation: tiled_* = k_fc1_agg<TAB, MMT>
+// over the [ef | time] tile of the projected table or the full [memory | ef | time] one, *_big its MAX_MT_BIG instantiation
+// (80 < k); reg = k_fc1_agg_reg, wide = k_fc1_agg_wide (aggregate_wide.hip), d100 = k_fc1_agg_d100, split = k_fc1_agg_split
+// (aggregate_split.hip).  Every kernel of a family gives the same bits; the choice is speed only (tests/test_launch_plan_cpu.py).
+enum class AggKernel { unsupported, reg, wide, d100, tiled_table, tiled_full, tiled_table_big, tiled_full_big, split };
+// the output layers: k_embed_out (tiled), k_embed_out2 (latency: small batches), k_embed_out3 (persist: large ones)
+enum class OutForm { tiled, latency, persist };
+// why a shape is refused: no kernel or workspace for it / no tile holds a query row and no chunk of one fits (zt_embed: it needs
+// the projected table) / partial-sum groups the output layers have no instantiation for
+enum class Refusal { none, shape, no_split, groups };
+struct KernelPlan {
+    AggKernel agg;
+    OutForm out;
+    Refusal refusal;       // agg == unsupported: why
+    size_t lds;            // dynamic LDS of the tiled and d100 launches (the other launchers size their own)
+    int rq, mt, lda;       // their tile: query rows, 16-row M-tiles, leading dimension
+    int hg;                // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
+};
+// Pure host code (no HIP calls).  training: zt_agg_train_forward's choice (no table; tiled_full or split)
+KernelPlan embed_kernel_plan(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
+                             int out_choice);
 // The output layers of an embed call, held back (embed_ex: `defer`) so that gru_update_ex can launch them in ONE kernel with the
 // GRU update (k_out_gru, memory_update.hip): the two are independent apart from the memory rows the source path reads --
 // the GRU half waits for those reads before it writes (a gate in the GRU workspace whose whole state is device memory: a
@@ -42,18 +73,16 @@ constexpr int TPPR_MEMBER_WORDS = TPPR_MAX_MEMBERS + 1;      // (the last word: 
 // every launch finds them at zero whatever the host did in between; the wait is bounded and reports to `status` / `latch`).
 struct embed_out_deferred {
     bool valid;
-    const float *memory;
-    long long num_nodes;
-    const int *nodes;
-    long long N;
-    int D, M, hg;
-    int form, gx;          // 1: the tiled kernel (k_embed_out); 2: the latency-organised one (k_embed_out2), gx tiles' worth of waves per path and N-tile
-    const float *H, *S, *fc2_p, *fc2_b, *fc1s_p, *fc1s_b, *fc2s_p, *fc2s_b;
-    float *out;
-    int *status;
+    EmbedOutArgs args;
+    int hg;
+    OutForm form;          // (latency: gx tiles' worth of waves per path and N-tile; persist is never held back)
+    int gx;
     int *latch;            // host-mapped word a gate wait that gives up writes ZT_ERR_TIMEOUT to (or NULL); kept across embed_ex calls
 };
-int embed_out_launch(const embed_out_deferred &d, void *stream);           // aggregate.hip: the held-back layers as a kernel of their own
+int embed_out_launch(const embed_out_deferred &d, void *stream);           // aggregate.hip: the output layers as a kernel of their own
+// zt_gru_update with the projected-table refresh folded into the GRU kernel (memory_update.hip); wm_p from embed_wm_ptr.
+// counter_zeroed: the row counter (first word of the workspace) is zero already; select_done: the row list and the counter
+// are filled (pipeline.hip: the message kernel hands its list of winners over), no compaction of flagged ids
 int gru_update_ex(float *memory_dev, float *last_update_dev, const float *messages_dev, const float *msg_ts_dev,
                   uint8_t *flags_dev, int64_t num_nodes, int32_t D, int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
                   const int32_t *n_ids_dev, const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready,
@@ -114,6 +143,19 @@ int exchange_step(zt_exchange *x, const int32_t *rows_dev, const int32_t *count_
                   int64_t *n_ids_out);
 void exchange_shape(const zt_exchange *x, int *rank, int *world);
 constexpr int TPPR_MAX_LAUNCH = 16384;     // edges one T-PPR launch can cover (tppr_stream.hip: MAX_CHUNK)
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel fn raised to `bytes` where that is above 48 KB and above what was set
+// for fn before (runtime.hip)
+hipError_t set_dynamic_lds(const void *fn, size_t bytes);
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v -- one instantiation of f per value -- and the ZT_* code
+// it returns; ZT_ERR_UNSUPPORTED where v is none of Vs
+template <int... Vs, class Fn>
+int dispatch(int v, Fn &&f)
+{
+    int rc = ZT_ERR_UNSUPPORTED;
+    (void)((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
+    return rc;
+}
 
 // flags of the events that only order streams of this device
 inline unsigned sync_event_flags() { return 0u; }

@@ -75,17 +75,7 @@ __device__ __forceinline__ void small_gemm(const float *X, int ldx, const float 
     }
 }
 
-// what the output layers need (by value: the fused kernel of memory_update.hip takes it beside the GRU's arguments)
-struct EmbedOutArgs {
-    const float *memory;
-    long long num_nodes;
-    const int *nodes;
-    long long N;
-    int D, M;
-    const float *H, *S, *fc2_p, *fc2_b, *fc1s_p, *fc1s_b, *fc2s_p, *fc2s_b;
-    float *out;
-    int *status;
-};
+using zt::EmbedOutArgs;          // (common.hpp)
 
 // bx = 32-row tile, path = 0 (source path) or 1 + model; the first AGG_THREADS threads of the workgroup.  src_read != nullptr:
 // a source-path workgroup adds 1 there once its memory rows are in LDS (k_out_gru: the GRU half waits for all of them before

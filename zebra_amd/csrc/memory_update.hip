@@ -955,44 +955,32 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
     const bool split = fits && (choice == ZT_GRU_SPLIT || (choice == 0 && max_rows <= 512));
     if (split) {
         const size_t lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
-        static size_t attr2 = 0;
-        if (lds2 > 48 * 1024 && lds2 > attr2) {
-            ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            attr2 = lds2;
-        }
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split), lds2));
         GruSplitArgs GS;
         GS.g.memory = memory_dev; GS.g.last_update = last_update_dev; GS.g.messages = messages_dev; GS.g.msg_ts = msg_ts_dev; GS.g.rows = rows;
         GS.g.n_rows = cnt; GS.g.D = D; GS.g.msg_dim = msg_dim; GS.g.Xp = p.Xp; GS.g.Hp = p.Hp; GS.g.lda = p.lda; GS.g.Wih_p = wih; GS.g.Whh_p = whh;
         GS.g.b_ih = wt->b_ih; GS.g.b_hh = wt->b_hh; GS.g.Wm_p = wm_p; GS.g.P = proj_table; GS.g.cap = (int)max_rows;
         GS.tile_cnt = reinterpret_cast<int *>(ws + p.off_tiles); GS.hnew = reinterpret_cast<float *>(ws + p.off_hnew);
         const int gru_tiles = (int)((max_rows + 15) / 16), NTg = p.Hp / 16;
-        const bool can_fuse2 = fuse != nullptr && fuse->valid && fuse->form == 2 && fuse->memory == memory_dev &&
-                               (fuse->D + 15) / 16 == NTg && (NTg == 7 || NTg == 8) && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10);
+        const bool can_fuse2 = fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::latency && fuse->args.memory == memory_dev &&
+                               (fuse->args.D + 15) / 16 == NTg && (NTg == 7 || NTg == 8) && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10);
         if (can_fuse2) {
             const zt::embed_out_deferred &d = *fuse;
-            EmbedOutArgs E;
-            E.memory = d.memory; E.num_nodes = d.num_nodes; E.nodes = d.nodes; E.N = d.N; E.D = d.D; E.M = d.M; E.H = d.H; E.S = d.S;
-            E.fc2_p = d.fc2_p; E.fc2_b = d.fc2_b; E.fc1s_p = d.fc1s_p; E.fc1s_b = d.fc1s_b; E.fc2s_p = d.fc2s_p; E.fc2s_b = d.fc2s_b;
-            E.out = d.out; E.status = d.status;
-            const int per_path = d.gx * NTg, n_src_wgs = (per_path + 3) / 4, n_nb_wgs = (per_path * d.M + 3) / 4;
+            const int per_path = d.gx * NTg, n_src_wgs = (per_path + 3) / 4, n_nb_wgs = (per_path * d.args.M + 3) / 4;
             size_t lds_f = (size_t)4 * 16 * (NTg * 16 + 4) * 4;
             if (lds_f < lds2) lds_f = lds2;
             SrcGate gate;
             gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)per_path; gate.participants = (unsigned)(per_path + gru_tiles * NTg);
-            gate.status = d.status; gate.latch = d.latch;
+            gate.status = d.args.status; gate.latch = d.latch;
             const unsigned grid = (unsigned)(n_src_wgs + gru_tiles * NTg + n_nb_wgs);
-#define ZT_OG2(NTV, HGV) do {                                                                                                   \
-                static size_t attr_og2 = 0;                                                                                     \
-                if (lds_f > 48 * 1024 && lds_f > attr_og2) {                                                                    \
-                    ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_out_gru2<NTV, HGV>),                            \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));                       \
-                    attr_og2 = lds_f;                                                                                           \
-                }                                                                                                               \
-                k_out_gru2<NTV, HGV><<<grid, 64 * GS_WAVES, lds_f, s>>>(E, d.gx, n_src_wgs, gru_tiles, GS, gate);                 \
-            } while (0)
-            if (NTg == 7) { if (d.hg == 1) ZT_OG2(7, 1); else if (d.hg == 5) ZT_OG2(7, 5); else ZT_OG2(7, 10); }
-            else          { if (d.hg == 1) ZT_OG2(8, 1); else if (d.hg == 5) ZT_OG2(8, 5); else ZT_OG2(8, 10); }
-#undef ZT_OG2
+            const int rc = dispatch<7, 8>(NTg, [&](auto NTV) {
+                return dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
+                    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru2<NTV, HGV>), lds_f));
+                    k_out_gru2<NTV, HGV><<<grid, 64 * GS_WAVES, lds_f, s>>>(d.args, d.gx, n_src_wgs, gru_tiles, GS, gate);
+                    return ZT_OK;
+                });
+            });
+            if (rc != ZT_OK) return rc;
             fuse->valid = false;
         } else {
             // (held-back output layers first: their source path reads the rows this kernel rewrites)
@@ -1001,41 +989,29 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
         }
     } else {
         const size_t lds = (size_t)16 * p.lda * 4 + 32 * 4;              // A tile + node ids + the gate's verdict (k_out_gru)
-        static size_t attr_lds = 0;
-        if (lds > 48 * 1024 && lds > attr_lds) {
-            ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_lds = lds;
-        }
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<1>), lds));
         GruArgs G;
         G.memory = memory_dev; G.last_update = last_update_dev; G.messages = messages_dev; G.msg_ts = msg_ts_dev; G.rows = rows; G.n_rows = cnt;
         G.D = D; G.msg_dim = msg_dim; G.Xp = p.Xp; G.Hp = p.Hp; G.lda = p.lda; G.Wih_p = wih; G.Whh_p = whh; G.b_ih = wt->b_ih; G.b_hh = wt->b_hh;
         G.Wm_p = wm_p; G.P = proj_table; G.cap = (int)max_rows;
         const unsigned gru_wgs = (unsigned)((max_rows + 15) / 16);
-        if (fuse != nullptr && fuse->valid && fuse->form == 1 && fuse->memory == memory_dev && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10)) {
+        if (fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::tiled && fuse->args.memory == memory_dev &&
+            (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10)) {
             const zt::embed_out_deferred &d = *fuse;
-            EmbedOutArgs E;
-            E.memory = d.memory; E.num_nodes = d.num_nodes; E.nodes = d.nodes; E.N = d.N; E.D = d.D; E.M = d.M; E.H = d.H; E.S = d.S;
-            E.fc2_p = d.fc2_p; E.fc2_b = d.fc2_b; E.fc1s_p = d.fc1s_p; E.fc1s_b = d.fc1s_b; E.fc2s_p = d.fc2s_p; E.fc2s_b = d.fc2s_b;
-            E.out = d.out; E.status = d.status;
-            const int out_tiles = (int)((d.N + OUT_ROWS - 1) / OUT_ROWS), n_out = out_tiles * (d.M + 1);
-            const int Dp = (d.D + 15) / 16 * 16;
+            const int out_tiles = (int)((d.args.N + OUT_ROWS - 1) / OUT_ROWS), n_out = out_tiles * (d.args.M + 1);
+            const int Dp = (d.args.D + 15) / 16 * 16;
             size_t lds_f = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
             if (lds_f < lds) lds_f = lds;
-            const void *fn = d.hg == 1 ? reinterpret_cast<const void *>(k_out_gru<1>)
-                                       : (d.hg == 5 ? reinterpret_cast<const void *>(k_out_gru<5>) : reinterpret_cast<const void *>(k_out_gru<10>));
-            static size_t attr_f[3] = {0, 0, 0};
-            const int hi = d.hg == 1 ? 0 : (d.hg == 5 ? 1 : 2);
-            if (lds_f > 48 * 1024 && lds_f > attr_f[hi]) {
-                ZT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-                attr_f[hi] = lds_f;
-            }
             SrcGate gate;
             gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)out_tiles; gate.participants = (unsigned)out_tiles + gru_wgs;
-            gate.status = d.status; gate.latch = d.latch;
+            gate.status = d.args.status; gate.latch = d.latch;
             const unsigned grid = (unsigned)n_out + gru_wgs;
-            if (d.hg == 1) k_out_gru<1><<<grid, 64 * GRU_WAVES, lds_f, s>>>(E, out_tiles, (int)gru_wgs, G, gate);
-            else if (d.hg == 5) k_out_gru<5><<<grid, 64 * GRU_WAVES, lds_f, s>>>(E, out_tiles, (int)gru_wgs, G, gate);
-            else k_out_gru<10><<<grid, 64 * GRU_WAVES, lds_f, s>>>(E, out_tiles, (int)gru_wgs, G, gate);
+            const int rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru<HGV>), lds_f));
+                k_out_gru<HGV><<<grid, 64 * GRU_WAVES, lds_f, s>>>(d.args, out_tiles, (int)gru_wgs, G, gate);
+                return ZT_OK;
+            });
+            if (rc != ZT_OK) return rc;
             fuse->valid = false;                       // (launched)
         } else {
             if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 namespace zt {
@@ -65,6 +66,22 @@ void prof_end(hipStream_t s, int id)
 // ---- kernel selection overrides (zt_set_kernel_choice) ---------------------------------
 namespace { int g_choice[ZT_CHOICE_COUNT] = {0}; }
 int kernel_choice(int which) { return (which >= 0 && which < ZT_CHOICE_COUNT) ? g_choice[which] : 0; }
+
+// ---- dynamic LDS above the 48 KB default ------------------------------------------------
+hipError_t set_dynamic_lds(const void *fn, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return hipSuccess;
+    // the largest value set per kernel; a kernel beyond the table's room is set on every call
+    static std::mutex mu;
+    static struct { const void *fn; size_t bytes; } done[64];
+    std::lock_guard<std::mutex> lock(mu);
+    int i = 0;
+    while (i < 64 && done[i].fn != nullptr && done[i].fn != fn) ++i;
+    if (i < 64 && done[i].fn == fn && done[i].bytes >= bytes) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && i < 64) done[i] = {fn, bytes};
+    return e;
+}
 
 // CUs the stream may use (CU-masked streams: the size of the mask).  Queried per call: a cache keyed by the stream
 // handle goes stale when a pipeline is destroyed and the runtime hands the same handle value to a stream with another

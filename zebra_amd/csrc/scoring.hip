@@ -399,14 +399,10 @@ extern "C" int zt_affinity(const float *emb_dev, int64_t B, int32_t H, const zt_
         // 16 edges per workgroup while that fills the chip once (two workgroups fit a CU), 32 beyond
         const int et = B <= 16 * 512 ? 16 : 32;
         const size_t lds = ((size_t)3 * et * (p.Hp + 4) + 4 * 2 * et) * 4;
-        static size_t attr[4] = {0, 0, 0, 0};
         const int ki = (p.Hp == 304 ? 0 : 1) * 2 + (et == 16 ? 0 : 1);
         const void *fns[4] = {reinterpret_cast<const void *>(k_affinity_tiled<19, 16>), reinterpret_cast<const void *>(k_affinity_tiled<19, 32>),
                               reinterpret_cast<const void *>(k_affinity_tiled<13, 16>), reinterpret_cast<const void *>(k_affinity_tiled<13, 32>)};
-        if (lds > attr[ki]) {
-            ZT_HIP(hipFuncSetAttribute(fns[ki], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr[ki] = lds;
-        }
+        ZT_HIP(set_dynamic_lds(fns[ki], lds));
         const unsigned wgs = (unsigned)((B + et - 1) / et);
         if (ki == 0)      k_affinity_tiled<19, 16><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
         else if (ki == 1) k_affinity_tiled<19, 32><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
@@ -427,11 +423,7 @@ extern "C" int zt_link_metrics(const float *pos_dev, const float *neg_dev, int64
     int n2 = MT_THREADS;                                                  // >= one element per thread keeps the chunks simple
     while (n2 < 2 * B) n2 <<= 1;
     const size_t lds = (size_t)n2 * 8;
-    static size_t attr = 0;
-    if (lds > 48 * 1024 && lds > attr) {
-        ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_link_metrics), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_link_metrics), lds));
     k_link_metrics<<<1, MT_THREADS, lds, (hipStream_t)stream>>>(pos_dev, neg_dev, (int)B, n2, out_dev, accumulate);
     ZT_LAUNCH_CHECK();
     return ZT_OK;

@@ -27,6 +27,12 @@ int zt_test_set_epoch(zt_tppr *h, uint32_t epoch);
  * planned launch's edges), owner_of [B], chain_node / chain_len [16], chain_edges [16][2048], *n_chains. */
 int zt_test_tppr_plan_dump(zt_tppr *h, int32_t *wo, int32_t *pflag, int32_t *hv, int32_t *owner_of, int32_t *chain_node,
                            int32_t *chain_len, int32_t *chain_edges, int32_t *n_chains);
+/* Test hook: the embedding's kernel choice for one shape (zt::embed_kernel_plan, host code only): *agg_out = 0 unsupported,
+ * 1 reg, 2 wide, 3 d100, 4 tiled table, 5 tiled full, 6 / 7 the same two with the big tile, 8 row split; *out_out = 0 tiled,
+ * 1 latency, 2 persist (the output layers); *lds_out = the tiled / d100 launch's dynamic LDS.  training: zt_agg_train_forward's
+ * choice; agg_choice / out_choice: the ZT_CHOICE_AGGREGATE / ZT_CHOICE_EMBED_OUT selections. */
+int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table, int32_t training,
+                       int32_t agg_choice, int32_t out_choice, int32_t *agg_out, int32_t *out_out, int64_t *lds_out);
 
 #ifdef __cplusplus
 }

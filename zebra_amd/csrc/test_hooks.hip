@@ -114,3 +114,15 @@ extern "C" int zt_test_tppr_plan_dump(zt_tppr *h, int32_t *wo, int32_t *pflag, i
     ZT_HIP(hipMemcpy(n_chains, P.ctl + 4, sizeof(int), hipMemcpyDeviceToHost));
     return ZT_OK;
 }
+
+extern "C" int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table,
+                                  int32_t training, int32_t agg_choice, int32_t out_choice, int32_t *agg_out, int32_t *out_out,
+                                  int64_t *lds_out)
+{
+    if (!agg_out || !out_out || !lds_out) return ZT_ERR_ARG;
+    const KernelPlan kp = embed_kernel_plan(N, D, F, T, M, k, have_table != 0, training != 0, agg_choice, out_choice);
+    *agg_out = (int32_t)kp.agg;
+    *out_out = (int32_t)kp.out;
+    *lds_out = (int64_t)kp.lds;
+    return ZT_OK;
+}

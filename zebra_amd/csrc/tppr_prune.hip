@@ -496,12 +496,7 @@ static int pruned_launch(const zt_csr *c, const int32_t *q_nodes_dev, const doub
         pm.M = mm;
         for (int q = 0; q < mm; ++q) { pm.alpha[q] = alpha[m0 + q]; pm.beta[q] = beta[m0 + q]; }
         const size_t lds = prune_lds_bytes(cap_c, cap_f, mm, k) * PR_WAVES;
-        static size_t attr_lds = 0;
-        if (lds > 48 * 1024 && lds > attr_lds) {
-            ZT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pruned_topk),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_lds = lds;
-        }
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_pruned_topk), lds));
         const int grid = (int)((nq + PR_WAVES - 1) / PR_WAVES);
         const size_t o = (size_t)m0 * nq * k;
         ZT_PROF_BEGIN(s, P_PRUNE);
