@@ -417,6 +417,31 @@ int zt_gru_update(float *memory_dev, float *last_update_dev,
                   const int32_t *n_ids_dev, const zt_gru_weights *weights,
                   void *workspace_dev, int32_t weights_ready, void *stream);
 
+/* The memory cell of an update: nn.GRUCell (zt_gru_update, the default) or
+ * nn.RNNCell (zt_rnn_update); zt_pipeline_set_cell picks it for a pipeline. */
+#define ZT_CELL_GRU 0
+#define ZT_CELL_RNN 1
+
+/* zt_gru_update with nn.RNNCell in place of nn.GRUCell: RNNMemoryUpdater
+ * (modules/memory_updater.py:100-103) with the cell's defaults (tanh, biases),
+ *   memory = tanh(W_ih messages + b_ih + W_hh memory + b_hh).
+ * The arguments are those of zt_gru_update; `weights` holds the RNN's shapes:
+ * w_ih [D][msg], w_hh [D][D], b_ih and b_hh [D].  The workspace is the GRU's
+ * (zt_gru_workspace_bytes, zt_gru_rows_offset: the row count and the row ids
+ * sit where they sit for the GRU; the packed weights use the first third of
+ * its weight region).  A workspace packed for the other cell must be called
+ * with weights_ready = 0.  The bounds are the GRU's: ZT_ERR_UNSUPPORTED for
+ * D > 128 and for a message width whose staging tile needs more than 150 KB of
+ * LDS (128 * (round16(msg_dim) + round16(D) + 4) + 128 bytes, the same limit
+ * zt_gru_update applies).  zt_set_kernel_choice(ZT_CHOICE_GRU, ZT_GRU_TILE /
+ * ZT_GRU_SPLIT) pins the kernel form for both cells. */
+int zt_rnn_update(float *memory_dev, float *last_update_dev,
+                  const float *messages_dev, const float *msg_ts_dev,
+                  uint8_t *flags_dev, int64_t num_nodes, int32_t D,
+                  int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
+                  const int32_t *n_ids_dev, const zt_gru_weights *weights,
+                  void *workspace_dev, int32_t weights_ready, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Training-side dense operators on exact-f32 MFMA (csrc/train_ops.hip).       */
 /*   What the reference's autograd does with nn.GRUCell (get_updated_memory,   */
@@ -456,6 +481,21 @@ int zt_gru_train_forward(const float *messages_dev, const float *memory_dev,
  * it holds the gathered rows (the tables themselves change between forward
  * and backward, model/tgn_model.py:155-168). */
 int zt_gru_train_backward(const float *d_h_dev, const float *messages_dev,
+                          const float *memory_dev, const int32_t *ids_dev, int64_t U,
+                          int32_t D, int32_t msg_dim, const float *saved_dev,
+                          float *d_w_ih_dev, float *d_w_hh_dev, float *d_b_ih_dev,
+                          float *d_b_hh_dev, void *workspace_dev, void *stream);
+/* The same pair for nn.RNNCell (RNNMemoryUpdater): h_out[u] = tanh(W_ih x + b_ih
+ * + W_hh h + b_hh) with x = messages[ids[u]], h = memory[ids[u]]; weights as for
+ * zt_rnn_update.  saved is [U][D] and holds h_out.  The backward writes dW_ih
+ * [D][msg], dW_hh [D][D], db_ih and db_hh [D].  The arguments, the workspace
+ * (zt_gru_train_workspace_bytes) and the rule that the backward gets the
+ * forward's workspace untouched are the GRU pair's. */
+int zt_rnn_train_forward(const float *messages_dev, const float *memory_dev,
+                         const int32_t *ids_dev, int64_t U, int32_t D, int32_t msg_dim,
+                         const zt_gru_weights *weights, float *h_out_dev, float *saved_dev,
+                         void *workspace_dev, void *stream);
+int zt_rnn_train_backward(const float *d_h_dev, const float *messages_dev,
                           const float *memory_dev, const int32_t *ids_dev, int64_t U,
                           int32_t D, int32_t msg_dim, const float *saved_dev,
                           float *d_w_ih_dev, float *d_w_hh_dev, float *d_b_ih_dev,
@@ -522,6 +562,10 @@ int zt_pipeline_step(zt_pipeline *p, const zt_batch *cur, const zt_batch *next, 
  * a group are equally long (the last may be shorter) and together at most 16384 edges.  zt_pipeline_step is this
  * call with ahead = {next, plan}.  The pruning strategy carries no state between batches: its group is 1. */
 int zt_pipeline_set_group(zt_pipeline *p, int32_t group);
+/* The memory cell of the pipeline's update: ZT_CELL_GRU (the default; desc.gw holds nn.GRUCell's weights) or
+ * ZT_CELL_RNN (desc.gw holds nn.RNNCell's, shapes as for zt_rnn_update; desc.gru_ws is sized as for the GRU).
+ * It takes effect at the next step, which packs the weights afresh.  ZT_ERR_ARG for a NULL pipeline or another value. */
+int zt_pipeline_set_cell(zt_pipeline *p, int32_t cell);
 /* embedding_module.average_topk (modules/embedding_module.py:232-233): with a non-NULL device float, every step
  * over a whole batch also writes the mean over the 2B rows of [src | dst] of the sum of model 0's T-PPR weights
  * there (main stream).  NULL switches it off. */

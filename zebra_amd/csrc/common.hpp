@@ -82,12 +82,13 @@ struct embed_out_deferred {
 int embed_out_launch(const embed_out_deferred &d, void *stream);           // aggregate.hip: the output layers as a kernel of their own
 // zt_gru_update with the projected-table refresh folded into the GRU kernel (memory_update.hip); wm_p from embed_wm_ptr.
 // counter_zeroed: the row counter (first word of the workspace) is zero already; select_done: the row list and the counter
-// are filled (pipeline.hip: the message kernel hands its list of winners over), no compaction of flagged ids
+// are filled (pipeline.hip: the message kernel hands its list of winners over), no compaction of flagged ids.
+// cell: ZT_CELL_GRU (zt_gru_update) or ZT_CELL_RNN (zt_rnn_update: wt holds the RNNCell's weights), same workspace
 int gru_update_ex(float *memory_dev, float *last_update_dev, const float *messages_dev, const float *msg_ts_dev,
                   uint8_t *flags_dev, int64_t num_nodes, int32_t D, int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
                   const int32_t *n_ids_dev, const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready,
                   const float *wm_p, float *proj_table, void *stream, bool counter_zeroed = false, bool select_done = false,
-                  embed_out_deferred *fuse = nullptr);
+                  embed_out_deferred *fuse = nullptr, int cell = ZT_CELL_GRU);
 // zt_store_messages_range that also zeroes one int (the GRU update's row counter: first word of its workspace)
 int store_messages_ex(const float *memory_dev, const float *last_update_dev, const float *efeat_dev, const float *time_w_dev,
                       int64_t num_nodes, int64_t num_edges, int32_t D, int32_t F, int32_t T, const int32_t *src_dev,

@@ -243,14 +243,21 @@ __device__ __forceinline__ void gate_leave(const SrcGate &g)
     if (before + 1u == g.participants) { st_agent(g.word, 0); st_agent(g.word + 1, 0); }
 }
 
-// Zero-padded gate-major copy in FRAGMENT order: W[3D][K] -> Wp[3][Dp / 16][Kp / 16][64 lanes][4]: the 16 x 16 block (N-tile
+// The cell of the memory update (zt_gru_update / zt_rnn_update): torch.nn.GRUCell (gates r, z, n) or torch.nn.RNNCell with
+// its defaults (tanh, biases): h' = tanh(W_ih x + b_ih + W_hh h + b_hh), the one-gate case of the same kernels.
+constexpr int CELL_GRU = ZT_CELL_GRU, CELL_RNN = ZT_CELL_RNN;
+template <int CELL> constexpr int cell_gates() { return CELL == CELL_RNN ? 1 : 3; }
+
+// Zero-padded gate-major copy in FRAGMENT order: W[NG D][K] -> Wp[NG][Dp / 16][Kp / 16][64 lanes][4] (NG gates: 3 for the GRU,
+// 1 for the RNN): the 16 x 16 block (N-tile
 // nt, k-chunk kc) of a gate as the MFMA's lanes hold it -- lane (r16, g4) has W[16 nt + r16][16 kc + 4 g4 .. + 3] -- so that a
 // wave's fragment load is ONE contiguous kilobyte.  (Row-major, the same load touched sixteen 128-byte lines and used half
 // of each: k_gru streams all 559 KB of gate weights per 16-row tile from L2, 286 MB per launch at C5's batch.)
+template <int NG>
 __global__ void k_pack_gates(const float *__restrict__ W, int D, int K, float *__restrict__ Wp, int Dp, int Kp)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 3 * Dp * Kp) return;
+    if (i >= NG * Dp * Kp) return;
     const int e = i & 3, lane = (i >> 2) & 63, rest = i >> 8;
     const int KC = Kp / 16, NT = Dp / 16;
     const int kc = rest % KC, nt = (rest / KC) % NT, g = rest / (KC * NT);
@@ -270,7 +277,8 @@ struct GruArgs {
 
 // bid = the workgroup's 16 MT-row tile.  gate != nullptr (k_out_gru): before a row of the memory table is written every
 // source-path workgroup of the output layers must have its rows in LDS (SrcGate; LDS: one word more behind the node ids).
-template <int MT>
+// CELL_RNN: one gate -- the message part and the memory part in accumulators of their own (ani, anh), added after the biases.
+template <int CELL, int MT>
 __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, const SrcGate *gate)
 {
     float *memory = G.memory, *last_update = G.last_update;
@@ -361,9 +369,13 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
                     const bool on = live[b] && kc0 + c < KC;
                     const size_t o = (((size_t)(colrow[b] >> 4) * KC + (on ? kc0 + c : 0)) * 64 + lane) * 4;       // (fragment order: k_pack_gates)
                     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-                    wr[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + o) : zero;
-                    wz[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)Dp * Kp + o) : zero;
-                    wn[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)2 * Dp * Kp + o) : zero;
+                    if constexpr (CELL == CELL_GRU) {
+                        wr[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + o) : zero;
+                        wz[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)Dp * Kp + o) : zero;
+                        wn[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)2 * Dp * Kp + o) : zero;
+                    } else {
+                        wn[c][b] = on ? *reinterpret_cast<const f32x4 *>(Wp + o) : zero;
+                    }
                 }
 #pragma unroll
             for (int c = 0; c < GRU_CH; ++c) {
@@ -379,8 +391,10 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
                     for (int a = 0; a < MT; ++a)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            ar[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wr[c][b][j], ar[a][b], 0, 0, 0);
-                            az[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wz[c][b][j], az[a][b], 0, 0, 0);
+                            if constexpr (CELL == CELL_GRU) {
+                                ar[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wr[c][b][j], ar[a][b], 0, 0, 0);
+                                az[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wz[c][b][j], az[a][b], 0, 0, 0);
+                            }
                             if (hidden) anh[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wn[c][b][j], anh[a][b], 0, 0, 0);
                             else        ani[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wn[c][b][j], ani[a][b], 0, 0, 0);
                         }
@@ -398,11 +412,26 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
         if (rid[MT * 16] == 0) return;                 // (gave up: reported; the table keeps its rows)
     } else if (P != nullptr) __syncthreads();
     // gates (torch.nn.GRUCell): r,z = sigmoid(gi+gh); n = tanh(gi_n + r*gh_n); h' = (1-z)*n + z*h
+    // (torch.nn.RNNCell: h' = tanh((gi + b_ih) + (gh + b_hh)))
 #pragma unroll
     for (int b = 0; b < GRU_NTW; ++b) {
         if (!live[b]) continue;
         const int col = (wave + b * GRU_WAVES) * 16 + r16;
         if (col >= D) continue;
+        if constexpr (CELL == CELL_RNN) {
+            const float bi = b_ih[col], bh = b_hh[col];
+#pragma unroll
+            for (int a = 0; a < MT; ++a)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int g = a * 16 + g4 * 4 + j;
+                    if (g >= nr) continue;
+                    const float hnew = tanhf((ani[a][b][j] + bi) + (anh[a][b][j] + bh));
+                    memory[(size_t)rid[g] * D + col] = hnew;
+                    if (P != nullptr) A[(size_t)g * lda + Xp + col] = hnew;
+                }
+            continue;
+        }
         const float bir = b_ih[col], biz = b_ih[D + col], bin = b_ih[2 * D + col];
         const float bhr = b_hh[col], bhz = b_hh[D + col], bhn = b_hh[2 * D + col];
 #pragma unroll
@@ -455,11 +484,11 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     }
 }
 
-template <int MT>
+template <int CELL, int MT>
 __global__ __launch_bounds__(64 * GRU_WAVES) void k_gru(GruArgs G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gru_body<MT>(G, smem, blockIdx.x, nullptr);
+    gru_body<CELL, MT>(G, smem, blockIdx.x, nullptr);
 }
 
 // The output layers and the GRU update in ONE launch (round 5).  The two kernels are independent but for the memory rows the
@@ -468,13 +497,13 @@ __global__ __launch_bounds__(64 * GRU_WAVES) void k_gru(GruArgs G)
 // path of k_embed_out's body (they are dispatched first, so the GRU half's wait for their reads can never be a wait for a
 // workgroup that has no compute unit), then the GRU tiles (the longest chains: not behind 200 short workgroups' dispatch),
 // then the neighbour paths.
-template <int HG>
+template <int CELL, int HG>
 __global__ __launch_bounds__(64 * GRU_WAVES) void k_out_gru(EmbedOutArgs E, int out_tiles, int gru_wgs, GruArgs G, SrcGate gate)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int bid = blockIdx.x;
     if (bid >= out_tiles && bid < out_tiles + gru_wgs) {
-        gru_body<1>(G, smem, bid - out_tiles, &gate);
+        gru_body<CELL, 1>(G, smem, bid - out_tiles, &gate);
         if (threadIdx.x == 0) gate_leave(gate);              // (thread 0 is the one that waited, if the tile had rows at all)
         return;
     }
@@ -517,7 +546,8 @@ struct GruSplitArgs {
 };
 
 // (bx, by) = (16-row tile, N-tile).  gate != nullptr (k_out_gru2): the tile's last workgroup waits at the gate (SrcGate)
-// before it commits the rows to the memory table.
+// before it commits the rows to the memory table.  CELL_RNN: one gate, partial sums ani (message) and anh (memory).
+template <int CELL>
 __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *smem, int bx, int by, const SrcGate *gate)
 {
     const GruArgs &G = GS.g;
@@ -554,13 +584,20 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *sme
         const float *W = hid ? Whh_p : Wih_p;
         const int Kp = hid ? Hp : Xp, cc = hid ? c - KCx : c;
         const size_t o = (((size_t)nt * (Kp / 16) + (on ? cc : 0)) * 64 + lane) * 4;                           // (fragment order: k_pack_gates)
-        wr[q] = on ? *reinterpret_cast<const f32x4 *>(W + o) : zero4;
-        wz[q] = on ? *reinterpret_cast<const f32x4 *>(W + (size_t)Hp * Kp + o) : zero4;
-        wn[q] = on ? *reinterpret_cast<const f32x4 *>(W + (size_t)2 * Hp * Kp + o) : zero4;
+        if constexpr (CELL == CELL_GRU) {
+            wr[q] = on ? *reinterpret_cast<const f32x4 *>(W + o) : zero4;
+            wz[q] = on ? *reinterpret_cast<const f32x4 *>(W + (size_t)Hp * Kp + o) : zero4;
+            wn[q] = on ? *reinterpret_cast<const f32x4 *>(W + (size_t)2 * Hp * Kp + o) : zero4;
+        } else {
+            wn[q] = on ? *reinterpret_cast<const f32x4 *>(W + o) : zero4;
+        }
     }
     const bool cin = col < D;
-    const float bir = cin ? b_ih[col] : 0.f, biz = cin ? b_ih[D + col] : 0.f, bin = cin ? b_ih[2 * D + col] : 0.f;
-    const float bhr = cin ? b_hh[col] : 0.f, bhz = cin ? b_hh[D + col] : 0.f, bhn = cin ? b_hh[2 * D + col] : 0.f;
+    // (CELL_RNN: bin / bhn are its b_ih, b_hh; the GRU's r and z biases are not read)
+    const float bir = (CELL == CELL_GRU && cin) ? b_ih[col] : 0.f, biz = (CELL == CELL_GRU && cin) ? b_ih[D + col] : 0.f;
+    const float bin = cin ? b_ih[(CELL == CELL_GRU ? 2 * D : 0) + col] : 0.f;
+    const float bhr = (CELL == CELL_GRU && cin) ? b_hh[col] : 0.f, bhz = (CELL == CELL_GRU && cin) ? b_hh[D + col] : 0.f;
+    const float bhn = cin ? b_hh[(CELL == CELL_GRU ? 2 * D : 0) + col] : 0.f;
     if (tid < 16) rid[tid] = tid < nr ? id_spec : 0;
     for (int f = tid; f < 16 * lda; f += 256) A[f] = 0.f;                // padding columns, rows beyond nr
     __syncthreads();
@@ -592,21 +629,38 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *sme
         const f32x4 av = *reinterpret_cast<const f32x4 *>(A + r16 * lda + 16 * c + 4 * g4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            ar = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wr[q][j], ar, 0, 0, 0);
-            az = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wz[q][j], az, 0, 0, 0);
+            if constexpr (CELL == CELL_GRU) {
+                ar = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wr[q][j], ar, 0, 0, 0);
+                az = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wz[q][j], az, 0, 0, 0);
+            }
             if (hid) anh = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wn[q][j], anh, 0, 0, 0);
             else     ani = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wn[q][j], ani, 0, 0, 0);
         }
     }
     GSTAMP(4);
     f32x4 *rw = reinterpret_cast<f32x4 *>(red) + (size_t)wave * 4 * 64;
-    rw[0 * 64 + lane] = ar; rw[1 * 64 + lane] = az; rw[2 * 64 + lane] = ani; rw[3 * 64 + lane] = anh;
+    if constexpr (CELL == CELL_GRU) { rw[0 * 64 + lane] = ar; rw[1 * 64 + lane] = az; }
+    rw[2 * 64 + lane] = ani; rw[3 * 64 + lane] = anh;
     __syncthreads();
     GSTAMP(5);
     if (wave == 0) {
         // gates (torch.nn.GRUCell): r, z = sigmoid(gi + gh); n = tanh(gi_n + r gh_n); h' = (1 - z) n + z h; the four waves'
         // partial sums are added in wave order
         const f32x4 *rr = reinterpret_cast<const f32x4 *>(red);
+        if constexpr (CELL == CELL_RNN) {
+            // torch.nn.RNNCell: h' = tanh((gi + b_ih) + (gh + b_hh)); the partial sums added in wave order
+            f32x4 sni = rr[2 * 64 + lane], snh = rr[3 * 64 + lane];
+#pragma unroll
+            for (int wv = 1; wv < GS_WAVES; ++wv) { sni += rr[(wv * 4 + 2) * 64 + lane]; snh += rr[(wv * 4 + 3) * 64 + lane]; }
+            if (cin) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int g = 4 * g4 + j;
+                    if (g >= nr) continue;
+                    st_agent(reinterpret_cast<int *>(hnew + (size_t)(r0 + g) * Hp + col), __float_as_int(tanhf((sni[j] + bin) + (snh[j] + bhn))));
+                }
+            }
+        } else {
         f32x4 sr = rr[0 * 64 + lane], sz = rr[1 * 64 + lane], sni = rr[2 * 64 + lane], snh = rr[3 * 64 + lane];
 #pragma unroll
         for (int wv = 1; wv < GS_WAVES; ++wv) {
@@ -624,6 +678,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *sme
                 const float hold = A[g * lda + Xp + col];
                 st_agent(reinterpret_cast<int *>(hnew + (size_t)(r0 + g) * Hp + col), __float_as_int((1.f - z) * n + z * hold));
             }
+        }
         }
         if (nt == 0 && lane < nr) { const int v = rid[lane]; last_update[v] = msg_ts[v]; }      // memory_updater.py:40
         // ---- arrive: the tile's last workgroup commits (sc1 stores drained, no fence: see k_gru_persist) ----
@@ -683,16 +738,17 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *sme
     }
 }
 
+template <int CELL>
 __global__ __launch_bounds__(64 * GS_WAVES) void k_gru_split(GruSplitArgs GS)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gru_split_body(GS, smem, blockIdx.x, blockIdx.y, nullptr);
+    gru_split_body<CELL>(GS, smem, blockIdx.x, blockIdx.y, nullptr);
 }
 
 // k_out_gru for SMALL batches: the latency-organised output layers (k_embed_out2: one wave per (tiles, path, N-tile), four of
 // them to a workgroup here) beside k_gru_split.  Workgroup order as in k_out_gru: the source-path waves first (n_src_wgs
 // workgroups), the GRU's (tile, N-tile) workgroups, the neighbour paths.
-template <int NT, int HG>
+template <int CELL, int NT, int HG>
 __global__ __launch_bounds__(64 * GS_WAVES) void k_out_gru2(EmbedOutArgs E, int gx, int n_src_wgs, int gru_tiles, GruSplitArgs GS, SrcGate gate)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -700,7 +756,7 @@ __global__ __launch_bounds__(64 * GS_WAVES) void k_out_gru2(EmbedOutArgs E, int 
     const int gru_wgs = gru_tiles * NT;
     if (bid >= n_src_wgs && bid < n_src_wgs + gru_wgs) {
         const int g = bid - n_src_wgs;
-        gru_split_body(GS, smem, g % gru_tiles, g / gru_tiles, &gate);
+        gru_split_body<CELL>(GS, smem, g % gru_tiles, g / gru_tiles, &gate);
         if (threadIdx.x == 0) gate_leave(gate);              // (every GRU workgroup is a participant, whether it waited or not)
         return;
     }
@@ -905,30 +961,41 @@ extern "C" int zt_gru_update(float *memory_dev, float *last_update_dev, const fl
                              n_ids, n_ids_dev, wt, workspace_dev, weights_ready, nullptr, nullptr, stream, false, false);
 }
 
+extern "C" int zt_rnn_update(float *memory_dev, float *last_update_dev, const float *messages_dev,
+                             const float *msg_ts_dev, uint8_t *flags_dev, int64_t num_nodes, int32_t D,
+                             int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids, const int32_t *n_ids_dev,
+                             const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready, void *stream)
+{
+    return zt::gru_update_ex(memory_dev, last_update_dev, messages_dev, msg_ts_dev, flags_dev, num_nodes, D, msg_dim, ids_dev,
+                             n_ids, n_ids_dev, wt, workspace_dev, weights_ready, nullptr, nullptr, stream, false, false, nullptr,
+                             ZT_CELL_RNN);
+}
+
 // zt_gru_update with the refresh of the projected table folded in (pipeline.hip): wm_p = W_m padded to [Dp][Dp]
 // (zt::embed_wm_ptr), proj_table = [num_nodes][Dp]; both NULL: plain zt_gru_update
 int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *messages_dev, const float *msg_ts_dev,
                       uint8_t *flags_dev, int64_t num_nodes, int32_t D, int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
                       const int32_t *n_ids_dev, const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready,
                       const float *wm_p, float *proj_table, void *stream, bool counter_zeroed, bool select_done,
-                      zt::embed_out_deferred *fuse)
+                      zt::embed_out_deferred *fuse, int cell)
 {
     // (output layers held back by embed_ex: launched here whatever happens -- beside the GRU kernel where the shapes allow)
     struct PendingOut {
         zt::embed_out_deferred *d; void *s;
         ~PendingOut() { if (d && d->valid) { (void)zt::embed_out_launch(*d, s); d->valid = false; } }
     } pending{fuse, stream};
+    const char *name = cell == CELL_RNN ? "zt_rnn_update" : "zt_gru_update";
     if (!memory_dev || !last_update_dev || !messages_dev || !msg_ts_dev || !flags_dev || !wt || !workspace_dev ||
-        D <= 0 || msg_dim <= 0 || n_ids < 0) {
-        set_error("zt_gru_update: bad argument");
+        D <= 0 || msg_dim <= 0 || n_ids < 0 || (cell != CELL_GRU && cell != CELL_RNN)) {
+        set_error("%s: bad argument", name);
         return ZT_ERR_ARG;
     }
-    if (D > 128) { set_error("zt_gru_update: D=%d > 128 unsupported", D); return ZT_ERR_UNSUPPORTED; }
+    if (D > 128) { set_error("%s: D=%d > 128 unsupported", name, D); return ZT_ERR_UNSUPPORTED; }
     const int64_t max_rows = ids_dev ? n_ids : num_nodes;
     if (max_rows == 0) return ZT_OK;
     GruPlan p;
     gru_plan(max_rows, D, msg_dim, p);
-    if (p.lds > 150 * 1024) { set_error("zt_gru_update: message width %d too large", msg_dim); return ZT_ERR_UNSUPPORTED; }
+    if (p.lds > 150 * 1024) { set_error("%s: message width %d too large", name, msg_dim); return ZT_ERR_UNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
     int *cnt = reinterpret_cast<int *>(ws + p.off_cnt);
@@ -939,85 +1006,96 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
     ZT_PROF_BEGIN(s, P_GRU);
     if (!select_done)
         k_select_flagged<<<(unsigned)((max_rows + 255) / 256), 256, 0, s>>>(ids_dev, n_ids, n_ids_dev, num_nodes, flags_dev, rows, cnt);
-    if (!weights_ready) {                       // gate-packed, padded copies: once per weight change
-        k_pack_gates<<<(3 * p.Hp * p.Xp + 255) / 256, 256, 0, s>>>(wt->w_ih, D, msg_dim, wih, p.Hp, p.Xp);
-        k_pack_gates<<<(3 * p.Hp * p.Hp + 255) / 256, 256, 0, s>>>(wt->w_hh, D, D, whh, p.Hp, p.Hp);
+    if (!weights_ready) {                       // gate-packed, padded copies: once per weight change (the RNN's one gate fills
+                                                // the first third of each region)
+        if (cell == CELL_RNN) {
+            k_pack_gates<1><<<(p.Hp * p.Xp + 255) / 256, 256, 0, s>>>(wt->w_ih, D, msg_dim, wih, p.Hp, p.Xp);
+            k_pack_gates<1><<<(p.Hp * p.Hp + 255) / 256, 256, 0, s>>>(wt->w_hh, D, D, whh, p.Hp, p.Hp);
+        } else {
+            k_pack_gates<3><<<(3 * p.Hp * p.Xp + 255) / 256, 256, 0, s>>>(wt->w_ih, D, msg_dim, wih, p.Hp, p.Xp);
+            k_pack_gates<3><<<(3 * p.Hp * p.Hp + 255) / 256, 256, 0, s>>>(wt->w_hh, D, D, whh, p.Hp, p.Hp);
+        }
         ZT_HIP(hipMemsetAsync(ws + p.off_tiles, 0, (size_t)GP_TILE_COUNTERS * 4, s));
         ZT_HIP(hipMemsetAsync(cnt + GRU_SRC_WORD, 0, 2 * sizeof(int), s));   // the gate's two words (a fresh workspace; afterwards every launch leaves them at zero)
     }
-    // Two organisations of the same update (zt_set_kernel_choice(ZT_CHOICE_GRU, ..) pins one; tests hold them against each
-    // other and torch's GRUCell):
+    // Two organisations of the same update (zt_set_kernel_choice(ZT_CHOICE_GRU, ..) pins one, for either cell; tests hold them
+    // against each other and torch's GRUCell / RNNCell):
     //   k_gru_split   <= 512 rows: a workgroup per (16 rows, N-tile) -- the whole chip works on what k_gru gives a tenth of it;
     //   k_gru         beyond: 16 rows per workgroup, the gate weights streamed from L2 per tile.
     const int choice = zt::kernel_choice(ZT_CHOICE_GRU);
     const bool fits = max_rows <= GS_MAX_ROWS && (p.Xp + p.Hp) / 16 <= GS_WAVES * GS_MAXCH && 16 * (msg_dim + D) <= GS_STAGE * 256 &&
                       16 * p.Hp <= 7 * 256;
     const bool split = fits && (choice == ZT_GRU_SPLIT || (choice == 0 && max_rows <= 512));
-    if (split) {
-        const size_t lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
-        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split), lds2));
-        GruSplitArgs GS;
-        GS.g.memory = memory_dev; GS.g.last_update = last_update_dev; GS.g.messages = messages_dev; GS.g.msg_ts = msg_ts_dev; GS.g.rows = rows;
-        GS.g.n_rows = cnt; GS.g.D = D; GS.g.msg_dim = msg_dim; GS.g.Xp = p.Xp; GS.g.Hp = p.Hp; GS.g.lda = p.lda; GS.g.Wih_p = wih; GS.g.Whh_p = whh;
-        GS.g.b_ih = wt->b_ih; GS.g.b_hh = wt->b_hh; GS.g.Wm_p = wm_p; GS.g.P = proj_table; GS.g.cap = (int)max_rows;
-        GS.tile_cnt = reinterpret_cast<int *>(ws + p.off_tiles); GS.hnew = reinterpret_cast<float *>(ws + p.off_hnew);
-        const int gru_tiles = (int)((max_rows + 15) / 16), NTg = p.Hp / 16;
-        const bool can_fuse2 = fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::latency && fuse->args.memory == memory_dev &&
-                               (fuse->args.D + 15) / 16 == NTg && (NTg == 7 || NTg == 8) && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10);
-        if (can_fuse2) {
-            const zt::embed_out_deferred &d = *fuse;
-            const int per_path = d.gx * NTg, n_src_wgs = (per_path + 3) / 4, n_nb_wgs = (per_path * d.args.M + 3) / 4;
-            size_t lds_f = (size_t)4 * 16 * (NTg * 16 + 4) * 4;
-            if (lds_f < lds2) lds_f = lds2;
-            SrcGate gate;
-            gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)per_path; gate.participants = (unsigned)(per_path + gru_tiles * NTg);
-            gate.status = d.args.status; gate.latch = d.latch;
-            const unsigned grid = (unsigned)(n_src_wgs + gru_tiles * NTg + n_nb_wgs);
-            const int rc = dispatch<7, 8>(NTg, [&](auto NTV) {
-                return dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
-                    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru2<NTV, HGV>), lds_f));
-                    k_out_gru2<NTV, HGV><<<grid, 64 * GS_WAVES, lds_f, s>>>(d.args, d.gx, n_src_wgs, gru_tiles, GS, gate);
+    const int rc_launch = dispatch<CELL_GRU, CELL_RNN>(cell, [&](auto CV) -> int {
+        constexpr int CELL = decltype(CV)::value;
+        if (split) {
+            const size_t lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split<CELL>), lds2));
+            GruSplitArgs GS;
+            GS.g.memory = memory_dev; GS.g.last_update = last_update_dev; GS.g.messages = messages_dev; GS.g.msg_ts = msg_ts_dev; GS.g.rows = rows;
+            GS.g.n_rows = cnt; GS.g.D = D; GS.g.msg_dim = msg_dim; GS.g.Xp = p.Xp; GS.g.Hp = p.Hp; GS.g.lda = p.lda; GS.g.Wih_p = wih; GS.g.Whh_p = whh;
+            GS.g.b_ih = wt->b_ih; GS.g.b_hh = wt->b_hh; GS.g.Wm_p = wm_p; GS.g.P = proj_table; GS.g.cap = (int)max_rows;
+            GS.tile_cnt = reinterpret_cast<int *>(ws + p.off_tiles); GS.hnew = reinterpret_cast<float *>(ws + p.off_hnew);
+            const int gru_tiles = (int)((max_rows + 15) / 16), NTg = p.Hp / 16;
+            const bool can_fuse2 = fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::latency && fuse->args.memory == memory_dev &&
+                                   (fuse->args.D + 15) / 16 == NTg && (NTg == 7 || NTg == 8) && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10);
+            if (can_fuse2) {
+                const zt::embed_out_deferred &d = *fuse;
+                const int per_path = d.gx * NTg, n_src_wgs = (per_path + 3) / 4, n_nb_wgs = (per_path * d.args.M + 3) / 4;
+                size_t lds_f = (size_t)4 * 16 * (NTg * 16 + 4) * 4;
+                if (lds_f < lds2) lds_f = lds2;
+                SrcGate gate;
+                gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)per_path; gate.participants = (unsigned)(per_path + gru_tiles * NTg);
+                gate.status = d.args.status; gate.latch = d.latch;
+                const unsigned grid = (unsigned)(n_src_wgs + gru_tiles * NTg + n_nb_wgs);
+                const int rc = dispatch<7, 8>(NTg, [&](auto NTV) {
+                    return dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
+                        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru2<CELL, NTV, HGV>), lds_f));
+                        k_out_gru2<CELL, NTV, HGV><<<grid, 64 * GS_WAVES, lds_f, s>>>(d.args, d.gx, n_src_wgs, gru_tiles, GS, gate);
+                        return ZT_OK;
+                    });
+                });
+                if (rc != ZT_OK) return rc;
+                fuse->valid = false;
+            } else {
+                // (held-back output layers first: their source path reads the rows this kernel rewrites)
+                if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
+                k_gru_split<CELL><<<dim3((unsigned)gru_tiles, (unsigned)NTg), 64 * GS_WAVES, lds2, s>>>(GS);
+            }
+        } else {
+            const size_t lds = (size_t)16 * p.lda * 4 + 32 * 4;              // A tile + node ids + the gate's verdict (k_out_gru)
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<CELL, 1>), lds));
+            GruArgs G;
+            G.memory = memory_dev; G.last_update = last_update_dev; G.messages = messages_dev; G.msg_ts = msg_ts_dev; G.rows = rows; G.n_rows = cnt;
+            G.D = D; G.msg_dim = msg_dim; G.Xp = p.Xp; G.Hp = p.Hp; G.lda = p.lda; G.Wih_p = wih; G.Whh_p = whh; G.b_ih = wt->b_ih; G.b_hh = wt->b_hh;
+            G.Wm_p = wm_p; G.P = proj_table; G.cap = (int)max_rows;
+            const unsigned gru_wgs = (unsigned)((max_rows + 15) / 16);
+            if (fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::tiled && fuse->args.memory == memory_dev &&
+                (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10)) {
+                const zt::embed_out_deferred &d = *fuse;
+                const int out_tiles = (int)((d.args.N + OUT_ROWS - 1) / OUT_ROWS), n_out = out_tiles * (d.args.M + 1);
+                const int Dp = (d.args.D + 15) / 16 * 16;
+                size_t lds_f = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
+                if (lds_f < lds) lds_f = lds;
+                SrcGate gate;
+                gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)out_tiles; gate.participants = (unsigned)out_tiles + gru_wgs;
+                gate.status = d.args.status; gate.latch = d.latch;
+                const unsigned grid = (unsigned)n_out + gru_wgs;
+                const int rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
+                    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru<CELL, HGV>), lds_f));
+                    k_out_gru<CELL, HGV><<<grid, 64 * GRU_WAVES, lds_f, s>>>(d.args, out_tiles, (int)gru_wgs, G, gate);
                     return ZT_OK;
                 });
-            });
-            if (rc != ZT_OK) return rc;
-            fuse->valid = false;
-        } else {
-            // (held-back output layers first: their source path reads the rows this kernel rewrites)
-            if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
-            k_gru_split<<<dim3((unsigned)gru_tiles, (unsigned)NTg), 64 * GS_WAVES, lds2, s>>>(GS);
+                if (rc != ZT_OK) return rc;
+                fuse->valid = false;                       // (launched)
+            } else {
+                if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
+                k_gru<CELL, 1><<<gru_wgs, 64 * GRU_WAVES, lds, s>>>(G);
+            }
         }
-    } else {
-        const size_t lds = (size_t)16 * p.lda * 4 + 32 * 4;              // A tile + node ids + the gate's verdict (k_out_gru)
-        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<1>), lds));
-        GruArgs G;
-        G.memory = memory_dev; G.last_update = last_update_dev; G.messages = messages_dev; G.msg_ts = msg_ts_dev; G.rows = rows; G.n_rows = cnt;
-        G.D = D; G.msg_dim = msg_dim; G.Xp = p.Xp; G.Hp = p.Hp; G.lda = p.lda; G.Wih_p = wih; G.Whh_p = whh; G.b_ih = wt->b_ih; G.b_hh = wt->b_hh;
-        G.Wm_p = wm_p; G.P = proj_table; G.cap = (int)max_rows;
-        const unsigned gru_wgs = (unsigned)((max_rows + 15) / 16);
-        if (fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::tiled && fuse->args.memory == memory_dev &&
-            (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10)) {
-            const zt::embed_out_deferred &d = *fuse;
-            const int out_tiles = (int)((d.args.N + OUT_ROWS - 1) / OUT_ROWS), n_out = out_tiles * (d.args.M + 1);
-            const int Dp = (d.args.D + 15) / 16 * 16;
-            size_t lds_f = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
-            if (lds_f < lds) lds_f = lds;
-            SrcGate gate;
-            gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)out_tiles; gate.participants = (unsigned)out_tiles + gru_wgs;
-            gate.status = d.args.status; gate.latch = d.latch;
-            const unsigned grid = (unsigned)n_out + gru_wgs;
-            const int rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
-                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru<HGV>), lds_f));
-                k_out_gru<HGV><<<grid, 64 * GRU_WAVES, lds_f, s>>>(d.args, out_tiles, (int)gru_wgs, G, gate);
-                return ZT_OK;
-            });
-            if (rc != ZT_OK) return rc;
-            fuse->valid = false;                       // (launched)
-        } else {
-            if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
-            k_gru<1><<<gru_wgs, 64 * GRU_WAVES, lds, s>>>(G);
-        }
-    }
+        return ZT_OK;
+    });
+    if (rc_launch != ZT_OK) return rc_launch;
     ZT_PROF_END(s, P_GRU);
     ZT_LAUNCH_CHECK();
     return ZT_OK;

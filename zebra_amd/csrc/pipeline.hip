@@ -77,6 +77,7 @@ struct zt_pipeline {
     int32_t *sh_on, *sh_oe;
     float *sh_od, *sh_ow;
     bool embed_ready, gru_ready;
+    int32_t cell;              // zt_pipeline_set_cell: ZT_CELL_GRU (0, as created) or ZT_CELL_RNN
     hipEvent_t entry;          // main stream at the moment a group is staged: the batches' tensors are written by then
     bool entry_recorded;       // ... recorded in the step call under way (only the calls that stage a group need it)
     float *avg_topk;           // zt_pipeline_set_stats: mean row sum of model 0's weights over [src | dst] (or NULL)
@@ -437,6 +438,14 @@ extern "C" int zt_pipeline_set_group(zt_pipeline *p, int32_t group)
     return ZT_OK;
 }
 
+extern "C" int zt_pipeline_set_cell(zt_pipeline *p, int32_t cell)
+{
+    if (!p || (cell != ZT_CELL_GRU && cell != ZT_CELL_RNN)) { set_error("zt_pipeline_set_cell: a pipeline and ZT_CELL_GRU or ZT_CELL_RNN"); return ZT_ERR_ARG; }
+    p->cell = cell;
+    p->gru_ready = false;                            // the next step packs the weights for this cell
+    return ZT_OK;
+}
+
 extern "C" int zt_pipeline_update(zt_pipeline *p, const zt_pipeline_desc *desc, int32_t weights_changed)
 {
     if (!p) return ZT_ERR_ARG;
@@ -620,7 +629,7 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
     if (!msgs_waited) ZT_HIP(hipStreamWaitEvent(p->main_s, p->msgs_done, 0));
     rc = zt::gru_update_ex(d.memory, d.last_update, d.messages, d.msg_ts, d.flags, d.num_nodes, d.D, msg_dim, nodes_cur, 2 * B,
                            nullptr, &d.gw, d.gru_ws, p->gru_ready ? 1 : 0, wm_p, wm_p ? d.proj_table : nullptr, p->main_s, true, true,
-                           n_rows > 0 ? &p->out_gru : nullptr);
+                           n_rows > 0 ? &p->out_gru : nullptr, p->cell);
     if (rc != ZT_OK) return rc;
     p->gru_ready = true;
     if (n_rows > 0 && p->aff_on && whole) {      // compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written

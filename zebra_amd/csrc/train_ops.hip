@@ -1,5 +1,5 @@
 // Training-side dense operators on exact-f32 MFMA: what the reference's autograd does with
-// nn.GRUCell and nn.Linear on the COMPACT rows of a training step --
+// nn.GRUCell (or nn.RNNCell, RNNMemoryUpdater :100-103) and nn.Linear on the COMPACT rows of a training step --
 //   * the lazily updated memory of the selected neighbours, get_updated_memory (reference
 //     modules/memory_updater.py:61-90, nn.GRUCell :95-98): forward over the U flagged rows with the gate activations
 //     kept for the backward, backward to dW_ih, dW_hh, db_ih, db_hh (the memory and the stored messages are buffers of the
@@ -220,6 +220,28 @@ __global__ void k_gru_gates_bwd(const float *__restrict__ dh, const float *__res
     b[c] = dr_pre; b[D + c] = dz_pre; b[2 * D + c] = dn_pre * r;
 }
 
+// torch.nn.RNNCell (tanh, biases): h' = tanh((gi + b_ih) + (gh + b_hh)), gi = W_ih x, gh = W_hh h ([U][D] each);
+// saved[u] = h' for the backward
+__global__ void k_rnn_fwd(const float *__restrict__ gi, const float *__restrict__ gh, const float *__restrict__ b_ih,
+                          const float *__restrict__ b_hh, long long U, int D, float *__restrict__ h_out, float *__restrict__ saved)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U * D) return;
+    const int c = (int)(i % D);
+    const float h = tanhf((gi[i] + b_ih[c]) + (gh[i] + b_hh[c]));
+    h_out[i] = h;
+    saved[i] = h;
+}
+
+// d_pre = d_h' (1 - h'^2): the gradient of both pre-activations (see k_rnn_fwd)
+__global__ void k_rnn_bwd(const float *__restrict__ dh, const float *__restrict__ saved, long long U, int D, float *__restrict__ dpre)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U * D) return;
+    const float h = saved[i];
+    dpre[i] = dh[i] * (1.f - h * h);
+}
+
 struct GruTrainPlan {
     size_t off_x, off_h, off_gi, off_gh, total;
 };
@@ -232,7 +254,7 @@ void gru_train_plan(long long U, int D, int msg, GruTrainPlan &p)
     p.off_x = take(u * msg * 4);
     p.off_h = take(u * D * 4);
     p.off_gi = take(u * 3 * D * 4);
-    p.off_gh = take(u * 3 * D * 4);
+    p.off_gh = take(u * 3 * D * 4);           // (the RNN pair uses the first [U][D] of gi and gh)
     p.total = o;
 }
 
@@ -350,6 +372,69 @@ extern "C" int zt_gru_train_backward(const float *d_h_dev, const float *messages
     if (rc != ZT_OK) return rc;
     k_colsum<<<(unsigned)((3 * D + 63) / 64), 64 * CS_WAVES, 0, s>>>(dgi, U, 3 * D, 3 * D, d_b_ih_dev, 0);
     k_colsum<<<(unsigned)((3 * D + 63) / 64), 64 * CS_WAVES, 0, s>>>(dgh, U, 3 * D, 3 * D, d_b_hh_dev, 0);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+// the RNN pair: the GRU pair's gathers and GEMMs with one gate ([U][D] products), the element-wise part k_rnn_fwd / k_rnn_bwd
+extern "C" int zt_rnn_train_forward(const float *messages_dev, const float *memory_dev, const int32_t *ids_dev, int64_t U,
+                                    int32_t D, int32_t msg_dim, const zt_gru_weights *wt, float *h_out_dev, float *saved_dev,
+                                    void *workspace_dev, void *stream)
+{
+    if (!messages_dev || !memory_dev || !wt || U < 0 || D <= 0 || msg_dim <= 0 || (U > 0 && (!ids_dev || !h_out_dev || !saved_dev || !workspace_dev))) {
+        set_error("zt_rnn_train_forward: bad argument");
+        return ZT_ERR_ARG;
+    }
+    if (U == 0) return ZT_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GruTrainPlan p;
+    gru_train_plan(U, D, msg_dim, p);
+    char *ws = reinterpret_cast<char *>(workspace_dev);
+    float *X = reinterpret_cast<float *>(ws + p.off_x), *H = reinterpret_cast<float *>(ws + p.off_h);
+    float *gi = reinterpret_cast<float *>(ws + p.off_gi), *gh = reinterpret_cast<float *>(ws + p.off_gh);
+    k_gather_rows_f32<<<(unsigned)((U * msg_dim + 255) / 256), 256, 0, s>>>(messages_dev, ids_dev, U, msg_dim, X);
+    k_gather_rows_f32<<<(unsigned)((U * D + 255) / 256), 256, 0, s>>>(memory_dev, ids_dev, U, D, H);
+    int rc = gemm(X, wt->w_ih, gi, U, D, msg_dim, msg_dim, msg_dim, D, false, true, false, s);      // gi = X W_ih^T
+    if (rc != ZT_OK) return rc;
+    rc = gemm(H, wt->w_hh, gh, U, D, D, D, D, D, false, true, false, s);                            // gh = H W_hh^T
+    if (rc != ZT_OK) return rc;
+    k_rnn_fwd<<<(unsigned)((U * D + 255) / 256), 256, 0, s>>>(gi, gh, wt->b_ih, wt->b_hh, U, D, h_out_dev, saved_dev);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_rnn_train_backward(const float *d_h_dev, const float *messages_dev, const float *memory_dev,
+                                     const int32_t *ids_dev, int64_t U, int32_t D, int32_t msg_dim, const float *saved_dev,
+                                     float *d_w_ih_dev, float *d_w_hh_dev, float *d_b_ih_dev, float *d_b_hh_dev,
+                                     void *workspace_dev, void *stream)
+{
+    if (!messages_dev || !memory_dev || U < 0 || D <= 0 || msg_dim <= 0 || !d_w_ih_dev || !d_w_hh_dev || !d_b_ih_dev || !d_b_hh_dev ||
+        (U > 0 && (!d_h_dev || !ids_dev || !saved_dev || !workspace_dev))) {
+        set_error("zt_rnn_train_backward: bad argument");
+        return ZT_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (U == 0) {
+        ZT_HIP(hipMemsetAsync(d_w_ih_dev, 0, (size_t)D * msg_dim * 4, s));
+        ZT_HIP(hipMemsetAsync(d_w_hh_dev, 0, (size_t)D * D * 4, s));
+        ZT_HIP(hipMemsetAsync(d_b_ih_dev, 0, (size_t)D * 4, s));
+        ZT_HIP(hipMemsetAsync(d_b_hh_dev, 0, (size_t)D * 4, s));
+        return ZT_OK;
+    }
+    GruTrainPlan p;
+    gru_train_plan(U, D, msg_dim, p);
+    char *ws = reinterpret_cast<char *>(workspace_dev);
+    float *X = reinterpret_cast<float *>(ws + p.off_x), *H = reinterpret_cast<float *>(ws + p.off_h);
+    float *dpre = reinterpret_cast<float *>(ws + p.off_gi);
+    // (X and H: the rows the forward gathered, see zt_gru_train_backward)
+    (void)messages_dev; (void)memory_dev; (void)ids_dev;
+    k_rnn_bwd<<<(unsigned)((U * D + 255) / 256), 256, 0, s>>>(d_h_dev, saved_dev, U, D, dpre);
+    int rc = gemm(dpre, X, d_w_ih_dev, D, msg_dim, U, D, msg_dim, msg_dim, true, false, false, s);   // dW_ih = d_pre^T X
+    if (rc != ZT_OK) return rc;
+    rc = gemm(dpre, H, d_w_hh_dev, D, D, U, D, D, D, true, false, false, s);                         // dW_hh = d_pre^T H
+    if (rc != ZT_OK) return rc;
+    k_colsum<<<(unsigned)((D + 63) / 64), 64 * CS_WAVES, 0, s>>>(dpre, U, D, D, d_b_ih_dev, 0);      // db_ih = db_hh = colsum(d_pre)
+    k_colsum<<<(unsigned)((D + 63) / 64), 64 * CS_WAVES, 0, s>>>(dpre, U, D, D, d_b_hh_dev, 0);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

@@ -7,6 +7,7 @@ driver written against it (and its ``state_dict``) keeps working:
   MergeLayer                utils/util.py:14-26
   Memory                    modules/memory.py:7-60
   GRUMemoryUpdater          modules/memory_updater.py:19-98
+  RNNMemoryUpdater          modules/memory_updater.py:19-90,100-103
   GraphDiffusionEmbedding   modules/embedding_module.py:76-336
   TemporalAttentionLayer    model/temporal_attention.py:7-68 (dead code in the reference)
 
@@ -144,15 +145,20 @@ class Memory(nn.Module):
         self.flags[self._ids(positives)] = 0
 
 
-class GRUMemoryUpdater(nn.Module):
-    """SequenceMemoryUpdater + nn.GRUCell (modules/memory_updater.py:19-98)."""
+class SequenceMemoryUpdater(nn.Module):
+    """SequenceMemoryUpdater (modules/memory_updater.py:19-90) over the HIP memory update.  A subclass names its cell:
+    the torch module (``cell_module``), the C-ABI entry point of the update (``update_symbol``) and the cell's code for
+    zt_pipeline_set_cell (``cell``).  The workspace (zt_gru_workspace_bytes) is the same for every cell."""
+    cell_module = None
+    update_symbol = None
+    cell = None
 
     def __init__(self, message_dimension, memory_dimension, device):
         super().__init__()
         self.layer_norm = nn.LayerNorm(memory_dimension)       # dead parameter in the reference; kept for state_dict
         self.message_dimension = message_dimension
         self.device = torch.device(device)
-        self.memory_updater = nn.GRUCell(input_size=message_dimension, hidden_size=memory_dimension)
+        self.memory_updater = self.cell_module(input_size=message_dimension, hidden_size=memory_dimension)
         self.t_index = self.t_real_update = self.t_others = 0
         self._ws = None
 
@@ -169,7 +175,7 @@ class GRUMemoryUpdater(nn.Module):
         return self._ws
 
     def update_device(self, memory, ids_d=None, n_ids=0, n_ids_d=None):
-        """GRU-update the flagged subset of ``ids_d`` (None = all nodes) in place
+        """Apply the cell to the flagged subset of ``ids_d`` (None = all nodes) in place
         and clear their flags; everything stays on the device."""
         D = memory.memory_dimension
         max_rows = memory.n_nodes if ids_d is None else int(n_ids)
@@ -178,13 +184,13 @@ class GRUMemoryUpdater(nn.Module):
         ws = self._workspace(max_rows, D)
         g = self.memory_updater
         # (the packed weights sit before the row list in the workspace: they survive a change of max_rows)
-        key = (ws.data_ptr(),) + tuple((t.data_ptr(), t._version) for t in (g.weight_ih, g.weight_hh))
+        key = (ws.data_ptr(), self.cell) + tuple((t.data_ptr(), t._version) for t in (g.weight_ih, g.weight_hh))
         ready = key == getattr(self, "_ws_key", None)
-        check(lib().zt_gru_update(ptr(memory.memory), ptr(memory.last_update), ptr(memory.messages),
-                                  ptr(memory.timestamps), ptr(memory._flag_buf), C.c_int64(memory.n_nodes),
-                                  C.c_int32(D), C.c_int32(self.message_dimension), ptr(ids_d), C.c_int64(n_ids),
-                                  ptr(n_ids_d), C.byref(self._weights()), ptr(ws), C.c_int32(1 if ready else 0),
-                                  stream_ptr()), "zt_gru_update")
+        check(getattr(lib(), self.update_symbol)(ptr(memory.memory), ptr(memory.last_update), ptr(memory.messages),
+                                                 ptr(memory.timestamps), ptr(memory._flag_buf), C.c_int64(memory.n_nodes),
+                                                 C.c_int32(D), C.c_int32(self.message_dimension), ptr(ids_d), C.c_int64(n_ids),
+                                                 ptr(n_ids_d), C.byref(self._weights()), ptr(ws), C.c_int32(1 if ready else 0),
+                                                 stream_ptr()), self.update_symbol)
         self._ws_key = key
         hook = getattr(memory, "_rows_changed", None)
         if hook is not None:                       # e.g. the embedding module's projected table follows the rows
@@ -208,7 +214,7 @@ class GRUMemoryUpdater(nn.Module):
         self.update_device(memory, None)
 
     def get_updated_memory(self, memory, index=None):           # modules/memory_updater.py:61-90
-        """Train-mode lazily-updated copy (autograd flows through the GRU).
+        """Train-mode lazily-updated copy (autograd flows through the cell).
         Device torch ops; the reference clones the whole memory here too."""
         flags = memory.flags
         if index is None:
@@ -225,10 +231,26 @@ class GRUMemoryUpdater(nn.Module):
         return updated_memory, updated_last_update
 
 
+class GRUMemoryUpdater(SequenceMemoryUpdater):
+    """SequenceMemoryUpdater + nn.GRUCell (modules/memory_updater.py:19-98)."""
+    cell_module = nn.GRUCell
+    update_symbol = "zt_gru_update"
+    cell = _capi.CELL_GRU
+
+
+class RNNMemoryUpdater(SequenceMemoryUpdater):
+    """SequenceMemoryUpdater + nn.RNNCell (modules/memory_updater.py:100-103; tanh, biases): zt_rnn_update."""
+    cell_module = nn.RNNCell
+    update_symbol = "zt_rnn_update"
+    cell = _capi.CELL_RNN
+
+
 def get_memory_updater(module_type, message_dimension, memory_dimension, device):
-    if module_type != "gru":
-        raise ValueError("only the GRU memory updater is on the accelerated path (got %r)" % module_type)
-    return GRUMemoryUpdater(message_dimension, memory_dimension, device)
+    if module_type == "gru":
+        return GRUMemoryUpdater(message_dimension, memory_dimension, device)
+    if module_type == "rnn":
+        return RNNMemoryUpdater(message_dimension, memory_dimension, device)
+    raise ValueError("only the GRU and RNN memory updaters are on the accelerated path (got %r)" % module_type)
 
 
 def _gemm(a, b, m, n, k, lda, ldb, ta, tb, out=None, accumulate=False):
@@ -274,6 +296,37 @@ class _HipLinear(torch.autograd.Function):
         return dx, dw, db
 
 
+def _cell_rows_forward(ctx, fwd, saved_cols, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32):
+    U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
+    dev = memory_t.device
+    h = torch.empty((U, D), dtype=torch.float32, device=dev)
+    saved = torch.empty((U, saved_cols * D), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib().zt_gru_train_workspace_bytes(C.c_int64(U), C.c_int32(D), C.c_int32(msg))), dtype=torch.uint8,
+                     device=dev)
+    wt = _capi.GruWeights(ptr(w_ih.detach().contiguous()), ptr(w_hh.detach().contiguous()), ptr(b_ih.detach().contiguous()),
+                          ptr(b_hh.detach().contiguous()))
+    check(getattr(lib(), fwd)(ptr(messages), ptr(memory_t), ptr(ids32), C.c_int64(U), C.c_int32(D), C.c_int32(msg),
+                              C.byref(wt), ptr(h), ptr(saved), ptr(ws), stream_ptr()), fwd)
+    ctx.save_for_backward(saved, ids32)
+    ctx.misc = (messages, memory_t, ws, w_ih.shape, w_hh.shape, b_ih.shape)
+    return h
+
+
+def _cell_rows_backward(ctx, bwd, dh):
+    saved, ids32 = ctx.saved_tensors
+    messages, memory_t, ws, s_ih, s_hh, s_b = ctx.misc
+    U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
+    dev = memory_t.device
+    d_w_ih = torch.empty(s_ih, dtype=torch.float32, device=dev)
+    d_w_hh = torch.empty(s_hh, dtype=torch.float32, device=dev)
+    d_b_ih = torch.empty(s_b, dtype=torch.float32, device=dev)
+    d_b_hh = torch.empty(s_b, dtype=torch.float32, device=dev)
+    check(getattr(lib(), bwd)(ptr(dh.contiguous()), ptr(messages), ptr(memory_t), ptr(ids32), C.c_int64(U),
+                              C.c_int32(D), C.c_int32(msg), ptr(saved), ptr(d_w_ih), ptr(d_w_hh), ptr(d_b_ih),
+                              ptr(d_b_hh), ptr(ws), stream_ptr()), bwd)
+    return d_w_ih, d_w_hh, d_b_ih, d_b_hh, None, None, None
+
+
 class _HipGruRows(torch.autograd.Function):
     """overlay[u] = GRUCell(messages[ids[u]], memory[ids[u]]) -- the lazily updated rows of get_updated_memory
     (modules/memory_updater.py:61-90) -- with the backward to the four GRU parameters on the HIP kernels
@@ -281,34 +334,24 @@ class _HipGruRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32):
-        U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
-        dev = memory_t.device
-        h = torch.empty((U, D), dtype=torch.float32, device=dev)
-        saved = torch.empty((U, 4 * D), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib().zt_gru_train_workspace_bytes(C.c_int64(U), C.c_int32(D), C.c_int32(msg))), dtype=torch.uint8,
-                         device=dev)
-        wt = _capi.GruWeights(ptr(w_ih.detach().contiguous()), ptr(w_hh.detach().contiguous()), ptr(b_ih.detach().contiguous()),
-                              ptr(b_hh.detach().contiguous()))
-        check(lib().zt_gru_train_forward(ptr(messages), ptr(memory_t), ptr(ids32), C.c_int64(U), C.c_int32(D), C.c_int32(msg),
-                                         C.byref(wt), ptr(h), ptr(saved), ptr(ws), stream_ptr()), "zt_gru_train_forward")
-        ctx.save_for_backward(saved, ids32)
-        ctx.misc = (messages, memory_t, ws, w_ih.shape, w_hh.shape)
-        return h
+        return _cell_rows_forward(ctx, "zt_gru_train_forward", 4, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32)
 
     @staticmethod
     def backward(ctx, dh):
-        saved, ids32 = ctx.saved_tensors
-        messages, memory_t, ws, s_ih, s_hh = ctx.misc
-        U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
-        dev = memory_t.device
-        d_w_ih = torch.empty(s_ih, dtype=torch.float32, device=dev)
-        d_w_hh = torch.empty(s_hh, dtype=torch.float32, device=dev)
-        d_b_ih = torch.empty(3 * D, dtype=torch.float32, device=dev)
-        d_b_hh = torch.empty(3 * D, dtype=torch.float32, device=dev)
-        check(lib().zt_gru_train_backward(ptr(dh.contiguous()), ptr(messages), ptr(memory_t), ptr(ids32), C.c_int64(U),
-                                          C.c_int32(D), C.c_int32(msg), ptr(saved), ptr(d_w_ih), ptr(d_w_hh), ptr(d_b_ih),
-                                          ptr(d_b_hh), ptr(ws), stream_ptr()), "zt_gru_train_backward")
-        return d_w_ih, d_w_hh, d_b_ih, d_b_hh, None, None, None
+        return _cell_rows_backward(ctx, "zt_gru_train_backward", dh)
+
+
+class _HipRnnRows(torch.autograd.Function):
+    """The same rows for RNNMemoryUpdater: overlay[u] = RNNCell(messages[ids[u]], memory[ids[u]])
+    (zt_rnn_train_forward / zt_rnn_train_backward; saved holds the [U, D] output)."""
+
+    @staticmethod
+    def forward(ctx, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32):
+        return _cell_rows_forward(ctx, "zt_rnn_train_forward", 1, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32)
+
+    @staticmethod
+    def backward(ctx, dh):
+        return _cell_rows_backward(ctx, "zt_rnn_train_backward", dh)
 
 
 class _OverlayRows(torch.autograd.Function):
@@ -667,8 +710,9 @@ class GraphDiffusionEmbedding(nn.Module):
         U = int(ids.numel())
         hip_dense = getattr(self, "fused_training", True)
         if U and hip_dense:
-            g = memory_updater.memory_updater                                   # nn.GRUCell's parameters, HIP forward + backward
-            overlay = _HipGruRows.apply(g.weight_ih, g.weight_hh, g.bias_ih, g.bias_hh, memory.messages, memory.memory,
+            g = memory_updater.memory_updater                                   # the cell's parameters, HIP forward + backward
+            rows_op = _HipRnnRows if getattr(memory_updater, "cell", _capi.CELL_GRU) == _capi.CELL_RNN else _HipGruRows
+            overlay = rows_op.apply(g.weight_ih, g.weight_hh, g.bias_ih, g.bias_hh, memory.messages, memory.memory,
                                         ids.to(torch.int32).contiguous())      # [U, D]
         elif U:
             overlay = memory_updater.memory_updater(memory.messages[ids], memory.memory[ids])      # [U, D]

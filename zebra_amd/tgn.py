@@ -318,11 +318,16 @@ class TGN(torch.nn.Module):
             if getattr(self, "_pipe_group", 1) > 1:
                 check(lib().zt_pipeline_set_group(h, C.c_int32(self._pipe_group)), "zt_pipeline_set_group")
             self.main_stream = torch.cuda.ExternalStream(lib().zt_pipeline_main_stream(h), device=self.device)
+            self._pipe_cell = _capi.CELL_GRU
         else:
             check(lib().zt_pipeline_update(self._pipe, C.byref(d), C.c_int32(1)), "zt_pipeline_update")
             if getattr(self, "_xchg", None) is not None:      # the exchange follows the tables
                 check(lib().zt_exchange_set_tables(self._xchg, ptr(m.memory), ptr(m.last_update), ptr(m.messages),
                                                    ptr(m.timestamps)), "zt_exchange_set_tables")
+        cell = getattr(mu, "cell", _capi.CELL_GRU)
+        if cell != self._pipe_cell:                     # the memory updater's cell (RNNMemoryUpdater: zt_rnn_update's kernels)
+            check(lib().zt_pipeline_set_cell(self._pipe, C.c_int32(cell)), "zt_pipeline_set_cell")
+            self._pipe_cell = cell
         em._ws_key = None                               # the pipeline remakes the padded weights at its next step
         mu._ws_key = None
         self._pipe_sig = self._pipe_signature()
