@@ -2,7 +2,7 @@
 """bench.py -- temporal edges/sec embedded by the T-PPR + top-k aggregate +
 memory-update path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of the synthetic stream
 (eval-mode protocol of reference model/tgn_model.py:124-174): streaming (or
@@ -23,9 +23,13 @@ batch.  Total work per step is fixed ("strong" scaling).
 `--dry-run` stops after the rendezvous (no GPU needed: the CPU-side test of the
 launch path).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with the
-`roofline` of the dominant kernel and the `cpu_baseline` (oracle timed on the
-host cores, N = 1 only).
+Rank 0 prints ONE JSON line with the headline figure, the per-kernel HIP-event
+times of the timed region and the `roofline` of its dominant kernel.  That is
+all a plain run does: set up, warm up, time K steps, write --dump-outputs,
+print.  `--full` adds what takes runs of its own: the `cpu_baseline` (oracle
+timed on the host cores, N = 1 only) with `parity_in_run` and `row_fill`, the
+`with_scorer` and `steady_state` regions behind the timed one, and the other
+workloads under `workloads` (`--legs`).
 """
 import argparse
 import contextlib
@@ -347,6 +351,10 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
     n_edges = n_steps_total * bs
     if n_edges > wl["n_edges"]:
         raise SystemExit("stream of %d edges is shorter than prefill+warmup+steps" % wl["n_edges"])
+    # without --full only the metric's region runs, but the stream keeps the length --full draws: the destinations' draws
+    # and the negatives depend on it, and the timed batches are the same in both modes
+    if not a.full:
+        scored, steady = False, 0
 
     src, dst, neg, ts, eidx = make_stream(wl, n_edges, perm_seed=None if a.perm_seed < 0 else a.perm_seed)
     n_edge_rows = (wl["n_edges"] if F == 1 else n_edges) + 1      # F=1: the full |E|+1 zero table is cheap
@@ -459,6 +467,11 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
     cpu_nb = 0
     if world == 1 and cpu_edges != 0:
         cpu_nb = max(2, min(steps + warmup, cpu_edges // bs))
+    # the clock spin below follows the snapshot; a plain run (no CPU leg) spins all the same, so that its warm-up starts
+    # from what --full's starts from: without it C5's 20-step region measured 0.8 % slower (five alternating pairs)
+    spin = bool(cpu_nb) and not a.no_clock_spin
+    if not a.full:
+        cpu_nb = 0
     snap, fill = None, None
     if cpu_nb:
         touched = np.unique(np.concatenate([src[:e0], dst[:e0]])) if e0 else np.zeros(0, np.int64)
@@ -470,7 +483,7 @@ def run_workload(a, name, steps, warmup, world, rank, device, headline, cpu_edge
             ln = np.where(seen, snap["tppr"][0]["len"][np.minimum(pos, len(touched) - 1)], 0)
             fill = dict(mean_row_len=float(ln.mean()), frac_empty=float((ln == 0).mean()), frac_full=float((ln == k).mean()))
     spun = False
-    if cpu_nb and not a.no_clock_spin:
+    if spin:
         # the snapshot above left the GPU idle for seconds (host-side export of the warm state): its clocks have dropped,
         # and W = 5 warm-up steps (2 ms) do not bring them back.  Throw-away matrix products for a third of a second, on
         # data that has nothing to do with the stream, before the warm-up steps -- so that the timed region measures the
@@ -965,22 +978,27 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c5", choices=["c1", "c2", "c3", "c4", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the CPU baseline with the in-run parity check, the "
+                         "scorer and steady-state regions, the other workloads (--legs).  The options below marked (--full) "
+                         "shape or trim these; a plain run times the headline region alone")
     ap.add_argument("--legs", default="default",
-                    help="further workloads timed after the headline one and printed under \"workloads\" of the same JSON "
+                    help="(--full) further workloads timed after the headline one and printed under \"workloads\" of the same JSON "
                          "line, each with its own ms_per_step / roofline / cpu_baseline: comma-separated names, 'none', or "
                          "'default' = c2,c3,c2_train,c4 behind the c5 headline (nothing behind another --workload); <name>_train = the TRAINING "
                          "step of that workload (run_train_workload)")
-    ap.add_argument("--leg-steps", type=int, default=100, help="timed steps of every leg (warm-up 10)")
+    ap.add_argument("--leg-steps", type=int, default=100, help="(--full) timed steps of every leg (warm-up 10)")
     ap.add_argument("--steady-steps", type=int, default=200,
-                    help="a further timed region of this many steps behind the headline's (printed as \"steady_state\"; skipped "
+                    help="(--full) a further timed region of this many steps behind the headline's (printed as \"steady_state\"; skipped "
                          "when --steps is at least as long; 0 = none)")
     ap.add_argument("--prefill-steps", type=int, default=-1,
                     help="untimed batches run before warm-up so that T-PPR rows are full (default: per workload)")
-    ap.add_argument("--cpu-edges", type=int, default=-1, help="edges of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-edges", type=int, default=-1, help="(--full) edges of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--no-score", action="store_true", help="skip the second timed region (the step with the link scorer at its tail)")
+    ap.add_argument("--no-score", action="store_true", help="(--full) skip the second timed region (the step with the link scorer at its tail)")
     ap.add_argument("--no-clock-spin", action="store_true",
-                    help="skip the throw-away GPU work between the warm-state snapshot (seconds of host work, GPU idle) and the warm-up steps")
+                    help="skip the throw-away GPU work before the warm-up steps (with --full it follows the warm-state snapshot: seconds of "
+                         "host work, GPU idle); --cpu-edges 0 skips it too")
     ap.add_argument("--profile-every", type=int, default=-1,
                     help="record HIP events around every n-th launch of the main stream's kernels (default 4: two "
                          "event records per kernel and step cost ~3 %% of the step; the T-PPR update, one launch per "
@@ -1027,6 +1045,8 @@ def main():
 
     if a.dump_outputs and a.gpus != 1:
         raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (a rank holds a shard of the rows)")
+    if not a.full and (a.legs not in ("default", "none") or a.cpu_edges > 0):
+        raise SystemExit("bench.py: --legs and --cpu-edges choose what --full measures beside the headline: add --full")
     # ---- --gpus N without a launcher: this process becomes the parent of N ranks and never touches the GPU ----
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -1074,7 +1094,7 @@ def main():
     ce = a.cpu_edges if a.cpu_edges >= 0 else cpu_default[a.workload]
     out = run_workload(a, a.workload, a.steps, a.warmup, world, rank, device, True, ce, steady=a.steady_steps)
     dump = out.pop("_dump", None) if out is not None else None
-    legs = a.legs
+    legs = a.legs if a.full else "none"
     if legs == "default":
         legs = "c2,c3,c2_train,c4" if a.workload == "c5" else "none"
     res = {}
