@@ -133,3 +133,164 @@ def test_train_forward_kernel_choice(hooks, shape, want):
     for table in (False, True):                   # (the training forward has no table)
         a, _, lds = plan(hooks, 600, D, F, T, 2, k, table, training=True)
         assert (a, lds) == (AGG[want[0]], want[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The memory update (zt::memory_kernel_plan, csrc/memory_update.hip; through the test hook zt_test_memory_plan).  Each row is
+# the kernel the shape took before the choice moved into one function, read off the predicates of gru_update_ex and
+# store_messages_ex as they were (Xp, Hp = msg, D rounded up to 16; rows = the ids given to the update):
+#   refused: D <= 0 or msg <= 0 (bad argument), then D > 128, then -- only where rows > 0 -- a message too wide for
+#            k_gru<2>'s two 16-row tiles of [message | memory] in 150 KB of LDS: 2 * 16 * (Xp + Hp + 4) * 4 + 128 > 153 600
+#   fits  = rows <= 8192 and (Xp + Hp) / 16 <= 40 and 16 (msg + D) <= 37 * 256 and 16 Hp <= 7 * 256
+#           (the chunk bound never decides alone: the staging bound fails from 39 chunks on)
+#   split = fits and (ZT_GRU_SPLIT, or no choice and rows <= 512); else the tile
+#   held-back output layers over the table updated: fused with the tile where they are tiled with hg in {1, 5, 10}; fused with
+#           the split where they are latency-organised, hg in {1, 5, 10}, their N-tiles are the GRU's and NTg in {7, 8};
+#           in front of the GRU kernel otherwise (and on the way out of a refused or empty update)
+#   messages: two positions per wave unless ZT_MSG_ONE, D > 128, T > 128 or F > 256
+REFUSAL = {"none": 0, "arg": 1, "d_large": 2, "msg_wide": 3}
+MSGK = {"one": 0, "two": 1}
+GRU = {"none": 0, "tile": 1, "split": 2}
+HELD = {"none": 0, "front": 1, "fused_tile": 2, "fused_split": 3}
+GRU_TILE, GRU_SPLIT = 1, 2                       # ZT_GRU_*
+MSG_ONE, MSG_TWO = 1, 2                          # ZT_MSG_*
+
+
+def memory_plan(hooks, rows, D, msg, F=172, T=100, gru_choice=0, msg_choice=0, held=None):
+    """held: (form, hg, D, M, gx, N, same memory) of output layers held back by embed_ex, or None"""
+    form, hg, hD, hM, gx, hN, same = held if held else ("tiled", 0, 0, 0, 0, 0, False)
+    out = (C.c_int64 * 14)(*([-1] * 14))
+    rc = hooks.zt_test_memory_plan(C.c_int64(rows), C.c_int32(D), C.c_int32(msg), C.c_int32(F), C.c_int32(T),
+                                   C.c_int32(gru_choice), C.c_int32(msg_choice), C.c_int32(int(held is not None)),
+                                   C.c_int32(OUT[form]), C.c_int32(hg), C.c_int32(hD), C.c_int32(hM), C.c_int32(gx),
+                                   C.c_int64(hN), C.c_int32(int(same)), out)
+    assert rc == 0
+    keys = ("refusal", "msg", "gru", "out", "lds", "lds2", "lds_f", "gru_tiles", "NTg", "n_src_wgs", "n_nb_wgs",
+            "out_tiles", "target", "participants")
+    return dict(zip(keys, list(out)))
+
+
+# (rows, D, msg, ZT_CHOICE_GRU) -> (form, dynamic LDS of its launch, 16-row tiles, N-tiles)
+GRU_ROWS = [
+    # BASELINE C2 - C5 (D = 100; messages 2 D + F + T: F = 172 for C2 / C3, 1 for C4 / C5)
+    ((400, 100, 472, 0), ("split", 54656, 25, 7)),
+    ((1200, 100, 472, 0), ("tile", 38272, 75, 7)),
+    ((2000, 100, 301, 0), ("tile", 27008, 125, 7)),
+    ((8192, 100, 301, 0), ("tile", 27008, 512, 7)),
+    # the row switch
+    ((512, 100, 472, 0), ("split", 54656, 32, 7)),
+    ((513, 100, 472, 0), ("tile", 38272, 33, 7)),
+    # the split pinned: up to GS_MAX_ROWS, beyond it the tile
+    ((8192, 100, 301, GRU_SPLIT), ("split", 43392, 512, 7)),
+    ((8193, 100, 301, GRU_SPLIT), ("tile", 27008, 513, 7)),
+    ((1200, 100, 472, GRU_SPLIT), ("split", 54656, 75, 7)),
+    # the tile pinned
+    ((400, 100, 472, GRU_TILE), ("tile", 38272, 25, 7)),
+    # the staging bound 16 (msg + D) <= 37 * 256
+    ((400, 100, 492, 0), ("split", 55680, 25, 7)),
+    ((400, 100, 493, 0), ("tile", 39296, 25, 7)),
+    # the chunk bound: 38 chunks fit, 39 do not (there the staging bound fails)
+    ((400, 1, 577, 0), ("split", 55680, 25, 1)),
+    ((400, 1, 593, 0), ("tile", 40320, 25, 1)),
+    # 16 Hp <= 7 * 256: D = 112 against 113, also pinned (the split that does not fit falls back)
+    ((400, 112, 100, 0), ("split", 31104, 25, 7)),
+    ((400, 113, 100, 0), ("tile", 15744, 25, 8)),
+    ((400, 113, 100, GRU_SPLIT), ("tile", 15744, 25, 8)),
+    # the widest messages taken (D = 100: 1 072; D = 128: 1 056)
+    ((400, 100, 1072, 0), ("tile", 76160, 25, 7)),
+    ((400, 100, 1072, GRU_SPLIT), ("tile", 76160, 25, 7)),
+    ((400, 128, 1056, 0), ("tile", 76160, 25, 8)),
+    ((400, 64, 236, 0), ("split", 36224, 25, 4)),
+]
+
+
+@pytest.mark.parametrize("shape,want", GRU_ROWS, ids=[str(s) for s, _ in GRU_ROWS])
+def test_gru_kernel_choice(hooks, shape, want):
+    rows, D, msg, gc = shape
+    p = memory_plan(hooks, rows, D, msg, gru_choice=gc)
+    assert (p["refusal"], p["out"]) == (REFUSAL["none"], HELD["none"])
+    lds = p["lds2"] if want[0] == "split" else p["lds"]
+    assert (p["gru"], lds, p["gru_tiles"], p["NTg"]) == (GRU[want[0]], want[1], want[2], want[3])
+
+
+# (rows, D, msg) -> refusal; nothing is launched
+REFUSED = [
+    ((400, 100, 1073), "msg_wide"),
+    ((400, 128, 1057), "msg_wide"),
+    ((400, 129, 472), "d_large"),
+    ((0, 129, 472), "d_large"),
+    ((400, 0, 472), "arg"),
+    ((400, 100, 0), "arg"),
+    ((0, 100, 2000), "none"),          # no rows: nothing to do, whatever the message width
+]
+
+
+@pytest.mark.parametrize("shape,want", REFUSED, ids=[str(s) for s, _ in REFUSED])
+def test_gru_refusals(hooks, shape, want):
+    p = memory_plan(hooks, *shape)
+    assert (p["refusal"], p["gru"]) == (REFUSAL[want], GRU["none"])
+
+
+# (D, F, T, ZT_CHOICE_MESSAGES) -> positions per wave
+MESSAGES = [
+    ((100, 172, 100, 0), "two"),
+    ((100, 1, 100, 0), "two"),
+    ((128, 172, 100, 0), "two"),
+    ((129, 172, 100, 0), "one"),
+    ((100, 172, 128, 0), "two"),
+    ((100, 172, 129, 0), "one"),
+    ((100, 256, 100, 0), "two"),
+    ((100, 257, 100, 0), "one"),
+    ((100, 172, 100, MSG_ONE), "one"),
+    ((100, 172, 100, MSG_TWO), "two"),
+    ((129, 172, 100, MSG_TWO), "one"),
+]
+
+
+@pytest.mark.parametrize("shape,want", MESSAGES, ids=[str(s) for s, _ in MESSAGES])
+def test_message_kernel_choice(hooks, shape, want):
+    D, F, T, mc = shape
+    assert memory_plan(hooks, 400, D, 2 * D + F + T, F=F, T=T, msg_choice=mc)["msg"] == MSGK[want]
+
+
+# (rows, D, msg, ZT_CHOICE_GRU, held: (form, hg, D, M, gx, N, same memory)) ->
+#   (output layers, lds_f, n_src_wgs, n_nb_wgs, out_tiles, gate target, gate participants)
+FRONT = ("front", 0, 0, 0, 0, 0, 0)
+FUSE = [
+    # C2: the split beside latency-organised output layers, hg = 1, 5, 10 (gx = 38 tiles per path)
+    ((400, 100, 472, 0, ("latency", 1, 100, 2, 38, 600, True)), ("fused_split", 54656, 67, 133, 0, 266, 441)),
+    ((400, 100, 472, 0, ("latency", 5, 100, 2, 38, 600, True)), ("fused_split", 54656, 67, 133, 0, 266, 441)),
+    ((400, 100, 472, 0, ("latency", 10, 100, 2, 38, 600, True)), ("fused_split", 54656, 67, 133, 0, 266, 441)),
+    ((400, 100, 472, 0, ("latency", 2, 100, 2, 38, 600, True)), FRONT),
+    ((400, 100, 472, 0, ("latency", 1, 100, 2, 38, 600, False)), FRONT),
+    ((400, 100, 472, 0, ("tiled", 1, 100, 2, 38, 600, True)), FRONT),
+    ((400, 100, 472, 0, ("persist", 1, 100, 2, 38, 600, True)), FRONT),
+    ((1200, 100, 472, GRU_SPLIT, ("latency", 5, 100, 2, 38, 1800, True)), ("fused_split", 54656, 67, 133, 0, 266, 791)),
+    # NTg: 7 at D = 112 (one model); output layers of other N-tiles; NTg = 4; NTg = 8 never fits the split
+    ((400, 112, 100, 0, ("latency", 1, 112, 1, 10, 300, True)), ("fused_split", 31104, 18, 18, 0, 70, 245)),
+    ((400, 100, 472, 0, ("latency", 1, 128, 2, 38, 600, True)), FRONT),
+    ((400, 64, 236, 0, ("latency", 1, 64, 2, 38, 600, True)), FRONT),
+    ((400, 128, 100, 0, ("latency", 1, 128, 2, 38, 600, True)), FRONT),
+    # C3 / C4: the tile beside tiled output layers, hg = 1, 5, 10
+    ((1200, 100, 472, 0, ("tiled", 1, 100, 2, 0, 1800, True)), ("fused_tile", 38272, 0, 0, 57, 57, 132)),
+    ((1200, 100, 472, 0, ("tiled", 5, 100, 2, 0, 1800, True)), ("fused_tile", 38272, 0, 0, 57, 57, 132)),
+    ((1200, 100, 472, 0, ("tiled", 10, 100, 2, 0, 1800, True)), ("fused_tile", 38272, 0, 0, 57, 57, 132)),
+    ((1200, 100, 472, 0, ("tiled", 2, 100, 2, 0, 1800, True)), FRONT),
+    ((1200, 100, 472, 0, ("tiled", 1, 100, 2, 0, 1800, False)), FRONT),
+    ((1200, 100, 472, 0, ("latency", 1, 100, 2, 38, 1800, True)), FRONT),
+    ((2000, 100, 301, 0, ("tiled", 10, 128, 2, 0, 3000, True)), ("fused_tile", 33920, 0, 0, 94, 94, 219)),
+    ((400, 100, 472, GRU_TILE, ("tiled", 1, 100, 2, 0, 600, True)), ("fused_tile", 38272, 0, 0, 19, 19, 44)),
+    # C5: the persistent output layers are never fused
+    ((8192, 100, 301, 0, ("persist", 1, 100, 2, 0, 12288, True)), FRONT),
+    # no rows, a refused update: the output layers still run
+    ((0, 100, 472, 0, ("tiled", 1, 100, 2, 0, 600, True)), FRONT),
+    ((400, 100, 1073, 0, ("tiled", 1, 100, 2, 0, 600, True)), FRONT),
+]
+
+
+@pytest.mark.parametrize("shape,want", FUSE, ids=[str(s) for s, _ in FUSE])
+def test_held_back_output_layers(hooks, shape, want):
+    rows, D, msg, gc, held = shape
+    p = memory_plan(hooks, rows, D, msg, gru_choice=gc, held=held)
+    got = (p["out"], p["lds_f"], p["n_src_wgs"], p["n_nb_wgs"], p["out_tiles"], p["target"], p["participants"])
+    assert got == (HELD[want[0]],) + want[1:]

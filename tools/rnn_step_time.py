@@ -6,7 +6,7 @@ rounds on one GPU:
 The model is bench.py's, with its memory updater swapped for an RNNMemoryUpdater of the same widths where the cell is
 rnn.  Prints one JSON line per (round, cell, shape) and a summary line with the medians.  The memory kernel's own time
 comes from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/rnn_step_time.py --shapes c2 ...`
-(k_gru<0, 1> / k_out_gru* against their <1, ...> instantiations).
+(k_gru<0> / k_out_gru* against their <1, ...> instantiations).
 
     python tools/rnn_step_time.py [--shapes c2,c5,c2_train] [--cells gru,rnn] [--rounds 2] [--steps 50] [--warmup 5]
 """

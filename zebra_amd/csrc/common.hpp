@@ -66,6 +66,36 @@ struct KernelPlan {
 // Pure host code (no HIP calls).  training: zt_agg_train_forward's choice (no table; tiled_full or split)
 KernelPlan embed_kernel_plan(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
                              int out_choice);
+// The memory update's kernels for one shape (memory_update.hip: memory_kernel_plan): the message build (k_build_messages, or
+// k_build_messages2: two batch positions per wave); the GRU / RNN update (none: no rows; tile = k_gru, split = k_gru_split);
+// output layers held back by embed_ex (launched in front of the GRU kernel -- or on the way out of a refused or empty update
+// --, fused with k_gru: k_out_gru, or with k_gru_split: k_out_gru2).  Every form gives the same bits; the choice is speed only.
+enum class MsgKernel { one, two };
+enum class GruForm { none, tile, split };
+enum class OutLaunch { none, front, fused_tile, fused_split };
+enum class MemRefusal { none, arg, d_large, msg_wide };      // bad argument / D > 128 / message width too large
+// the held-back output layers (embed_out_deferred) as far as the GRU launch needs them; same_memory: they read the table updated
+struct HeldOut {
+    bool present;
+    OutForm form;
+    int hg, D, M, gx;
+    long long N;
+    bool same_memory;
+};
+struct MemoryPlan {
+    MsgKernel msg;
+    GruForm gru;
+    OutLaunch out;
+    MemRefusal refusal;
+    size_t lds, lds2, lds_f;           // dynamic LDS of k_gru, k_gru_split and the fused kernel
+    int gru_tiles, NTg;                // 16-row tiles, hidden N-tiles
+    int n_src_wgs, n_nb_wgs, out_tiles;     // k_out_gru2's source- and neighbour-path workgroups; k_out_gru's row tiles
+    unsigned grid;                     // workgroups of the launch (k_gru_split: x dimension)
+    unsigned target, participants;     // the fused kernels' SrcGate
+};
+// Pure host code (no HIP calls).  F, T: the message's edge-feature and time widths; the choices: ZT_CHOICE_GRU, ZT_CHOICE_MESSAGES
+MemoryPlan memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, int T, int gru_choice, int msg_choice,
+                              const HeldOut &held);
 // The output layers of an embed call, held back (embed_ex: `defer`) so that gru_update_ex can launch them in ONE kernel with the
 // GRU update (k_out_gru, memory_update.hip): the two are independent apart from the memory rows the source path reads --
 // the GRU half waits for those reads before it writes (a gate in the GRU workspace whose whole state is device memory: a

@@ -103,8 +103,8 @@ namespace {
 // buffers, communicator, mapping and the handle itself (zt_exchange_destroy; every failing path of zt_exchange_create)
 void release_exchange(zt_exchange *x);
 
-// [id | row of every table] of the rows a rank's GRU update rewrote (k_pack_rows of memory_update.hip, with the ids in a
-// compact array beside the payload on the receiving side)
+// [id | row of every table] of the rows a rank's GRU update rewrote: slot r < cap carries ids[r] (r < *n_valid) or -1, then
+// the id's row of every table (zeros for -1).  One wavefront per slot.
 __global__ __launch_bounds__(256) void k_xchg_pack(zt_row_tables T, int row_floats, const int *__restrict__ ids,
                                                    const int *__restrict__ n_valid, long long cap, float *__restrict__ out)
 {
@@ -123,7 +123,8 @@ __global__ __launch_bounds__(256) void k_xchg_pack(zt_row_tables T, int row_floa
     }
 }
 
-// every received row with id >= 0 overwrites the local tables; ids_out[r] = id (or -1)
+// every received row with id >= 0 overwrites the local tables; IDS: ids_out[r] = id (or -1).  One wavefront per row.
+template <bool IDS>
 __global__ __launch_bounds__(256) void k_xchg_scatter(zt_row_tables T, int row_floats, const float *__restrict__ recv, long long rows,
                                                       int *__restrict__ ids_out)
 {
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256) void k_xchg_scatter(zt_row_tables T, int row_f
     if (r >= rows) return;
     const float *in = recv + r * row_floats;
     const int id = __float_as_int(in[0]);
-    if (lane == 0) ids_out[r] = id;
+    if (IDS && lane == 0) ids_out[r] = id;
     if (id < 0) return;
     int col = 1;
     for (int t = 0; t < T.n; ++t) {
@@ -141,6 +142,18 @@ __global__ __launch_bounds__(256) void k_xchg_scatter(zt_row_tables T, int row_f
         for (int c = lane; c < w; c += 64) dst[c] = in[col + c];
         col += w;
     }
+}
+
+// the floats of a packed row: 1 + the tables' widths; 0: not a valid set of tables
+int row_floats_of(const zt_row_tables *t)
+{
+    if (!t || t->n < 1 || t->n > 8) return 0;
+    int row_floats = 1;
+    for (int q = 0; q < t->n; ++q) {
+        if (!t->ptr[q] || t->width[q] < 1) return 0;
+        row_floats += t->width[q];
+    }
+    return row_floats;
 }
 
 bool spin_until(const std::atomic<long long> *c, int world, long long want)
@@ -192,8 +205,7 @@ extern "C" int zt_exchange_create(zt_exchange **out, const zt_exchange_desc *d)
     add(d->memory, d->D);
     add(d->last_update, 1);
     if (x->with_messages) { add(d->messages, d->msg_dim); add(d->msg_ts, 1); }
-    x->row_floats = 1;
-    for (int q = 0; q < x->tables.n; ++q) x->row_floats += x->tables.width[q];
+    x->row_floats = row_floats_of(&x->tables);
     const size_t rowb = (size_t)x->row_floats * 4;
     ZT_HIP(hipMalloc(&x->send, (size_t)x->cap * rowb));
     ZT_HIP(hipMalloc(&x->recv, (size_t)x->world * x->cap * rowb));
@@ -303,7 +315,7 @@ int zt::exchange_step(zt_exchange *x, const int32_t *rows_dev, const int32_t *co
         h->read_done[x->rank].store(st, std::memory_order_release);
     }
     const long long rows = (long long)x->world * x->cap;
-    k_xchg_scatter<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(x->tables, x->row_floats, x->recv, rows, x->ids);
+    k_xchg_scatter<true><<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(x->tables, x->row_floats, x->recv, rows, x->ids);
     ZT_PROF_END(s, P_EXCHANGE);
     ZT_LAUNCH_CHECK();
     if (ids_out) *ids_out = x->ids;
@@ -312,3 +324,25 @@ int zt::exchange_step(zt_exchange *x, const int32_t *rows_dev, const int32_t *co
 }
 
 void zt::exchange_shape(const zt_exchange *x, int *rank, int *world) { *rank = x->rank; *world = x->world; }
+
+// the same pack and scatter as entry points of their own (a transport outside the library)
+extern "C" int zt_pack_rows(const zt_row_tables *tables, const int32_t *ids_dev, const int32_t *n_valid_dev, int64_t cap,
+                            float *out_dev, void *stream)
+{
+    const int row_floats = row_floats_of(tables);
+    if (row_floats == 0 || !ids_dev || !n_valid_dev || cap < 0 || (cap > 0 && !out_dev)) { set_error("zt_pack_rows: bad argument"); return ZT_ERR_ARG; }
+    if (cap == 0) return ZT_OK;
+    k_xchg_pack<<<(unsigned)((cap + 3) / 4), 256, 0, (hipStream_t)stream>>>(*tables, row_floats, ids_dev, n_valid_dev, cap, out_dev);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_scatter_rows(const zt_row_tables *tables, const float *recv_dev, int64_t rows, void *stream)
+{
+    const int row_floats = row_floats_of(tables);
+    if (row_floats == 0 || rows < 0 || (rows > 0 && !recv_dev)) { set_error("zt_scatter_rows: bad argument"); return ZT_ERR_ARG; }
+    if (rows == 0) return ZT_OK;
+    k_xchg_scatter<false><<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(*tables, row_floats, recv_dev, rows, nullptr);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}

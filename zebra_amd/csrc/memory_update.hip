@@ -190,9 +190,9 @@ __global__ void k_select_flagged(const int *__restrict__ ids, long long n_ids, c
     if (take) rows[base + __popcll(bm & ((1ull << lane) - 1ull))] = v;
 }
 
-// k_gru<MT>, MT = 1:            16 rows per workgroup: the kernel's time is one workgroup's latency (<= 1 per CU),
-                               // so smaller tiles on more CUs win over weight-fragment reuse -- also at C5's 8 192 rows
-                               // (512 tiles, each streaming the 686 KB of gate weights from L2: k_gru<2>, measured slower)
+// k_gru: 16 rows per workgroup: the kernel's time is one workgroup's latency (<= 1 per CU), so smaller tiles on more CUs
+// win over weight-fragment reuse -- also at C5's 8 192 rows (512 tiles, each streaming the 686 KB of gate weights from L2:
+// 32-row tiles, k_gru<2>, measured slower and removed)
 constexpr int GRU_NTW = 1;     // hidden N-tiles per wave; 8 waves -> D <= 128
 constexpr int GRU_WAVES = 8;
 constexpr int GRU_CH = 6;      // k-steps of weight fragments in flight
@@ -275,10 +275,10 @@ struct GruArgs {
     int cap;
 };
 
-// bid = the workgroup's 16 MT-row tile.  gate != nullptr (k_out_gru): before a row of the memory table is written every
+// bid = the workgroup's 16-row tile.  gate != nullptr (k_out_gru): before a row of the memory table is written every
 // source-path workgroup of the output layers must have its rows in LDS (SrcGate; LDS: one word more behind the node ids).
 // CELL_RNN: one gate -- the message part and the memory part in accumulators of their own (ani, anh), added after the biases.
-template <int CELL, int MT>
+template <int CELL>
 __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, const SrcGate *gate)
 {
     float *memory = G.memory, *last_update = G.last_update;
@@ -288,51 +288,51 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     const float *__restrict__ Wih_p = G.Wih_p, *__restrict__ Whh_p = G.Whh_p, *__restrict__ b_ih = G.b_ih, *__restrict__ b_hh = G.b_hh;
     const float *__restrict__ Wm_p = G.Wm_p;
     float *__restrict__ P = G.P;
-    float *A = reinterpret_cast<float *>(smem);      // [32][lda]: [message (Xp) | memory (Hp)]
+    float *A = reinterpret_cast<float *>(smem);      // [16][lda]: [message (Xp) | memory (Hp)]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r0 = bid * (MT * 16);
+    const int r0 = bid * 16;
     // the tile's node ids are requested TOGETHER with the row count, not after it (one dependent round trip less; an
     // entry beyond the count is a stale id that nobody dereferences: every gather below is masked by g < nr)
-    const int id_spec = tid < MT * 16 ? __builtin_nontemporal_load(rows + (r0 + tid < cap ? r0 + tid : cap - 1)) : 0;
+    const int id_spec = tid < 16 ? __builtin_nontemporal_load(rows + (r0 + tid < cap ? r0 + tid : cap - 1)) : 0;
     const int total = *n_rows;
     if (r0 >= total) return;
-    const int nr = (total - r0) < MT * 16 ? (total - r0) : MT * 16;
+    const int nr = (total - r0) < 16 ? (total - r0) : 16;
     const int Dp = Hp;
 
     // flat (row, column) gather, GU loads in flight per thread before any LDS store (see aggregate.hip)
     const int nthr = 64 * GRU_WAVES;
     constexpr int GU = 8;
-    int *rid = reinterpret_cast<int *>(A + (size_t)MT * 16 * lda);     // this tile's node ids
-    if (tid < MT * 16) rid[tid] = tid < nr ? id_spec : 0;
+    int *rid = reinterpret_cast<int *>(A + (size_t)16 * lda);     // this tile's node ids
+    if (tid < 16) rid[tid] = tid < nr ? id_spec : 0;
     __syncthreads();
-    for (int f0 = tid; f0 < MT * 16 * Xp; f0 += nthr * GU) {
+    for (int f0 = tid; f0 < 16 * Xp; f0 += nthr * GU) {
         float v[GU];
 #pragma unroll
         for (int u = 0; u < GU; ++u) {
             const int f = f0 + u * nthr;
             const int g = f / Xp, c = f - g * Xp;
-            v[u] = (f < MT * 16 * Xp && g < nr && c < msg_dim) ? messages[(size_t)rid[g] * msg_dim + c] : 0.f;
+            v[u] = (f < 16 * Xp && g < nr && c < msg_dim) ? messages[(size_t)rid[g] * msg_dim + c] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < GU; ++u) {
             const int f = f0 + u * nthr;
             const int g = f / Xp, c = f - g * Xp;
-            if (f < MT * 16 * Xp) A[(size_t)g * lda + c] = v[u];
+            if (f < 16 * Xp) A[(size_t)g * lda + c] = v[u];
         }
     }
     {   // the memory columns: all of a thread's elements in flight before its first LDS store (one round trip, not four)
         constexpr int HU = 4;
-        for (int f0 = tid; f0 < MT * 16 * Hp; f0 += nthr * HU) {
+        for (int f0 = tid; f0 < 16 * Hp; f0 += nthr * HU) {
             float v[HU];
 #pragma unroll
             for (int u = 0; u < HU; ++u) {
                 const int f = f0 + u * nthr, g = f / Hp, c = f - g * Hp;
-                v[u] = (f < MT * 16 * Hp && g < nr && c < D) ? memory[(size_t)rid[g] * D + c] : 0.f;
+                v[u] = (f < 16 * Hp && g < nr && c < D) ? memory[(size_t)rid[g] * D + c] : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < HU; ++u) {
                 const int f = f0 + u * nthr, g = f / Hp, c = f - g * Hp;
-                if (f < MT * 16 * Hp) A[(size_t)g * lda + Xp + c] = v[u];
+                if (f < 16 * Hp) A[(size_t)g * lda + Xp + c] = v[u];
             }
         }
     }
@@ -340,14 +340,12 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
 
     const int NT = (D + 15) / 16;
     const int r16 = lane & 15, g4 = lane >> 4;
-    // per (m-tile, n-tile): r, z (message + memory), n_i (message), n_h (memory)
-    f32x4 ar[MT][GRU_NTW], az[MT][GRU_NTW], ani[MT][GRU_NTW], anh[MT][GRU_NTW];
+    // per n-tile: r, z (message + memory), n_i (message), n_h (memory)
+    f32x4 ar[GRU_NTW], az[GRU_NTW], ani[GRU_NTW], anh[GRU_NTW];
 #pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < GRU_NTW; ++b) {
-            ar[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; az[a][b] = ar[a][b]; ani[a][b] = ar[a][b]; anh[a][b] = ar[a][b];
-        }
+    for (int b = 0; b < GRU_NTW; ++b) {
+        ar[b] = f32x4{0.f, 0.f, 0.f, 0.f}; az[b] = ar[b]; ani[b] = ar[b]; anh[b] = ar[b];
+    }
     bool live[GRU_NTW];
     int colrow[GRU_NTW];
 #pragma unroll
@@ -380,24 +378,19 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
 #pragma unroll
             for (int c = 0; c < GRU_CH; ++c) {
                 if (kc0 + c >= KC) break;
-                f32x4 av[MT];
-#pragma unroll
-                for (int a = 0; a < MT; ++a)
-                    av[a] = *reinterpret_cast<const f32x4 *>(A + (size_t)(a * 16 + r16) * lda + a_off + 16 * (kc0 + c) + 4 * g4);
+                const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)r16 * lda + a_off + 16 * (kc0 + c) + 4 * g4);
 #pragma unroll
                 for (int b = 0; b < GRU_NTW; ++b) {
                     if (!live[b]) continue;
 #pragma unroll
-                    for (int a = 0; a < MT; ++a)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if constexpr (CELL == CELL_GRU) {
-                                ar[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wr[c][b][j], ar[a][b], 0, 0, 0);
-                                az[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wz[c][b][j], az[a][b], 0, 0, 0);
-                            }
-                            if (hidden) anh[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wn[c][b][j], anh[a][b], 0, 0, 0);
-                            else        ani[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], wn[c][b][j], ani[a][b], 0, 0, 0);
+                    for (int j = 0; j < 4; ++j) {
+                        if constexpr (CELL == CELL_GRU) {
+                            ar[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wr[c][b][j], ar[b], 0, 0, 0);
+                            az[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wz[c][b][j], az[b], 0, 0, 0);
                         }
+                        if (hidden) anh[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wn[c][b][j], anh[b], 0, 0, 0);
+                        else        ani[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wn[c][b][j], ani[b], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -407,9 +400,9 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     // (the new rows go back into the tile for the projection below: every wave must be done READING the old ones -- the
     //  memory columns are the K operand of everybody's W_hh product)
     if (gate != nullptr) {
-        if (tid == 0) rid[MT * 16] = gate_wait(*gate) ? 1 : 0;
+        if (tid == 0) rid[16] = gate_wait(*gate) ? 1 : 0;
         __syncthreads();
-        if (rid[MT * 16] == 0) return;                 // (gave up: reported; the table keeps its rows)
+        if (rid[16] == 0) return;                 // (gave up: reported; the table keeps its rows)
     } else if (P != nullptr) __syncthreads();
     // gates (torch.nn.GRUCell): r,z = sigmoid(gi+gh); n = tanh(gi_n + r*gh_n); h' = (1-z)*n + z*h
     // (torch.nn.RNNCell: h' = tanh((gi + b_ih) + (gh + b_hh)))
@@ -421,33 +414,29 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
         if constexpr (CELL == CELL_RNN) {
             const float bi = b_ih[col], bh = b_hh[col];
 #pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int g = a * 16 + g4 * 4 + j;
-                    if (g >= nr) continue;
-                    const float hnew = tanhf((ani[a][b][j] + bi) + (anh[a][b][j] + bh));
-                    memory[(size_t)rid[g] * D + col] = hnew;
-                    if (P != nullptr) A[(size_t)g * lda + Xp + col] = hnew;
-                }
+            for (int j = 0; j < 4; ++j) {
+                const int g = g4 * 4 + j;
+                if (g >= nr) continue;
+                const float hnew = tanhf((ani[b][j] + bi) + (anh[b][j] + bh));
+                memory[(size_t)rid[g] * D + col] = hnew;
+                if (P != nullptr) A[(size_t)g * lda + Xp + col] = hnew;
+            }
             continue;
         }
         const float bir = b_ih[col], biz = b_ih[D + col], bin = b_ih[2 * D + col];
         const float bhr = b_hh[col], bhz = b_hh[D + col], bhn = b_hh[2 * D + col];
 #pragma unroll
-        for (int a = 0; a < MT; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int g = a * 16 + g4 * 4 + j;
-                if (g >= nr) continue;
-                const float r = 1.f / (1.f + expf(-(ar[a][b][j] + bir + bhr)));
-                const float z = 1.f / (1.f + expf(-(az[a][b][j] + biz + bhz)));
-                const float n = tanhf(ani[a][b][j] + bin + r * (anh[a][b][j] + bhn));
-                const float hold = A[(size_t)g * lda + Xp + col];
-                const float hnew = (1.f - z) * n + z * hold;
-                memory[(size_t)rid[g] * D + col] = hnew;
-                if (P != nullptr) A[(size_t)g * lda + Xp + col] = hnew;    // (this thread alone reads and writes the element)
-            }
+        for (int j = 0; j < 4; ++j) {
+            const int g = g4 * 4 + j;
+            if (g >= nr) continue;
+            const float r = 1.f / (1.f + expf(-(ar[b][j] + bir + bhr)));
+            const float z = 1.f / (1.f + expf(-(az[b][j] + biz + bhz)));
+            const float n = tanhf(ani[b][j] + bin + r * (anh[b][j] + bhn));
+            const float hold = A[(size_t)g * lda + Xp + col];
+            const float hnew = (1.f - z) * n + z * hold;
+            memory[(size_t)rid[g] * D + col] = hnew;
+            if (P != nullptr) A[(size_t)g * lda + Xp + col] = hnew;    // (this thread alone reads and writes the element)
+        }
     }
     for (int g = tid; g < nr; g += nthr) {
         const int v = rid[g];
@@ -464,31 +453,28 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
             for (int c = 0; c < 8; ++c)
                 wv[c] = c < KC ? *reinterpret_cast<const f32x4 *>(Wm_p + (size_t)(wave * 16 + r16) * Hp + 16 * c + 4 * g4)
                                : f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int a = 0; a < MT; ++a) {
-                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < 8; ++c) {
+                if (c >= KC) break;
+                const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)r16 * lda + Xp + 16 * c + 4 * g4);
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    if (c >= KC) break;
-                    const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)(a * 16 + r16) * lda + Xp + 16 * c + 4 * g4);
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv[c][j], acc, 0, 0, 0);
+            }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv[c][j], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int g = a * 16 + g4 * 4 + j;
-                    if (g < nr) P[(size_t)rid[g] * Hp + wave * 16 + r16] = acc[j];
-                }
+            for (int j = 0; j < 4; ++j) {
+                const int g = g4 * 4 + j;
+                if (g < nr) P[(size_t)rid[g] * Hp + wave * 16 + r16] = acc[j];
             }
         }
     }
 }
 
-template <int CELL, int MT>
+template <int CELL>
 __global__ __launch_bounds__(64 * GRU_WAVES) void k_gru(GruArgs G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gru_body<CELL, MT>(G, smem, blockIdx.x, nullptr);
+    gru_body<CELL>(G, smem, blockIdx.x, nullptr);
 }
 
 // The output layers and the GRU update in ONE launch (round 5).  The two kernels are independent but for the memory rows the
@@ -503,7 +489,7 @@ __global__ __launch_bounds__(64 * GRU_WAVES) void k_out_gru(EmbedOutArgs E, int 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int bid = blockIdx.x;
     if (bid >= out_tiles && bid < out_tiles + gru_wgs) {
-        gru_body<CELL, 1>(G, smem, bid - out_tiles, &gate);
+        gru_body<CELL>(G, smem, bid - out_tiles, &gate);
         if (threadIdx.x == 0) gate_leave(gate);              // (thread 0 is the one that waited, if the tile had rows at all)
         return;
     }
@@ -681,7 +667,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &GS, char *sme
         }
         }
         if (nt == 0 && lane < nr) { const int v = rid[lane]; last_update[v] = msg_ts[v]; }      // memory_updater.py:40
-        // ---- arrive: the tile's last workgroup commits (sc1 stores drained, no fence: see k_gru_persist) ----
+        // ---- arrive: the tile's last workgroup commits (sc1 stores drained, no fence: see the k_gru_persist note below) ----
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         int done = 0;
         if (lane == 0) done = atomicAdd(&tile_cnt[bx], 1);
@@ -779,12 +765,9 @@ __global__ __launch_bounds__(64 * GS_WAVES) void k_out_gru2(EmbedOutArgs E, int 
 //  arrival per tile -- drained sc1 stores, a returning atomic, two barriers -- that a persistent loop pays per TILE where
 //  k_gru_split pays it once per workgroup: 8 192 rows 137 us against k_gru's 66, 2 000 rows 47 against 30, 1 200 rows
 //  (message 472 wide) 43 against 37; only at 400 rows 25 against 27.  tools/exp/p23_kernels.py, profiles/r5/experiments/.)
-constexpr int GP_TILE_COUNTERS = GS_TILE_COUNTERS;
-constexpr long long GP_MAX_ROWS = (long long)GS_MAX_ROWS;
-
 struct GruPlan {
     int Xp, Hp, lda;
-    size_t lds, off_rows, off_cnt, off_wih, off_whh, off_tiles, off_hnew, total;
+    size_t off_rows, off_cnt, off_wih, off_whh, off_tiles, off_hnew, total;
 };
 
 void gru_plan(int64_t max_rows, int D, int msg_dim, GruPlan &p)
@@ -792,7 +775,6 @@ void gru_plan(int64_t max_rows, int D, int msg_dim, GruPlan &p)
     p.Xp = round_up(msg_dim, 16);
     p.Hp = round_up(D, 16);
     p.lda = p.Xp + p.Hp + 4;
-    p.lds = (size_t)2 * 16 * p.lda * 4 + 2 * 16 * 4;   // A tile + node ids of k_gru<2> (k_gru<1> uses half)
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
     // the packed weights come BEFORE the row list: their place does not depend on max_rows, so a workspace whose
@@ -800,70 +782,22 @@ void gru_plan(int64_t max_rows, int D, int msg_dim, GruPlan &p)
     p.off_cnt = take(256);
     p.off_wih = take((size_t)3 * p.Hp * p.Xp * 4);
     p.off_whh = take((size_t)3 * p.Hp * p.Hp * 4);
-    p.off_tiles = take((size_t)GP_TILE_COUNTERS * 4);                    // k_gru_split / k_gru_persist: arrival counters per tile (zeroed with the weights)
+    p.off_tiles = take((size_t)GS_TILE_COUNTERS * 4);                    // k_gru_split: arrival counters per tile (zeroed with the weights)
     p.off_rows = take((size_t)(max_rows > 0 ? max_rows : 1) * 4);
-    // new rows until the tile's commit (k_gru_split, k_gru_persist)
-    p.off_hnew = take(max_rows > 0 && max_rows <= GP_MAX_ROWS ? (size_t)((max_rows + 15) / 16 * 16) * p.Hp * 4 : 0);
+    // new rows until the tile's commit (k_gru_split)
+    p.off_hnew = take(max_rows > 0 && max_rows <= GS_MAX_ROWS ? (size_t)((max_rows + 15) / 16 * 16) * p.Hp * 4 : 0);
     p.total = o;
 }
 
+// The widest [message | memory] row the update takes: Xp + Hp <= GRU_MAX_XH.  (The limit two 16-row tiles of the row in
+// 150 KB of LDS once set -- 2 x 16 x (Xp + Hp + 4) x 4 + 128 bytes; at D = 100 a message of 1 072 floats.  k_gru stages one
+// tile now, but the widths the update accepts stay as they were.)
+constexpr int GRU_MAX_XH = 1184;
 
-// ---- one-node multi-GPU exchange (no reference counterpart) ----
-// A touched row travels as float32 [id (int bits) | row of table 0 | row of table 1 | ...].
-struct RowTables {
-    float *ptr[8];
-    int width[8];
-    int n, row_floats;
-};
-
-// one wavefront per slot r < cap: ids[r] (r < *n_valid) or -1, then the id's row of every table (zeros for -1)
-__global__ __launch_bounds__(256) void k_pack_rows(RowTables T, const int *__restrict__ ids, const int *__restrict__ n_valid,
-                                                   long long cap, float *__restrict__ out)
+// two positions per wave where the shape allows (zt_set_kernel_choice(ZT_CHOICE_MESSAGES, ZT_MSG_ONE) pins the other kernel)
+MsgKernel message_kernel(int D, int F, int T, int msg_choice)
 {
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= cap) return;
-    const int id = r < (long long)*n_valid ? ids[r] : -1;
-    float *o = out + r * T.row_floats;
-    if (lane == 0) o[0] = __int_as_float(id);
-    int col = 1;
-    for (int t = 0; t < T.n; ++t) {
-        const int w = T.width[t];
-        const float *src = T.ptr[t] + (size_t)(id < 0 ? 0 : id) * w;
-        for (int c = lane; c < w; c += 64) o[col + c] = id < 0 ? 0.f : src[c];
-        col += w;
-    }
-}
-
-// one wavefront per received row: rows with id >= 0 overwrite the local tables
-__global__ __launch_bounds__(256) void k_scatter_rows(RowTables T, const float *__restrict__ recv, long long rows)
-{
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= rows) return;
-    const float *in = recv + r * T.row_floats;
-    const int id = __float_as_int(in[0]);
-    if (id < 0) return;
-    int col = 1;
-    for (int t = 0; t < T.n; ++t) {
-        const int w = T.width[t];
-        float *dst = T.ptr[t] + (size_t)id * w;
-        for (int c = lane; c < w; c += 64) dst[c] = in[col + c];
-        col += w;
-    }
-}
-
-static bool make_tables(const zt_row_tables *t, RowTables &T)
-{
-    if (!t || t->n < 1 || t->n > 8) return false;
-    T.n = t->n;
-    T.row_floats = 1;
-    for (int q = 0; q < t->n; ++q) {
-        if (!t->ptr[q] || t->width[q] < 1) return false;
-        T.ptr[q] = t->ptr[q]; T.width[q] = t->width[q];
-        T.row_floats += t->width[q];
-    }
-    return true;
+    return msg_choice != ZT_MSG_ONE && D <= 128 && T <= 128 && F <= 256 ? MsgKernel::two : MsgKernel::one;
 }
 
 }  // namespace
@@ -921,15 +855,14 @@ int zt::store_messages_ex(const float *memory_dev, const float *last_update_dev,
     ZT_PROF_BEGIN(s, P_STORE_MSG);
     k_last_pos<<<(unsigned)((2 * B + 255) / 256), 256, 0, s>>>(src_dev, dst_dev, e64, B, num_nodes, num_edges,
                                                                scratch_dev, status_dev, zero_word_dev);
-    // two positions per wave where the shape allows (zt_set_kernel_choice(ZT_CHOICE_MESSAGES, ZT_MSG_ONE) pins the other kernel)
-    if (zt::kernel_choice(ZT_CHOICE_MESSAGES) != ZT_MSG_ONE && D <= 128 && T <= 128 && F <= 256)
+    if (message_kernel(D, F, T, zt::kernel_choice(ZT_CHOICE_MESSAGES)) == MsgKernel::two)
         k_build_messages2<<<(unsigned)(((2 * B + 1) / 2 + 3) / 4), 256, 0, s>>>(
             memory_dev, last_update_dev, efeat_dev, time_w_dev, num_nodes, num_edges, D, F, T, src_dev, dst_dev, ts_dev, e64,
             B, messages_dev, msg_ts_dev, flags_dev, scratch_dev, uniq_ids_dev, n_uniq_dev, status_dev, pos_lo, pos_hi, set_flags ? 1 : 0);
     else
-    k_build_messages<<<(unsigned)((2 * B + 3) / 4), 256, 0, s>>>(
-        memory_dev, last_update_dev, efeat_dev, time_w_dev, num_nodes, num_edges, D, F, T, src_dev, dst_dev, ts_dev, e64,
-        B, messages_dev, msg_ts_dev, flags_dev, scratch_dev, uniq_ids_dev, n_uniq_dev, status_dev, pos_lo, pos_hi, set_flags ? 1 : 0);
+        k_build_messages<<<(unsigned)((2 * B + 3) / 4), 256, 0, s>>>(
+            memory_dev, last_update_dev, efeat_dev, time_w_dev, num_nodes, num_edges, D, F, T, src_dev, dst_dev, ts_dev, e64,
+            B, messages_dev, msg_ts_dev, flags_dev, scratch_dev, uniq_ids_dev, n_uniq_dev, status_dev, pos_lo, pos_hi, set_flags ? 1 : 0);
     ZT_PROF_END(s, P_STORE_MSG);
     ZT_LAUNCH_CHECK();
     if (zeroed_out) *zeroed_out = zero_word_dev != nullptr;      // k_last_pos ran: the word is zero for whatever follows on this stream
@@ -971,6 +904,59 @@ extern "C" int zt_rnn_update(float *memory_dev, float *last_update_dev, const fl
                              ZT_CELL_RNN);
 }
 
+// Two organisations of the same update (zt_set_kernel_choice(ZT_CHOICE_GRU, ..) pins one, for either cell; tests hold them
+// against each other and torch's GRUCell / RNNCell):
+//   split (k_gru_split) <= 512 rows: a workgroup per (16 rows, N-tile) -- the whole chip works on what k_gru gives a tenth of it;
+//   tile (k_gru)        beyond: 16 rows per workgroup, the gate weights streamed from L2 per tile.
+// Output layers held back by embed_ex go into the same launch where both take their tiled forms (k_out_gru) or both their
+// latency-organised ones (k_out_gru2), otherwise in front of the GRU kernel: their source path reads the rows it rewrites.
+MemoryPlan zt::memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, int T, int gru_choice, int msg_choice,
+                                  const HeldOut &held)
+{
+    MemoryPlan mp{};
+    mp.msg = message_kernel(D, F, T, msg_choice);
+    mp.out = held.present ? OutLaunch::front : OutLaunch::none;         // (a refused or empty update: launched on the way out)
+    if (D <= 0 || msg_dim <= 0) { mp.refusal = MemRefusal::arg; return mp; }
+    if (D > 128) { mp.refusal = MemRefusal::d_large; return mp; }
+    if (max_rows == 0) return mp;
+    if (msg_dim > GRU_MAX_XH - round_up(D, 16)) { mp.refusal = MemRefusal::msg_wide; return mp; }
+    GruPlan p;
+    gru_plan(max_rows, D, msg_dim, p);
+    const bool hg_ok = held.hg == 1 || held.hg == 5 || held.hg == 10;
+    const bool fits = max_rows <= GS_MAX_ROWS && (p.Xp + p.Hp) / 16 <= GS_WAVES * GS_MAXCH && 16 * (msg_dim + D) <= GS_STAGE * 256 &&
+                      16 * p.Hp <= 7 * 256;
+    mp.gru_tiles = (int)((max_rows + 15) / 16);
+    mp.NTg = p.Hp / 16;
+    mp.grid = (unsigned)mp.gru_tiles;
+    if (fits && (gru_choice == ZT_GRU_SPLIT || (gru_choice == 0 && max_rows <= 512))) {
+        mp.gru = GruForm::split;
+        mp.lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
+        if (held.present && held.form == OutForm::latency && held.same_memory && (held.D + 15) / 16 == mp.NTg &&
+            (mp.NTg == 7 || mp.NTg == 8) && hg_ok) {
+            const int per_path = held.gx * mp.NTg;
+            mp.out = OutLaunch::fused_split;
+            mp.n_src_wgs = (per_path + 3) / 4;
+            mp.n_nb_wgs = (per_path * held.M + 3) / 4;
+            mp.lds_f = std::max((size_t)4 * 16 * (mp.NTg * 16 + 4) * 4, mp.lds2);
+            mp.target = (unsigned)per_path;
+            mp.participants = (unsigned)(per_path + mp.gru_tiles * mp.NTg);
+            mp.grid = (unsigned)(mp.n_src_wgs + mp.gru_tiles * mp.NTg + mp.n_nb_wgs);
+        }
+    } else {
+        mp.gru = GruForm::tile;
+        mp.lds = (size_t)16 * p.lda * 4 + 32 * 4;                       // A tile + node ids + the gate's verdict (k_out_gru)
+        if (held.present && held.form == OutForm::tiled && held.same_memory && hg_ok) {
+            mp.out = OutLaunch::fused_tile;
+            mp.out_tiles = (int)((held.N + OUT_ROWS - 1) / OUT_ROWS);
+            mp.lds_f = std::max((size_t)2 * OUT_ROWS * (round_up(held.D, 16) + 4) * 4 + OUT_ROWS * 4, mp.lds);
+            mp.target = (unsigned)mp.out_tiles;
+            mp.participants = (unsigned)mp.out_tiles + (unsigned)mp.gru_tiles;
+            mp.grid = (unsigned)(mp.out_tiles * (held.M + 1)) + (unsigned)mp.gru_tiles;
+        }
+    }
+    return mp;
+}
+
 // zt_gru_update with the refresh of the projected table folded in (pipeline.hip): wm_p = W_m padded to [Dp][Dp]
 // (zt::embed_wm_ptr), proj_table = [num_nodes][Dp]; both NULL: plain zt_gru_update
 int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *messages_dev, const float *msg_ts_dev,
@@ -979,23 +965,34 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
                       const float *wm_p, float *proj_table, void *stream, bool counter_zeroed, bool select_done,
                       zt::embed_out_deferred *fuse, int cell)
 {
-    // (output layers held back by embed_ex: launched here whatever happens -- beside the GRU kernel where the shapes allow)
+    // (output layers held back by embed_ex run exactly once whatever happens: fused with the GRU kernel, else launched in
+    //  front of it or on the way out)
     struct PendingOut {
         zt::embed_out_deferred *d; void *s;
-        ~PendingOut() { if (d && d->valid) { (void)zt::embed_out_launch(*d, s); d->valid = false; } }
+        int launch() { if (!d || !d->valid) return ZT_OK; d->valid = false; return zt::embed_out_launch(*d, s); }
+        ~PendingOut() { (void)launch(); }
     } pending{fuse, stream};
     const char *name = cell == CELL_RNN ? "zt_rnn_update" : "zt_gru_update";
-    if (!memory_dev || !last_update_dev || !messages_dev || !msg_ts_dev || !flags_dev || !wt || !workspace_dev ||
-        D <= 0 || msg_dim <= 0 || n_ids < 0 || (cell != CELL_GRU && cell != CELL_RNN)) {
+    if (!memory_dev || !last_update_dev || !messages_dev || !msg_ts_dev || !flags_dev || !wt || !workspace_dev || n_ids < 0 ||
+        (cell != CELL_GRU && cell != CELL_RNN)) {
         set_error("%s: bad argument", name);
         return ZT_ERR_ARG;
     }
-    if (D > 128) { set_error("%s: D=%d > 128 unsupported", name, D); return ZT_ERR_UNSUPPORTED; }
     const int64_t max_rows = ids_dev ? n_ids : num_nodes;
-    if (max_rows == 0) return ZT_OK;
+    HeldOut held{};
+    if (fuse != nullptr && fuse->valid)
+        held = HeldOut{true, fuse->form, fuse->hg, fuse->args.D, fuse->args.M, fuse->gx, fuse->args.N, fuse->args.memory == memory_dev};
+    // (F, T = 0: the message kernel is store_messages_ex's)
+    const MemoryPlan mp = memory_kernel_plan(max_rows, D, msg_dim, 0, 0, zt::kernel_choice(ZT_CHOICE_GRU), 0, held);
+    switch (mp.refusal) {
+    case MemRefusal::none: break;
+    case MemRefusal::arg: set_error("%s: bad argument", name); return ZT_ERR_ARG;
+    case MemRefusal::d_large: set_error("%s: D=%d > 128 unsupported", name, D); return ZT_ERR_UNSUPPORTED;
+    case MemRefusal::msg_wide: set_error("%s: message width %d too large", name, msg_dim); return ZT_ERR_UNSUPPORTED;
+    }
+    if (mp.gru == GruForm::none) return ZT_OK;                           // no rows
     GruPlan p;
     gru_plan(max_rows, D, msg_dim, p);
-    if (p.lds > 150 * 1024) { set_error("%s: message width %d too large", name, msg_dim); return ZT_ERR_UNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
     int *cnt = reinterpret_cast<int *>(ws + p.off_cnt);
@@ -1015,87 +1012,46 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
             k_pack_gates<3><<<(3 * p.Hp * p.Xp + 255) / 256, 256, 0, s>>>(wt->w_ih, D, msg_dim, wih, p.Hp, p.Xp);
             k_pack_gates<3><<<(3 * p.Hp * p.Hp + 255) / 256, 256, 0, s>>>(wt->w_hh, D, D, whh, p.Hp, p.Hp);
         }
-        ZT_HIP(hipMemsetAsync(ws + p.off_tiles, 0, (size_t)GP_TILE_COUNTERS * 4, s));
+        ZT_HIP(hipMemsetAsync(ws + p.off_tiles, 0, (size_t)GS_TILE_COUNTERS * 4, s));
         ZT_HIP(hipMemsetAsync(cnt + GRU_SRC_WORD, 0, 2 * sizeof(int), s));   // the gate's two words (a fresh workspace; afterwards every launch leaves them at zero)
     }
-    // Two organisations of the same update (zt_set_kernel_choice(ZT_CHOICE_GRU, ..) pins one, for either cell; tests hold them
-    // against each other and torch's GRUCell / RNNCell):
-    //   k_gru_split   <= 512 rows: a workgroup per (16 rows, N-tile) -- the whole chip works on what k_gru gives a tenth of it;
-    //   k_gru         beyond: 16 rows per workgroup, the gate weights streamed from L2 per tile.
-    const int choice = zt::kernel_choice(ZT_CHOICE_GRU);
-    const bool fits = max_rows <= GS_MAX_ROWS && (p.Xp + p.Hp) / 16 <= GS_WAVES * GS_MAXCH && 16 * (msg_dim + D) <= GS_STAGE * 256 &&
-                      16 * p.Hp <= 7 * 256;
-    const bool split = fits && (choice == ZT_GRU_SPLIT || (choice == 0 && max_rows <= 512));
+    if (mp.out == OutLaunch::front) { const int rc = pending.launch(); if (rc != ZT_OK) return rc; }
+    const GruArgs G{memory_dev, last_update_dev, messages_dev, msg_ts_dev, rows, cnt, D, msg_dim, p.Xp, p.Hp, p.lda,
+                    wih, whh, wt->b_ih, wt->b_hh, wm_p, proj_table, (int)max_rows};
+    const GruSplitArgs GS{G, reinterpret_cast<int *>(ws + p.off_tiles), reinterpret_cast<float *>(ws + p.off_hnew)};
+    const SrcGate gate{cnt + GRU_SRC_WORD, mp.target, mp.participants, held.present ? fuse->args.status : nullptr,
+                       held.present ? fuse->latch : nullptr};
     const int rc_launch = dispatch<CELL_GRU, CELL_RNN>(cell, [&](auto CV) -> int {
         constexpr int CELL = decltype(CV)::value;
-        if (split) {
-            const size_t lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
-            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split<CELL>), lds2));
-            GruSplitArgs GS;
-            GS.g.memory = memory_dev; GS.g.last_update = last_update_dev; GS.g.messages = messages_dev; GS.g.msg_ts = msg_ts_dev; GS.g.rows = rows;
-            GS.g.n_rows = cnt; GS.g.D = D; GS.g.msg_dim = msg_dim; GS.g.Xp = p.Xp; GS.g.Hp = p.Hp; GS.g.lda = p.lda; GS.g.Wih_p = wih; GS.g.Whh_p = whh;
-            GS.g.b_ih = wt->b_ih; GS.g.b_hh = wt->b_hh; GS.g.Wm_p = wm_p; GS.g.P = proj_table; GS.g.cap = (int)max_rows;
-            GS.tile_cnt = reinterpret_cast<int *>(ws + p.off_tiles); GS.hnew = reinterpret_cast<float *>(ws + p.off_hnew);
-            const int gru_tiles = (int)((max_rows + 15) / 16), NTg = p.Hp / 16;
-            const bool can_fuse2 = fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::latency && fuse->args.memory == memory_dev &&
-                                   (fuse->args.D + 15) / 16 == NTg && (NTg == 7 || NTg == 8) && (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10);
-            if (can_fuse2) {
-                const zt::embed_out_deferred &d = *fuse;
-                const int per_path = d.gx * NTg, n_src_wgs = (per_path + 3) / 4, n_nb_wgs = (per_path * d.args.M + 3) / 4;
-                size_t lds_f = (size_t)4 * 16 * (NTg * 16 + 4) * 4;
-                if (lds_f < lds2) lds_f = lds2;
-                SrcGate gate;
-                gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)per_path; gate.participants = (unsigned)(per_path + gru_tiles * NTg);
-                gate.status = d.args.status; gate.latch = d.latch;
-                const unsigned grid = (unsigned)(n_src_wgs + gru_tiles * NTg + n_nb_wgs);
-                const int rc = dispatch<7, 8>(NTg, [&](auto NTV) {
-                    return dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
-                        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru2<CELL, NTV, HGV>), lds_f));
-                        k_out_gru2<CELL, NTV, HGV><<<grid, 64 * GS_WAVES, lds_f, s>>>(d.args, d.gx, n_src_wgs, gru_tiles, GS, gate);
-                        return ZT_OK;
-                    });
-                });
-                if (rc != ZT_OK) return rc;
-                fuse->valid = false;
-            } else {
-                // (held-back output layers first: their source path reads the rows this kernel rewrites)
-                if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
-                k_gru_split<CELL><<<dim3((unsigned)gru_tiles, (unsigned)NTg), 64 * GS_WAVES, lds2, s>>>(GS);
-            }
-        } else {
-            const size_t lds = (size_t)16 * p.lda * 4 + 32 * 4;              // A tile + node ids + the gate's verdict (k_out_gru)
-            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<CELL, 1>), lds));
-            GruArgs G;
-            G.memory = memory_dev; G.last_update = last_update_dev; G.messages = messages_dev; G.msg_ts = msg_ts_dev; G.rows = rows; G.n_rows = cnt;
-            G.D = D; G.msg_dim = msg_dim; G.Xp = p.Xp; G.Hp = p.Hp; G.lda = p.lda; G.Wih_p = wih; G.Whh_p = whh; G.b_ih = wt->b_ih; G.b_hh = wt->b_hh;
-            G.Wm_p = wm_p; G.P = proj_table; G.cap = (int)max_rows;
-            const unsigned gru_wgs = (unsigned)((max_rows + 15) / 16);
-            if (fuse != nullptr && fuse->valid && fuse->form == zt::OutForm::tiled && fuse->args.memory == memory_dev &&
-                (fuse->hg == 1 || fuse->hg == 5 || fuse->hg == 10)) {
-                const zt::embed_out_deferred &d = *fuse;
-                const int out_tiles = (int)((d.args.N + OUT_ROWS - 1) / OUT_ROWS), n_out = out_tiles * (d.args.M + 1);
-                const int Dp = (d.args.D + 15) / 16 * 16;
-                size_t lds_f = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
-                if (lds_f < lds) lds_f = lds;
-                SrcGate gate;
-                gate.word = cnt + GRU_SRC_WORD; gate.target = (unsigned)out_tiles; gate.participants = (unsigned)out_tiles + gru_wgs;
-                gate.status = d.args.status; gate.latch = d.latch;
-                const unsigned grid = (unsigned)n_out + gru_wgs;
-                const int rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
-                    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru<CELL, HGV>), lds_f));
-                    k_out_gru<CELL, HGV><<<grid, 64 * GRU_WAVES, lds_f, s>>>(d.args, out_tiles, (int)gru_wgs, G, gate);
+        switch (mp.out) {
+        case OutLaunch::fused_tile:
+            return dispatch<1, 5, 10>(fuse->hg, [&](auto HGV) {
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru<CELL, HGV>), mp.lds_f));
+                k_out_gru<CELL, HGV><<<mp.grid, 64 * GRU_WAVES, mp.lds_f, s>>>(fuse->args, mp.out_tiles, mp.gru_tiles, G, gate);
+                return ZT_OK;
+            });
+        case OutLaunch::fused_split:
+            return dispatch<7, 8>(mp.NTg, [&](auto NTV) {
+                return dispatch<1, 5, 10>(fuse->hg, [&](auto HGV) {
+                    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_out_gru2<CELL, NTV, HGV>), mp.lds_f));
+                    k_out_gru2<CELL, NTV, HGV><<<mp.grid, 64 * GS_WAVES, mp.lds_f, s>>>(fuse->args, fuse->gx, mp.n_src_wgs,
+                                                                                      mp.gru_tiles, GS, gate);
                     return ZT_OK;
                 });
-                if (rc != ZT_OK) return rc;
-                fuse->valid = false;                       // (launched)
+            });
+        default:
+            if (mp.gru == GruForm::split) {
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split<CELL>), mp.lds2));
+                k_gru_split<CELL><<<dim3(mp.grid, (unsigned)mp.NTg), 64 * GS_WAVES, mp.lds2, s>>>(GS);
             } else {
-                if (fuse != nullptr && fuse->valid) { const int rc = zt::embed_out_launch(*fuse, s); fuse->valid = false; if (rc != ZT_OK) return rc; }
-                k_gru<CELL, 1><<<gru_wgs, 64 * GRU_WAVES, lds, s>>>(G);
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<CELL>), mp.lds));
+                k_gru<CELL><<<mp.grid, 64 * GRU_WAVES, mp.lds, s>>>(G);
             }
+            return ZT_OK;
         }
-        return ZT_OK;
     });
     if (rc_launch != ZT_OK) return rc_launch;
+    if (mp.out == OutLaunch::fused_tile || mp.out == OutLaunch::fused_split) fuse->valid = false;     // (launched)
     ZT_PROF_END(s, P_GRU);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
@@ -1109,30 +1065,3 @@ extern "C" int zt_debug_gru(unsigned long long *host)
     return ZT_OK;
 }
 #endif
-
-extern "C" int zt_pack_rows(const zt_row_tables *tables, const int32_t *ids_dev, const int32_t *n_valid_dev, int64_t cap,
-                            float *out_dev, void *stream)
-{
-    RowTables T;
-    if (!make_tables(tables, T) || !ids_dev || !n_valid_dev || cap < 0 || (cap > 0 && !out_dev)) {
-        set_error("zt_pack_rows: bad argument");
-        return ZT_ERR_ARG;
-    }
-    if (cap == 0) return ZT_OK;
-    k_pack_rows<<<(unsigned)((cap + 3) / 4), 256, 0, (hipStream_t)stream>>>(T, ids_dev, n_valid_dev, cap, out_dev);
-    ZT_LAUNCH_CHECK();
-    return ZT_OK;
-}
-
-extern "C" int zt_scatter_rows(const zt_row_tables *tables, const float *recv_dev, int64_t rows, void *stream)
-{
-    RowTables T;
-    if (!make_tables(tables, T) || rows < 0 || (rows > 0 && !recv_dev)) {
-        set_error("zt_scatter_rows: bad argument");
-        return ZT_ERR_ARG;
-    }
-    if (rows == 0) return ZT_OK;
-    k_scatter_rows<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(T, recv_dev, rows);
-    ZT_LAUNCH_CHECK();
-    return ZT_OK;
-}

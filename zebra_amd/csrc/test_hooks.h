@@ -33,6 +33,14 @@ int zt_test_tppr_plan_dump(zt_tppr *h, int32_t *wo, int32_t *pflag, int32_t *hv,
  * choice; agg_choice / out_choice: the ZT_CHOICE_AGGREGATE / ZT_CHOICE_EMBED_OUT selections. */
 int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table, int32_t training,
                        int32_t agg_choice, int32_t out_choice, int32_t *agg_out, int32_t *out_out, int64_t *lds_out);
+/* Test hook: the memory update's kernel choice for one shape (zt::memory_kernel_plan, host code only).  The held-back output
+ * layers: held (0 / 1), out_form (0 tiled, 1 latency, 2 persist), hg, out_D, out_M, gx, out_N, same_memory.  out[14] =
+ * refusal (0 none, 1 bad argument, 2 D > 128, 3 message width), message kernel (0 one, 1 two positions per wave), GRU form
+ * (0 none, 1 tile, 2 split), output layers (0 none, 1 in front, 2 fused with the tile, 3 fused with the split), lds, lds2,
+ * lds_f, gru_tiles, NTg, n_src_wgs, n_nb_wgs, out_tiles, target, participants. */
+int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F, int32_t T, int32_t gru_choice,
+                        int32_t msg_choice, int32_t held, int32_t out_form, int32_t hg, int32_t out_D, int32_t out_M,
+                        int32_t gx, int64_t out_N, int32_t same_memory, int64_t *out);
 
 #ifdef __cplusplus
 }

@@ -126,3 +126,17 @@ extern "C" int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, in
     *lds_out = (int64_t)kp.lds;
     return ZT_OK;
 }
+
+extern "C" int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F, int32_t T, int32_t gru_choice,
+                                   int32_t msg_choice, int32_t held, int32_t out_form, int32_t hg, int32_t out_D, int32_t out_M,
+                                   int32_t gx, int64_t out_N, int32_t same_memory, int64_t *out)
+{
+    if (!out || out_form < 0 || out_form > 2) return ZT_ERR_ARG;
+    const HeldOut h{held != 0, (OutForm)out_form, hg, out_D, out_M, gx, (long long)out_N, same_memory != 0};
+    const MemoryPlan mp = memory_kernel_plan(max_rows, D, msg_dim, F, T, gru_choice, msg_choice, h);
+    const int64_t v[14] = {(int64_t)mp.refusal, (int64_t)mp.msg, (int64_t)mp.gru, (int64_t)mp.out, (int64_t)mp.lds, (int64_t)mp.lds2,
+                           (int64_t)mp.lds_f, mp.gru_tiles, mp.NTg, mp.n_src_wgs, mp.n_nb_wgs, mp.out_tiles, mp.target,
+                           mp.participants};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+    return ZT_OK;
+}
