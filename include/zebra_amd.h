@@ -330,7 +330,7 @@ int zt_project_memory(const float *memory_dev, int64_t num_nodes, int32_t D,
  * drop_p > 0: the reference's training dropout of the hidden layer (nn.Dropout(0.1) between fc1's ReLU and fc2,
  *   modules/embedding_module.py:89,323-326) inside the kernels: the keep-mask is a hash of (drop_seed, element),
  *   regenerated by the backward from the same seed -- pass the forward's values.
- * Shapes: D <= 128, k <= ZT_MAX_K_WIDE.  A query row of up to 80 neighbours is one tile of the fused kernels; a wider one
+ * Shapes: D <= 128 or a multiple of 4 up to 256, k <= ZT_MAX_K_WIDE.  A query row of up to 80 neighbours is one tile of the fused kernels; a wider one
  *   is split into chunks of neighbours (forward: one workgroup per query row walks its chunks, H the same from run to run;
  *   backward: one tile per chunk), so F = 172 trains at any k up to ZT_MAX_K_WIDE as well.
  * workspaces: zt_embed_workspace_bytes(N, ...) / zt_agg_backward_workspace_bytes(D, F, T). */
@@ -342,6 +342,9 @@ int zt_agg_train_forward(const float *memory_dev, const float *overlay_dev, cons
                          void *workspace_dev, int32_t *status_dev, float drop_p, uint64_t drop_seed,
                          void *stream);
 int64_t zt_agg_backward_workspace_bytes(int32_t D, int32_t F, int32_t T);
+/* 1 if zt_agg_train_forward and zt_agg_train_backward both take (N, D, F, T, M, k), else 0: the fused training path
+ * where the library has kernels for the shape, the caller's own composition elsewhere. */
+int32_t zt_agg_train_supported(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k);
 int zt_agg_train_backward(const float *memory_dev, const float *overlay_dev, const int32_t *row_map_dev,
                           const float *efeat_dev, const float *time_w_dev, int64_t num_nodes,
                           int64_t num_edges, int32_t D, int32_t F, int32_t T, int64_t N, int32_t M,
@@ -431,7 +434,7 @@ int zt_gru_update(float *memory_dev, float *last_update_dev,
  * sit where they sit for the GRU; the packed weights use the first third of
  * its weight region).  A workspace packed for the other cell must be called
  * with weights_ready = 0.  The bounds are the GRU's: ZT_ERR_UNSUPPORTED for
- * D > 128 and for a message width whose staging tile needs more than 150 KB of
+ * D outside (D <= 128, or a multiple of 4 up to 256) and for a message width whose staging tile needs more than 150 KB of
  * LDS (128 * (round16(msg_dim) + round16(D) + 4) + 128 bytes, the same limit
  * zt_gru_update applies).  zt_set_kernel_choice(ZT_CHOICE_GRU, ZT_GRU_TILE /
  * ZT_GRU_SPLIT) pins the kernel form for both cells. */

@@ -27,6 +27,7 @@ namespace {
 
 constexpr int MAX_MT = 5;          // M-tiles (16 gathered rows each) per workgroup
 constexpr int MAX_MT_BIG = 16;     // ... of the instantiation for 80 < k <= 255 (k_fc1_agg<TAB, MAX_MT_BIG>)
+constexpr int MAX_MT_BIG_WIDE = 8; // ... of the one for 128 < D (k_fc1_agg<TAB, MAX_MT_BIG_WIDE, NTW_WIDE>: 80 < k <= 128)
 constexpr int LDS_BUDGET = 150 * 1024;
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -65,7 +66,9 @@ __global__ void k_pad_matrix(const float *__restrict__ W, int ld, int c0, int ro
 // MMT: M-tiles a workgroup can hold.  MAX_MT (5: 80 gathered rows) for every k <= 80; MAX_MT_BIG (16) is instantiated for
 // 80 < k <= 255 -- a query row of that many neighbours must still fit ONE workgroup's tile (dictionaries wider than a
 // wavefront: tppr_wide.hpp; correct first, not tuned).
-template <bool TAB, int MMT = MAX_MT>
+// NW: N-tiles of the hidden layer per wave.  NTW (Dp <= 128); NTW_WIDE for 128 < D <= 256, D % 4 == 0 (MMT <= MAX_MT_BIG_WIDE:
+// the accumulators of MMT x NW tiles stay at the MAX_MT_BIG instantiation's 128 registers).
+template <bool TAB, int MMT = MAX_MT, int NW = NTW>
 __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     const float *__restrict__ memory, const float *__restrict__ efeat, const float *__restrict__ time_w,
     long long num_nodes, long long num_edges, int D, int F, int T, long long N, int k, int rq, int mt_count, int lda,
@@ -86,14 +89,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     const int CM = TAB ? 0 : D;                                       // memory columns held in the tile
     const int K1 = CM + F + T;
     const size_t mb = ((size_t)m * N + q0) * k;                       // first entry of this tile in [M][N][k]
-    // ---- this wave's N-tiles {wave, wave+4}; weight fragments stream from L2 one chunk ahead of their MFMAs
+    // ---- this wave's N-tiles {wave, wave+4, ..}; weight fragments stream from L2 one chunk ahead of their MFMAs
     // ---- (keeping all of them in registers was measured: no gain, and it halves the occupancy)
     const int NT = (Dout + 15) / 16;
     const int r16 = lane & 15, g4 = lane >> 4;
-    const float *bp[NTW];
-    bool live[NTW];
+    const float *bp[NW];
+    bool live[NW];
 #pragma unroll
-    for (int b = 0; b < NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         const int nt = wave + b * AGG_WAVES;
         live[b] = nt < NT;
         bp[b] = W1p + (size_t)((live[b] ? nt : 0) * 16 + r16) * K1p + 4 * g4;
@@ -141,11 +144,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     AGG_STAMP(0);
     // accumulators: zero, or (TAB) the projected rows P[nbr[row]][col] -- issued before the staging below so that the
     // memory round trip is hidden behind it; the MFMAs then accumulate on top of them
-    f32x4 acc[MMT][NTW];
+    f32x4 acc[MMT][NW];
 #pragma unroll
     for (int a = 0; a < MMT; ++a)
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (TAB && a < mt_count && live[b]) {
                 const int col = (wave + b * AGG_WAVES) * 16 + r16;
@@ -344,16 +347,16 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     __syncthreads();
     AGG_STAMP(4);
 
-    // ---- fc1 on f32 MFMA: wave handles N-tiles {wave, wave+4}, all M-tiles ----
+    // ---- fc1 on f32 MFMA: wave handles N-tiles {wave, wave+4, ..}, all M-tiles ----
     {
         const int nchunk = K1p / 16;
-        f32x4 bcur[NTW], bnext[NTW];
+        f32x4 bcur[NW], bnext[NW];
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) bcur[b] = *reinterpret_cast<const f32x4 *>(bp[b]);
+        for (int b = 0; b < NW; ++b) bcur[b] = *reinterpret_cast<const f32x4 *>(bp[b]);
         for (int kc = 0; kc < nchunk; ++kc) {
             if (kc + 1 < nchunk) {
 #pragma unroll
-                for (int b = 0; b < NTW; ++b) bnext[b] = *reinterpret_cast<const f32x4 *>(bp[b] + 16 * (kc + 1));
+                for (int b = 0; b < NW; ++b) bnext[b] = *reinterpret_cast<const f32x4 *>(bp[b] + 16 * (kc + 1));
             }
             f32x4 av[MMT];
 #pragma unroll
@@ -366,11 +369,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
 #pragma unroll
                 for (int a = 0; a < MMT; ++a)
 #pragma unroll
-                    for (int b = 0; b < NTW; ++b)
+                    for (int b = 0; b < NW; ++b)
                         if (a < mt_count && live[b])
                             acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bcur[b][j], acc[a][b], 0, 0, 0);
 #pragma unroll
-            for (int b = 0; b < NTW; ++b) bcur[b] = bnext[b];
+            for (int b = 0; b < NW; ++b) bcur[b] = bnext[b];
         }
     }
     AGG_STAMP(5);
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     float *Hs = A;                               // [rows_p][ldh]
     const int ldh = NT * 16 + 1;
 #pragma unroll
-    for (int b = 0; b < NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         if (!live[b]) continue;
         const int col = (wave + b * AGG_WAVES) * 16 + r16;
         const float bias = col < Dout ? b1[col] : 0.f;
@@ -1203,6 +1206,7 @@ __global__ __launch_bounds__(AGG_THREADS, 1) void k_embed_out3(
 // [Dp][Dp]; columns >= D of P are zero).  rows == nullptr: every node; else the n rows listed (ids < 0 or
 // beyond *count are skipped): the rows a batch's GRU update / exchange has just rewritten.
 // ---------------------------------------------------------------------------
+template <int NW = NTW>
 __global__ __launch_bounds__(AGG_THREADS) void k_project_rows(const float *__restrict__ memory, long long num_nodes,
                                                               int D, const float *__restrict__ Wm_p,
                                                               const int *__restrict__ rows, const int *__restrict__ count,
@@ -1230,10 +1234,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_project_rows(const float *__res
         X[f] = (rid[g] >= 0 && c < D) ? memory[(size_t)rid[g] * D + c] : 0.f;
     }
     __syncthreads();
-    f32x4 acc[OUT_MT][NTW];
+    f32x4 acc[OUT_MT][NW];
     small_gemm(X, ldx, Wm_p, Dp, NT, wave, lane, acc);
 #pragma unroll
-    for (int b = 0; b < NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         const int col = (wave + b * AGG_WAVES) * 16 + r16;
         if (col >= Dp) continue;
 #pragma unroll
@@ -1282,11 +1286,12 @@ bool split_fits(int D, int F, int T, int k) { return k <= ZT_MAX_K_WIDE && fc1_a
 
 bool make_plan(int64_t N, int D, int F, int T, int M, int k, EmbedPlan &p)
 {
+    if (!width_supported(D)) return false;
     const int K1 = D + F + T;
     p.Dp = round_up(D, 16);
     p.K1p = round_up(K1, 16);
-    const bool big = k > MAX_MT * 16;           // the MAX_MT_BIG instantiation
-    const int max_mt = big ? MAX_MT_BIG : MAX_MT;
+    const bool big = k > MAX_MT * 16;           // the MAX_MT_BIG (wide D: MAX_MT_BIG_WIDE) instantiation
+    const int max_mt = big ? (p.Dp > 16 * NTW * AGG_WAVES ? MAX_MT_BIG_WIDE : MAX_MT_BIG) : MAX_MT;
     const bool full_ok = tile_shape(p.K1p, p.Dp, k, T, &p.lda, &p.mt, &p.rq, &p.lds, max_mt);
     // no tile for a query row with its memory columns: the table path's narrower tile (wide k), or the row split
     if (!full_ok) { p.mt = 0; p.rq = 1; p.lda = p.K1p + 4; p.lds = 0; }
@@ -1317,8 +1322,8 @@ KernelPlan plan_kernels(int64_t N, int D, int F, int T, int M, int k, bool have_
                         int out_choice, EmbedPlan &p)
 {
     KernelPlan kp{AggKernel::unsupported, OutForm::tiled, Refusal::shape, 0, 0, 0, 0, 1};
-    static_assert(16 * NTW * AGG_WAVES == 128, "the output layers' N-tiles cover D <= 128");
-    if (D > 128 || !make_plan(N, D, F, T, M, k, p)) return kp;
+    static_assert(16 * NTW * AGG_WAVES == 128 && 16 * NTW_WIDE * AGG_WAVES == MAX_D, "the N-tiles cover D <= 128 / D <= 256");
+    if (!make_plan(N, D, F, T, M, k, p)) return kp;
     const bool big = k > MAX_MT * 16;
     const bool tab = have_table && !training && p.mt2 > 0;
     // the reference's default widths take the specialised kernels (zt_set_kernel_choice(ZT_CHOICE_AGGREGATE, ZT_AGG_GENERIC): the generic one)
@@ -1398,6 +1403,14 @@ extern "C" int64_t zt_embed_workspace_bytes(int64_t N, int32_t D, int32_t F, int
     return (int64_t)p.total;
 }
 
+extern "C" int32_t zt_agg_train_supported(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k)
+{
+    if (N < 0 || D <= 0 || F < 0 || T < 0 || M <= 0 || k <= 0) return 0;
+    EmbedPlan p;
+    const KernelPlan kp = plan_kernels(N > 0 ? N : 1, D, F, T, M, k, false, true, 0, 0, p);
+    return kp.refusal == Refusal::none && agg_backward_supported(D, F, T, k) ? 1 : 0;
+}
+
 // pads every weight matrix into the workspace (once per weight change: zt_embed's weights_ready = 0)
 static void embed_prepare(const zt_embed_weights *wt, int D, int F, int T, const EmbedPlan &p, char *ws, hipStream_t s)
 {
@@ -1420,7 +1433,7 @@ static void embed_prepare(const zt_embed_weights *wt, int D, int F, int T, const
 const float *zt::embed_wm_ptr(void *embed_ws, int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k)
 {
     EmbedPlan p;
-    if (!embed_ws || D > 128 || !make_plan(N > 0 ? N : 1, D, F, T, M, k, p)) return nullptr;
+    if (!embed_ws || !make_plan(N > 0 ? N : 1, D, F, T, M, k, p)) return nullptr;
     return reinterpret_cast<const float *>(reinterpret_cast<char *>(embed_ws) + p.off_wm);
 }
 
@@ -1440,7 +1453,7 @@ extern "C" int zt_project_memory(const float *memory_dev, int64_t num_nodes, int
         return ZT_ERR_ARG;
     }
     EmbedPlan p;
-    if (D > 128 || !make_plan(ws_N > 0 ? ws_N : 1, D, F, T, ws_M, ws_k, p)) {
+    if (!make_plan(ws_N > 0 ? ws_N : 1, D, F, T, ws_M, ws_k, p)) {
         set_error("zt_project_memory: unsupported shape");
         return ZT_ERR_UNSUPPORTED;
     }
@@ -1450,7 +1463,8 @@ extern "C" int zt_project_memory(const float *memory_dev, int64_t num_nodes, int
     const long long n = rows_dev ? max_rows : num_nodes;
     if (n == 0) return ZT_OK;
     const size_t lds = (size_t)OUT_ROWS * (p.Dp + 4) * 4 + OUT_ROWS * 4;
-    k_project_rows<<<(unsigned)((n + OUT_ROWS - 1) / OUT_ROWS), AGG_THREADS, lds, s>>>(
+    const auto project = p.Dp > 16 * NTW * AGG_WAVES ? k_project_rows<NTW_WIDE> : k_project_rows<NTW>;
+    project<<<(unsigned)((n + OUT_ROWS - 1) / OUT_ROWS), AGG_THREADS, lds, s>>>(
         memory_dev, num_nodes, D, reinterpret_cast<const float *>(ws + p.off_wm), rows_dev, count_dev, n, table_dev);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
@@ -1478,8 +1492,8 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
     const KernelPlan kp = plan_kernels(N, D, F, T, M, k, proj_table_dev != nullptr, false, kernel_choice(ZT_CHOICE_AGGREGATE),
                                        kernel_choice(ZT_CHOICE_EMBED_OUT), p);
     if (kp.refusal == Refusal::shape) {
-        set_error("zt_embed: D=%d F=%d T=%d k=%d outside the supported shapes (D<=128, one query row of k "
-                  "neighbours must fit the %d KB LDS tile)", D, F, T, k, LDS_BUDGET / 1024);
+        set_error("zt_embed: D=%d F=%d T=%d k=%d outside the supported shapes (D <= 128, or a multiple of 4 up to %d; one query "
+                  "row of k neighbours must fit the %d KB LDS tile)", D, F, T, k, MAX_D, LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1504,6 +1518,7 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
         if (rc != ZT_OK) return rc;
     }
     const dim3 tile_grid((unsigned)(kp.rq > 0 ? (N + kp.rq - 1) / kp.rq : 0), (unsigned)M);
+    const bool wide = p.Dp > 16 * NTW * AGG_WAVES;     // the NTW_WIDE instantiations (128 < D <= 256)
     // k_fc1_agg over the plan's tile: `rows` is memory (row stride D) or the projected table (stride Dp)
     auto tiled = [&](decltype(&k_fc1_agg<false>) fn, const float *rows, int ld, size_t w_off, int Kp) {
         ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), kp.lds));
@@ -1552,10 +1567,17 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
             return ZT_OK;
         });
         break;
-    case AggKernel::tiled_table: rc = tiled(k_fc1_agg<true>, proj_table_dev, p.Dp, p.off_w1t, p.K2p); break;
-    case AggKernel::tiled_table_big: rc = tiled(k_fc1_agg<true, MAX_MT_BIG>, proj_table_dev, p.Dp, p.off_w1t, p.K2p); break;
-    case AggKernel::tiled_full: rc = tiled(k_fc1_agg<false>, memory_dev, D, p.off_w1p, p.K1p); break;
-    case AggKernel::tiled_full_big: rc = tiled(k_fc1_agg<false, MAX_MT_BIG>, memory_dev, D, p.off_w1p, p.K1p); break;
+    case AggKernel::tiled_table:
+        rc = tiled(wide ? k_fc1_agg<true, MAX_MT, NTW_WIDE> : k_fc1_agg<true>, proj_table_dev, p.Dp, p.off_w1t, p.K2p);
+        break;
+    case AggKernel::tiled_table_big:
+        rc = tiled(wide ? k_fc1_agg<true, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<true, MAX_MT_BIG>, proj_table_dev, p.Dp, p.off_w1t,
+                   p.K2p);
+        break;
+    case AggKernel::tiled_full: rc = tiled(wide ? k_fc1_agg<false, MAX_MT, NTW_WIDE> : k_fc1_agg<false>, memory_dev, D, p.off_w1p, p.K1p); break;
+    case AggKernel::tiled_full_big:
+        rc = tiled(wide ? k_fc1_agg<false, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<false, MAX_MT_BIG>, memory_dev, D, p.off_w1p, p.K1p);
+        break;
     case AggKernel::split:
         rc = fc1_agg_split_launch(memory_dev, nullptr, nullptr, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, M, k,
                                   nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_w1p), p.K1p,
@@ -1631,7 +1653,16 @@ int zt::embed_out_launch(const zt::embed_out_deferred &d, void *stream)
     } else {
         const size_t lds2 = (size_t)2 * OUT_ROWS * (Dp + 4) * 4 + OUT_ROWS * 4;
         const dim3 grid((unsigned)((E.N + OUT_ROWS - 1) / OUT_ROWS), (unsigned)(E.M + 1));
-        rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) { k_embed_out<HGV><<<grid, AGG_THREADS, lds2, s>>>(E); return ZT_OK; });
+        if (Dp > 16 * NTW * AGG_WAVES) {
+            // 128 < D <= 256: four N-tiles per wave, up to 66 KB of LDS (no partial-sum groups: k_fc1_agg_wide is D = 100 only)
+            rc = dispatch<1>(d.hg, [&](auto HGV) {
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_out<HGV, NTW_WIDE>), lds2));
+                k_embed_out<HGV, NTW_WIDE><<<grid, AGG_THREADS, lds2, s>>>(E);
+                return ZT_OK;
+            });
+        } else {
+            rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) { k_embed_out<HGV><<<grid, AGG_THREADS, lds2, s>>>(E); return ZT_OK; });
+        }
     }
     if (rc == ZT_ERR_UNSUPPORTED) set_error("zt_embed: %d partial-sum groups per row", d.hg);      // (no instantiation for it)
     if (rc != ZT_OK) return rc;
@@ -1708,12 +1739,13 @@ extern "C" int zt_agg_train_forward(const float *memory_dev, const float *overla
         return fc1_agg_split_launch(memory_dev, overlay_dev, row_map_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
                                     M, k, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b, H_dev, S_dev, status_dev, drop_p,
                                     drop_seed, s);
-    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg<false>), kp.lds));
+    const auto fwd = p.Dp > 16 * NTW * AGG_WAVES ? k_fc1_agg<false, MAX_MT, NTW_WIDE> : k_fc1_agg<false>;
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fwd), kp.lds));
     dim3 grid((unsigned)((N + kp.rq - 1) / kp.rq), (unsigned)M);
-    k_fc1_agg<false><<<grid, AGG_THREADS, kp.lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, k,
-                                                     kp.rq, kp.mt, kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b,
-                                                     H_dev, S_dev, status_dev, D, row_map_dev, overlay_dev, (unsigned)drop_seed,
-                                                     (unsigned)(drop_seed >> 32), zt::drop_threshold(drop_p), 1.f / (1.f - drop_p));
+    fwd<<<grid, AGG_THREADS, kp.lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, k,
+                                          kp.rq, kp.mt, kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b,
+                                          H_dev, S_dev, status_dev, D, row_map_dev, overlay_dev, (unsigned)drop_seed,
+                                          (unsigned)(drop_seed >> 32), zt::drop_threshold(drop_p), 1.f / (1.f - drop_p));
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

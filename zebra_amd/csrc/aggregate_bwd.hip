@@ -26,7 +26,10 @@ constexpr int BW_THREADS = 256;
 constexpr int BW_WAVES = 4;
 constexpr int BW_MT = 5;           // 16-row tiles of gathered rows per step (80 rows)
 constexpr int BW_NTW = 2;          // forward N-tiles per wave (D <= 128)
+constexpr int BW_NTW_WIDE = 4;     // ... of the instantiation for 128 < D <= 256 (D % 4 == 0)
 constexpr int BW_MAX_OT = 24;      // dW1 output tiles per wave and launch (96 accumulator registers)
+constexpr int BW_MT_WIDE = 3;      // ... the BW_NTW_WIDE instantiation: 48 rows per step, 12 dW1 tiles per wave (the accumulators of
+constexpr int BW_MAX_OT_WIDE = 12; // its forward recompute are four N-tiles wide: within the register file without scratch)
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -51,6 +54,7 @@ struct BwdArgs {
     float drop_inv;
 };
 
+template <int NW, int OT, int MT>  // forward N-tiles per wave, dW1 tiles per wave, 16-row tiles per step: BW_* or BW_*_WIDE
 __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -68,9 +72,9 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
     const int r16 = lane & 15, g4 = lane >> 4;
     const int NT = Dp / 16, KT = a.kt_hi - a.kt_lo;
     const int n_ot = NT * KT;                                   // 16x16 tiles of dW1 handled by this launch
-    f32x4 gw[BW_MAX_OT];                                        // this wave's dW1 tiles (tile t = wave + 4*q)
+    f32x4 gw[OT];                                        // this wave's dW1 tiles (tile t = wave + 4*q)
 #pragma unroll
-    for (int q = 0; q < BW_MAX_OT; ++q) gw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < OT; ++q) gw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     float gb = 0.f;                                             // db1[tid] (tid < Dp)
     for (int c = tid; c < T; c += BW_THREADS) tw[c] = a.time_w[c];
 
@@ -136,20 +140,20 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
             A[(size_t)g * lda + c] = v;
         }
         __syncthreads();
-        // ---- recompute pre = x W1^T (f32 MFMA; wave owns N-tiles {wave, wave+4}) ----
-        f32x4 acc[BW_MT][BW_NTW];
+        // ---- recompute pre = x W1^T (f32 MFMA; wave owns N-tiles {wave, wave+4, ..}) ----
+        f32x4 acc[MT][NW];
 #pragma unroll
-        for (int x = 0; x < BW_MT; ++x)
+        for (int x = 0; x < MT; ++x)
 #pragma unroll
-            for (int b = 0; b < BW_NTW; ++b) acc[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < NW; ++b) acc[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kc = 0; kc < K1p / 16; ++kc) {
-            f32x4 av[BW_MT], bv[BW_NTW];
+            f32x4 av[MT], bv[NW];
 #pragma unroll
-            for (int x = 0; x < BW_MT; ++x)
+            for (int x = 0; x < MT; ++x)
                 av[x] = x < mt ? *reinterpret_cast<const f32x4 *>(A + (size_t)(x * 16 + r16) * lda + 16 * kc + 4 * g4)
                                : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int b = 0; b < BW_NTW; ++b) {
+            for (int b = 0; b < NW; ++b) {
                 const int nt = wave + b * BW_WAVES;
                 bv[b] = nt < NT ? *reinterpret_cast<const f32x4 *>(a.W1p + (size_t)(nt * 16 + r16) * K1p + 16 * kc + 4 * g4)
                                 : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -157,20 +161,20 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int x = 0; x < BW_MT; ++x)
+                for (int x = 0; x < MT; ++x)
 #pragma unroll
-                    for (int b = 0; b < BW_NTW; ++b)
+                    for (int b = 0; b < NW; ++b)
                         if (x < mt) acc[x][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[x][j], bv[b][j], acc[x][b], 0, 0, 0);
         }
         // ---- dpre = w_k dH 1[pre > 0] into P ----
 #pragma unroll
-        for (int b = 0; b < BW_NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             const int nt = wave + b * BW_WAVES;
             if (nt >= NT) continue;
             const int col = nt * 16 + r16;
             const float bias = col < D ? a.b1[col] : 0.f;
 #pragma unroll
-            for (int x = 0; x < BW_MT; ++x)
+            for (int x = 0; x < MT; ++x)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (x >= mt) continue;
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         }
         // ---- dW1[i][c] += sum_g P[g][i] x[g][c]: tiles t = wave, wave+4, ...; tile t = (dt, kt) ----
 #pragma unroll
-        for (int q = 0; q < BW_MAX_OT; ++q) {
+        for (int q = 0; q < OT; ++q) {
             const int t = wave + q * BW_WAVES;
             if (t >= n_ot) break;
             const int dtile = t / KT, ktile = a.kt_lo + t - dtile * KT;
@@ -208,33 +212,33 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         }
         // ---- d_overlay[row][c] += sum_col P[g][col] W1[col][c]  (memory columns c < D only) ----
         if (a.first && a.row_map != nullptr) {
-            f32x4 dx[BW_MT][BW_NTW];
+            f32x4 dx[MT][NW];
 #pragma unroll
-            for (int x = 0; x < BW_MT; ++x)
+            for (int x = 0; x < MT; ++x)
 #pragma unroll
-                for (int b = 0; b < BW_NTW; ++b) dx[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int b = 0; b < NW; ++b) dx[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int s = 0; s < Dp / 4; ++s) {
                 const int col = 4 * s + g4;
-                float pa[BW_MT], wb[BW_NTW];
+                float pa[MT], wb[NW];
 #pragma unroll
-                for (int x = 0; x < BW_MT; ++x) pa[x] = x < mt ? P[(size_t)(x * 16 + r16) * ldp + col] : 0.f;   // [m = row g][k = col]
+                for (int x = 0; x < MT; ++x) pa[x] = x < mt ? P[(size_t)(x * 16 + r16) * ldp + col] : 0.f;   // [m = row g][k = col]
 #pragma unroll
-                for (int b = 0; b < BW_NTW; ++b) {
+                for (int b = 0; b < NW; ++b) {
                     const int c = (wave + b * BW_WAVES) * 16 + r16;
                     wb[b] = c < D ? a.W1p[(size_t)col * K1p + c] : 0.f;                           // [k = col][n = c]
                 }
 #pragma unroll
-                for (int x = 0; x < BW_MT; ++x)
+                for (int x = 0; x < MT; ++x)
 #pragma unroll
-                    for (int b = 0; b < BW_NTW; ++b)
+                    for (int b = 0; b < NW; ++b)
                         if (x < mt) dx[x][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[x], wb[b], dx[x][b], 0, 0, 0);
             }
 #pragma unroll
-            for (int b = 0; b < BW_NTW; ++b) {
+            for (int b = 0; b < NW; ++b) {
                 const int c = (wave + b * BW_WAVES) * 16 + r16;
                 if (c >= D) continue;
 #pragma unroll
-                for (int x = 0; x < BW_MT; ++x)
+                for (int x = 0; x < MT; ++x)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int g = x * 16 + g4 * 4 + j;
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
     }
     // ---- flush the accumulated weight gradient ----
 #pragma unroll
-    for (int q = 0; q < BW_MAX_OT; ++q) {
+    for (int q = 0; q < OT; ++q) {
         const int t = wave + q * BW_WAVES;
         if (t >= n_ot) break;
         const int dtile = t / KT, ktile = a.kt_lo + t - dtile * KT;
@@ -270,7 +274,38 @@ __global__ void k_pad(const float *__restrict__ W, int rows, int cols, float *__
     Wp[i] = (r < rows && c < cols) ? W[(size_t)r * cols + c] : 0.f;
 }
 
+// the backward's tile: as many whole query rows as fit max_mt 16-row tiles and 150 KB of LDS, else (a query row does not fit)
+// the row split: tiles of one chunk of max_mt (or as many as fit) 16-row tiles, nch chunks per row.  false: refused
+size_t bwd_lds(int mt, int K1p, int Dp, int T) { return ((size_t)mt * 16 * (K1p + 4 + Dp + 4) + (size_t)mt * 16 * 4 + T) * 4; }
+
+bool bwd_tile(int D, int F, int T, int k, int &mt, int &rq, int &nch)
+{
+    if (!zt::width_supported(D) || F < 0 || T < 0 || k <= 0) return false;
+    const int Dp = round_up(D, 16), K1p = round_up(D + F + T, 16);
+    const int max_mt = Dp > 16 * BW_NTW * BW_WAVES ? BW_MT_WIDE : BW_MT;
+    mt = max_mt;
+    while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > 150 * 1024) --mt;
+    rq = (mt * 16) / k;
+    if (rq < 1) { mt = (k + 15) / 16; rq = 1; }
+    nch = 0;
+    if ((mt > max_mt || bwd_lds(mt, K1p, Dp, T) > 150 * 1024) && k <= ZT_MAX_K_WIDE) {
+        mt = max_mt;
+        while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > 150 * 1024) --mt;
+        rq = 1;
+        nch = (k + mt * 16 - 1) / (mt * 16);
+    }
+    if (mt > max_mt || bwd_lds(mt, K1p, Dp, T) > 150 * 1024) return false;
+    if (nch == 0) mt = (rq * k + 15) / 16;
+    return true;
+}
+
 }  // namespace
+
+bool zt::agg_backward_supported(int D, int F, int T, int k)
+{
+    int mt, rq, nch;
+    return bwd_tile(D, F, T, k, mt, rq, nch);
+}
 
 extern "C" int64_t zt_agg_backward_workspace_bytes(int32_t D, int32_t F, int32_t T)
 {
@@ -294,25 +329,13 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     }
     if (N == 0) return ZT_OK;
     const int K1 = D + F + T, Dp = round_up(D, 16), K1p = round_up(K1, 16);
-    // tile: as many whole query rows as fit BW_MT 16-row tiles and 150 KB of LDS
-    int mt = BW_MT;
-    auto lds_of = [&](int t) { return ((size_t)t * 16 * (K1p + 4 + Dp + 4) + (size_t)t * 16 * 4 + T) * 4; };
-    while (mt > 1 && lds_of(mt) > 150 * 1024) --mt;
-    int rq = (mt * 16) / k;
-    if (rq < 1) { mt = (k + 15) / 16; rq = 1; }
-    int nch = 0;
-    if (D <= 128 && (mt > BW_MT || lds_of(mt) > 150 * 1024) && k <= ZT_MAX_K_WIDE) {
-        // a query row does not fit one tile: row split, tiles of one chunk of BW_MT (or as many as fit) 16-row tiles
-        mt = BW_MT;
-        while (mt > 1 && lds_of(mt) > 150 * 1024) --mt;
-        rq = 1;
-        nch = (k + mt * 16 - 1) / (mt * 16);
-    }
-    if (D > 128 || mt > BW_MT || lds_of(mt) > 150 * 1024) {
-        set_error("zt_agg_train_backward: D=%d F=%d T=%d k=%d outside the supported shapes", D, F, T, k);
+    const bool wide = Dp > 16 * BW_NTW * BW_WAVES;
+    int mt, rq, nch;
+    if (!bwd_tile(D, F, T, k, mt, rq, nch)) {
+        set_error("zt_agg_train_backward: D=%d F=%d T=%d k=%d outside the supported shapes (D <= 128, or a multiple of 4 up to %d)",
+                  D, F, T, k, zt::MAX_D);
         return ZT_ERR_UNSUPPORTED;
     }
-    if (nch == 0) mt = (rq * k + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
     float *W1p = reinterpret_cast<float *>(workspace_dev);
     k_pad<<<(Dp * K1p + 255) / 256, 256, 0, s>>>(fc1_w_dev, D, K1, W1p, Dp, K1p);
@@ -328,21 +351,23 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     a.n_tiles = nch > 0 ? N * nch : (N + rq - 1) / rq;
     a.mt = mt;
     a.nch = nch;
-    const size_t lds = lds_of(mt);
-    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_bwd), lds));
+    const size_t lds = bwd_lds(mt, K1p, Dp, T);
+    const auto fn = wide ? k_fc1_agg_bwd<BW_NTW_WIDE, BW_MAX_OT_WIDE, BW_MT_WIDE> : k_fc1_agg_bwd<BW_NTW, BW_MAX_OT, BW_MT>;
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), lds));
     hipDeviceProp_t prop;
     int dev = 0;
     ZT_HIP(hipGetDevice(&dev));
     ZT_HIP(hipGetDeviceProperties(&prop, dev));
     long long grid = a.n_tiles * M;
     if (grid > prop.multiProcessorCount) grid = prop.multiProcessorCount;      // persistent: one weight-gradient flush per CU
-    // the weight gradient of one launch lives in registers: BW_MAX_OT tiles per wave.  Wide inputs (F = 172)
-    // take several launches over windows of input columns (the recompute is repeated, db1 / d_overlay are not).
+    // the weight gradient of one launch lives in registers: BW_MAX_OT (wide D: BW_MAX_OT_WIDE) tiles per wave.  Wide inputs
+    // (F = 172; D > 128: at D = 256, windows of 3 column tiles) take several launches over windows of input columns (the
+    // recompute is repeated, db1 / d_overlay are not).
     const int NT = Dp / 16, KT = K1p / 16;
-    const int win = (BW_MAX_OT * BW_WAVES) / NT;
+    const int win = ((wide ? BW_MAX_OT_WIDE : BW_MAX_OT) * BW_WAVES) / NT;
     for (int lo = 0; lo < KT; lo += win) {
         a.kt_lo = lo; a.kt_hi = lo + win < KT ? lo + win : KT; a.first = lo == 0 ? 1 : 0;
-        k_fc1_agg_bwd<<<(unsigned)grid, BW_THREADS, lds, s>>>(a);
+        fn<<<(unsigned)grid, BW_THREADS, lds, s>>>(a);
     }
     ZT_LAUNCH_CHECK();
     return ZT_OK;

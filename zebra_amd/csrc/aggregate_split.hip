@@ -12,7 +12,7 @@
 // LDS: the chunk tile [cr][K1p + 4] floats + the row's staged ids / dt / weights (4 x 256 words) + the frequencies.
 // D = T = 100, F = 172: K1p = 384, 80 rows x 388 floats = 124 KB + 4.4 KB (one workgroup per CU); F = 1: 68 KB.
 #include "common.hpp"
-#include "embed_out_body.hpp"     // f32x4, AGG_THREADS / AGG_WAVES / NTW
+#include "embed_out_body.hpp"     // f32x4, AGG_THREADS / AGG_WAVES / NTW / NTW_WIDE
 
 using namespace zt;
 
@@ -28,6 +28,8 @@ __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m *
 
 size_t split_lds(int lda, int mt, int T) { return ((size_t)mt * 16 * lda + 4 * SPLIT_KMAX + T + 4) * 4; }
 
+// NW: N-tiles of the hidden layer per wave (NTW: D <= 128; NTW_WIDE: 128 < D <= 256)
+template <int NW>
 __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
     const float *__restrict__ memory, const float *__restrict__ overlay, const int *__restrict__ row_map,
     const float *__restrict__ efeat, const float *__restrict__ time_w, long long num_nodes, long long num_edges, int D,
@@ -77,10 +79,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
         if (tid < k) wn[tid] = (s == 0.f) ? 0.f : wn[tid] / s;
     }
 
-    const float *bp[NTW];
-    bool live[NTW];
+    const float *bp[NW];
+    bool live[NW];
 #pragma unroll
-    for (int b = 0; b < NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         const int nt = wave + b * AGG_WAVES;
         live[b] = nt < NT;
         bp[b] = W1p + (size_t)((live[b] ? nt : 0) * 16 + r16) * K1p + 4 * g4;
@@ -132,21 +134,21 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
         }
         __syncthreads();
 
-        // ---- fc1 on f32 MFMA: wave handles N-tiles {wave, wave+4}, all M-tiles of the chunk ----
-        f32x4 acc[SPLIT_MT][NTW];
+        // ---- fc1 on f32 MFMA: wave handles N-tiles {wave, wave+4, ..}, all M-tiles of the chunk ----
+        f32x4 acc[SPLIT_MT][NW];
 #pragma unroll
         for (int a = 0; a < SPLIT_MT; ++a)
 #pragma unroll
-            for (int b = 0; b < NTW; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < NW; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
         {
             const int nchunk = K1p / 16;
-            f32x4 bcur[NTW], bnext[NTW];
+            f32x4 bcur[NW], bnext[NW];
 #pragma unroll
-            for (int b = 0; b < NTW; ++b) bcur[b] = *reinterpret_cast<const f32x4 *>(bp[b]);
+            for (int b = 0; b < NW; ++b) bcur[b] = *reinterpret_cast<const f32x4 *>(bp[b]);
             for (int kc = 0; kc < nchunk; ++kc) {
                 if (kc + 1 < nchunk) {
 #pragma unroll
-                    for (int b = 0; b < NTW; ++b) bnext[b] = *reinterpret_cast<const f32x4 *>(bp[b] + 16 * (kc + 1));
+                    for (int b = 0; b < NW; ++b) bnext[b] = *reinterpret_cast<const f32x4 *>(bp[b] + 16 * (kc + 1));
                 }
                 f32x4 av[SPLIT_MT];
 #pragma unroll
@@ -158,11 +160,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
 #pragma unroll
                     for (int a = 0; a < SPLIT_MT; ++a)
 #pragma unroll
-                        for (int b = 0; b < NTW; ++b)
+                        for (int b = 0; b < NW; ++b)
                             if (a < mt && live[b])
                                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bcur[b][j], acc[a][b], 0, 0, 0);
 #pragma unroll
-                for (int b = 0; b < NTW; ++b) bcur[b] = bnext[b];
+                for (int b = 0; b < NW; ++b) bcur[b] = bnext[b];
             }
         }
         __syncthreads();   // every wave is done reading the A tile: reuse it for the hidden rows
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
         // ---- bias + ReLU + dropout + weight, staged as Hs[g][col] in the A region ----
         float *Hs = A;
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             if (!live[b]) continue;
             const int col = (wave + b * AGG_WAVES) * 16 + r16;
             const float bias = col < D ? b1[col] : 0.f;
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_split(
 // rows of one chunk (a multiple of 16, at most SPLIT_MT * 16); 0: not even one 16-row tile fits the LDS budget
 int zt::fc1_agg_split_rows(int D, int F, int T)
 {
-    if (D <= 0 || D > 16 * NTW * AGG_WAVES || F < 0 || T < 0) return 0;
+    if (!width_supported(D) || F < 0 || T < 0) return 0;
     const int lda = round_up(D + F + T, 16) + 4;
     for (int mt = SPLIT_MT; mt >= 1; --mt)
         if (split_lds(lda, mt, T) <= (size_t)SPLIT_LDS_BUDGET) return mt * 16;
@@ -223,19 +225,20 @@ int zt::fc1_agg_split_launch(const float *memory, const float *overlay, const in
 {
     const int cr = fc1_agg_split_rows(D, F, T);
     if (cr == 0 || k <= 0 || k > ZT_MAX_K_WIDE || K1p != round_up(D + F + T, 16) || N > 0x7fffffffLL || M > 65535) {
-        set_error("row-split aggregation: D=%d F=%d T=%d k=%d M=%d unsupported (k <= %d, one 16-row chunk within %d KB of LDS)",
-                  D, F, T, k, M, ZT_MAX_K_WIDE, SPLIT_LDS_BUDGET / 1024);
+        set_error("row-split aggregation: D=%d F=%d T=%d k=%d M=%d unsupported (D <= 128 or a multiple of 4 up to %d, k <= %d, one "
+                  "16-row chunk within %d KB of LDS)", D, F, T, k, M, MAX_D, ZT_MAX_K_WIDE, SPLIT_LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     if (N == 0) return ZT_OK;
     const size_t lds = fc1_agg_split_lds(D, F, T);
-    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_fc1_agg_split), lds));
+    const auto fn = D > 16 * NTW * AGG_WAVES ? k_fc1_agg_split<NTW_WIDE> : k_fc1_agg_split<NTW>;
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), lds));
     const unsigned thr = drop_threshold(drop_p);
     dim3 grid((unsigned)N, (unsigned)M);
-    k_fc1_agg_split<<<grid, AGG_THREADS, lds, s>>>(memory, overlay, row_map, efeat, time_w, num_nodes, num_edges, D, F, T, N, k,
-                                                   cr / 16, K1p + 4, nbr, eix, dt, w, W1p, K1p, b1, H, S, status,
-                                                   (unsigned)drop_seed, (unsigned)(drop_seed >> 32), thr,
-                                                   thr ? 1.f / (1.f - drop_p) : 1.f);
+    fn<<<grid, AGG_THREADS, lds, s>>>(memory, overlay, row_map, efeat, time_w, num_nodes, num_edges, D, F, T, N, k,
+                                      cr / 16, K1p + 4, nbr, eix, dt, w, W1p, K1p, b1, H, S, status,
+                                      (unsigned)drop_seed, (unsigned)(drop_seed >> 32), thr,
+                                      thr ? 1.f / (1.f - drop_p) : 1.f);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

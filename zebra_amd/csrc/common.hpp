@@ -157,6 +157,8 @@ int fc1_agg_wide_launch(const float *P, const float *efeat, const float *time_w,
 // the row-split aggregation (aggregate_split.hip): one workgroup per (model, query row), the k gathered rows in chunks --
 // zt_agg_train_forward beyond one tile and zt_embed where no tile holds a query row.  rows: 0 = unsupported widths
 int fc1_agg_split_rows(int D, int F, int T);
+// zt_agg_train_backward takes (D, F, T, k) (aggregate_bwd.hip)
+bool agg_backward_supported(int D, int F, int T, int k);
 size_t fc1_agg_split_lds(int D, int F, int T);
 int fc1_agg_split_launch(const float *memory, const float *overlay, const int *row_map, const float *efeat,
                          const float *time_w, long long num_nodes, long long num_edges, int D, int F, int T, long long N,
@@ -174,6 +176,10 @@ int exchange_step(zt_exchange *x, const int32_t *rows_dev, const int32_t *count_
                   int64_t *n_ids_out);
 void exchange_shape(const zt_exchange *x, int *rank, int *world);
 constexpr int TPPR_MAX_LAUNCH = 16384;     // edges one T-PPR launch can cover (tppr_stream.hip: MAX_CHUNK)
+// The memory / embedding widths the dense kernels take: D <= 128 (two N-tiles per wave of four, one per wave of eight), or
+// 128 < D <= 256 with D % 4 == 0 (their wide instantiations move memory rows as 16-byte vectors)
+constexpr int MAX_D = 256;
+inline bool width_supported(int D) { return D > 0 && (D <= 128 || (D <= MAX_D && D % 4 == 0)); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of kernel fn raised to `bytes` where that is above 48 KB and above what was set
 // for fn before (runtime.hip)

@@ -20,12 +20,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int AGG_THREADS = 256;
 constexpr int AGG_WAVES = 4;
 constexpr int NTW = 2;             // N-tiles per wave -> D <= 128
+constexpr int NTW_WIDE = 4;        // ... of the instantiations for 128 < D <= 256 (D % 4 == 0)
 
 // ---------------------------------------------------------------------------
 // out[n] = [ fc2s(relu(fc1s(memory[nodes[n]]))) | fc2(H_0[n]) + b2*S_0[n] | ... ]
 // Three small D x D layers on f32 MFMA.  One workgroup per 32 rows; the input
 // rows sit in LDS, weights ([Dp][Dp], zero padded) stream from L2 as b128
-// fragments; wave w owns output N-tiles {w, w+4}.
+// fragments; wave w owns output N-tiles {w, w+4} (NW = NTW_WIDE: {w, w+4, w+8, w+12}).
 // ---------------------------------------------------------------------------
 constexpr int OUT_ROWS = 32;
 constexpr int OUT_MT = OUT_ROWS / 16;
@@ -33,23 +34,24 @@ constexpr int SG_CH = 8;             // k-steps of weight fragments in flight (s
 constexpr int EO_GU = 8;             // staged elements in flight per thread (k_embed_out)
 
 // acc[a][b] = X[a-th 16 rows] * W[b-th owned N-tile]^T   (X in LDS [32][ldx], W padded [Dp][Dp])
+template <int NW>
 __device__ __forceinline__ void small_gemm(const float *X, int ldx, const float *__restrict__ Wp, int Dp, int NT,
-                                           int wave, int lane, f32x4 (&acc)[OUT_MT][NTW])
+                                           int wave, int lane, f32x4 (&acc)[OUT_MT][NW])
 {
     const int r16 = lane & 15, g4 = lane >> 4;
 #pragma unroll
     for (int a = 0; a < OUT_MT; ++a)
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < NW; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     // The weight fragments of SG_CH k-steps are fetched together, before the first MFMA that needs one: a
     // workgroup has one tile of 32 rows, so nothing else hides the L2 round trip of a load issued per k-step.
     const int KC = Dp / 16;
     for (int kc0 = 0; kc0 < KC; kc0 += SG_CH) {
-        f32x4 bv[SG_CH][NTW];
+        f32x4 bv[SG_CH][NW];
 #pragma unroll
         for (int c = 0; c < SG_CH; ++c)
 #pragma unroll
-            for (int b = 0; b < NTW; ++b) {
+            for (int b = 0; b < NW; ++b) {
                 const int nt = wave + b * AGG_WAVES;
                 bv[c][b] = (kc0 + c < KC && nt < NT)
                                ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)(nt * 16 + r16) * Dp + 16 * (kc0 + c) + 4 * g4)
@@ -63,7 +65,7 @@ __device__ __forceinline__ void small_gemm(const float *X, int ldx, const float 
             for (int a = 0; a < OUT_MT; ++a)
                 av[a] = *reinterpret_cast<const f32x4 *>(X + (size_t)(a * 16 + r16) * ldx + 16 * (kc0 + c) + 4 * g4);
 #pragma unroll
-            for (int b = 0; b < NTW; ++b) {
+            for (int b = 0; b < NW; ++b) {
                 if (wave + b * AGG_WAVES >= NT) continue;
 #pragma unroll
                 for (int a = 0; a < OUT_MT; ++a)
@@ -80,7 +82,8 @@ using zt::EmbedOutArgs;          // (common.hpp)
 // bx = 32-row tile, path = 0 (source path) or 1 + model; the first AGG_THREADS threads of the workgroup.  src_read != nullptr:
 // a source-path workgroup adds 1 there once its memory rows are in LDS (k_out_gru: the GRU half waits for all of them before
 // it writes the table).
-template <int HG>                    // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
+// NW: N-tiles per wave (NTW: Dp <= 128; NTW_WIDE: Dp <= 256)
+template <int HG, int NW = NTW>      // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
 __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem, int bx, int path, int *src_read)
 {
     const float *__restrict__ memory = E.memory;
@@ -101,7 +104,7 @@ __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem
     const int nr = (int)((N - r0) < OUT_ROWS ? (N - r0) : OUT_ROWS);
     const int OW = D * (M + 1);
     const unsigned mL = fastdiv_magic((unsigned)ldx);
-    f32x4 acc[OUT_MT][NTW];
+    f32x4 acc[OUT_MT][NW];
 
     // blockIdx.y = 0: the source path (two dependent layers); 1 + m: fc2 of model m.  The paths are independent,
     // and the kernel's time is the latency of ONE workgroup (there are fewer workgroups than the chip holds).
@@ -133,7 +136,7 @@ __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem
         if (src_read != nullptr && tid == 0) atomicAdd(src_read, 1);      // (the rows are in LDS: every load has returned)
         small_gemm(X, ldx, fc1s_p, Dp, NT, wave, lane, acc);
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             const int col = (wave + b * AGG_WAVES) * 16 + r16;
             if (col >= Dp) continue;
             const float bias = col < D ? fc1s_b[col] : 0.f;
@@ -148,7 +151,7 @@ __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem
         __syncthreads();
         small_gemm(Y, ldx, fc2s_p, Dp, NT, wave, lane, acc);
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             const int col = (wave + b * AGG_WAVES) * 16 + r16;
             if (col >= D) continue;
             const float bias = fc2s_b[col];
@@ -187,7 +190,7 @@ __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem
         __syncthreads();
         small_gemm(X, ldx, fc2_p, Dp, NT, wave, lane, acc);
 #pragma unroll
-        for (int b = 0; b < NTW; ++b) {
+        for (int b = 0; b < NW; ++b) {
             const int col = (wave + b * AGG_WAVES) * 16 + r16;
             if (col >= D) continue;
             const float bias = fc2_b[col];
@@ -204,11 +207,11 @@ __device__ __forceinline__ void embed_out_body(const EmbedOutArgs &E, char *smem
     }
 }
 
-template <int HG>
+template <int HG, int NW = NTW>
 __global__ __launch_bounds__(AGG_THREADS) void k_embed_out(EmbedOutArgs E)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    embed_out_body<HG>(E, smem, blockIdx.x, blockIdx.y, nullptr);
+    embed_out_body<HG, NW>(E, smem, blockIdx.x, blockIdx.y, nullptr);
 }
 
 // ---------------------------------------------------------------------------

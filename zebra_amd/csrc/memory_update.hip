@@ -194,6 +194,7 @@ __global__ void k_select_flagged(const int *__restrict__ ids, long long n_ids, c
 // win over weight-fragment reuse -- also at C5's 8 192 rows (512 tiles, each streaming the 686 KB of gate weights from L2:
 // 32-row tiles, k_gru<2>, measured slower and removed)
 constexpr int GRU_NTW = 1;     // hidden N-tiles per wave; 8 waves -> D <= 128
+constexpr int GRU_NTW_WIDE = 2; // ... of the instantiations for 128 < D <= 256 (the tile keeps every column of its 16 rows)
 constexpr int GRU_WAVES = 8;
 constexpr int GRU_CH = 6;      // k-steps of weight fragments in flight
 constexpr int GRU_SRC_WORD = 32; // words 32, 33 of the workspace's counter block: the gate of k_out_gru / k_out_gru2 (SrcGate)
@@ -278,7 +279,8 @@ struct GruArgs {
 // bid = the workgroup's 16-row tile.  gate != nullptr (k_out_gru): before a row of the memory table is written every
 // source-path workgroup of the output layers must have its rows in LDS (SrcGate; LDS: one word more behind the node ids).
 // CELL_RNN: one gate -- the message part and the memory part in accumulators of their own (ani, anh), added after the biases.
-template <int CELL>
+// NW: hidden N-tiles per wave ({wave, wave + 8, ..}); GRU_NTW_WIDE fetches half as many k-steps of fragments at a time.
+template <int CELL, int NW = GRU_NTW>
 __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, const SrcGate *gate)
 {
     float *memory = G.memory, *last_update = G.last_update;
@@ -341,29 +343,30 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     const int NT = (D + 15) / 16;
     const int r16 = lane & 15, g4 = lane >> 4;
     // per n-tile: r, z (message + memory), n_i (message), n_h (memory)
-    f32x4 ar[GRU_NTW], az[GRU_NTW], ani[GRU_NTW], anh[GRU_NTW];
+    f32x4 ar[NW], az[NW], ani[NW], anh[NW];
 #pragma unroll
-    for (int b = 0; b < GRU_NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         ar[b] = f32x4{0.f, 0.f, 0.f, 0.f}; az[b] = ar[b]; ani[b] = ar[b]; anh[b] = ar[b];
     }
-    bool live[GRU_NTW];
-    int colrow[GRU_NTW];
+    bool live[NW];
+    int colrow[NW];
 #pragma unroll
-    for (int b = 0; b < GRU_NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         const int nt = wave + b * GRU_WAVES;
         live[b] = nt < NT;
         colrow[b] = (live[b] ? nt : 0) * 16 + r16;
     }
     // Both parts stream their weight fragments from L2; GRU_CH k-steps are fetched together so that one
     // round trip is paid per chunk rather than per k-step (a workgroup owns one tile, nothing else hides it).
+    constexpr int CH = GRU_CH / NW;
     auto part = [&](const float *__restrict__ Wp, int Kp, int a_off, bool hidden) {
         const int KC = Kp / 16;
-        for (int kc0 = 0; kc0 < KC; kc0 += GRU_CH) {
-            f32x4 wr[GRU_CH][GRU_NTW], wz[GRU_CH][GRU_NTW], wn[GRU_CH][GRU_NTW];
+        for (int kc0 = 0; kc0 < KC; kc0 += CH) {
+            f32x4 wr[CH][NW], wz[CH][NW], wn[CH][NW];
 #pragma unroll
-            for (int c = 0; c < GRU_CH; ++c)
+            for (int c = 0; c < CH; ++c)
 #pragma unroll
-                for (int b = 0; b < GRU_NTW; ++b) {
+                for (int b = 0; b < NW; ++b) {
                     const bool on = live[b] && kc0 + c < KC;
                     const size_t o = (((size_t)(colrow[b] >> 4) * KC + (on ? kc0 + c : 0)) * 64 + lane) * 4;       // (fragment order: k_pack_gates)
                     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -376,11 +379,11 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
                     }
                 }
 #pragma unroll
-            for (int c = 0; c < GRU_CH; ++c) {
+            for (int c = 0; c < CH; ++c) {
                 if (kc0 + c >= KC) break;
                 const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)r16 * lda + a_off + 16 * (kc0 + c) + 4 * g4);
 #pragma unroll
-                for (int b = 0; b < GRU_NTW; ++b) {
+                for (int b = 0; b < NW; ++b) {
                     if (!live[b]) continue;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -407,7 +410,7 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     // gates (torch.nn.GRUCell): r,z = sigmoid(gi+gh); n = tanh(gi_n + r*gh_n); h' = (1-z)*n + z*h
     // (torch.nn.RNNCell: h' = tanh((gi + b_ih) + (gh + b_hh)))
 #pragma unroll
-    for (int b = 0; b < GRU_NTW; ++b) {
+    for (int b = 0; b < NW; ++b) {
         if (!live[b]) continue;
         const int col = (wave + b * GRU_WAVES) * 16 + r16;
         if (col >= D) continue;
@@ -446,35 +449,43 @@ __device__ __forceinline__ void gru_body(const GruArgs &G, char *smem, int bid, 
     // ---- here from the new rows while they are still in LDS: one kernel and one pass over the rows less per step
     if (P != nullptr) {
         __syncthreads();                              // every column of the new rows is in the tile
-        if (wave < Hp / 16) {                         // wave w: output columns 16 w .. 16 w + 15
-            const int KC = Hp / 16;                   // <= 8 (D <= 128)
-            f32x4 wv[8];
 #pragma unroll
-            for (int c = 0; c < 8; ++c)
-                wv[c] = c < KC ? *reinterpret_cast<const f32x4 *>(Wm_p + (size_t)(wave * 16 + r16) * Hp + 16 * c + 4 * g4)
-                               : f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < NW; ++b) {
+            const int nt = wave + b * GRU_WAVES;
+            if (nt < Hp / 16) {                           // wave w: output columns 16 nt .. 16 nt + 15
+                const int KC = Hp / 16;                   // <= 8 NW
+                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                if (c >= KC) break;
-                const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)r16 * lda + Xp + 16 * c + 4 * g4);
+                for (int h = 0; h < NW; ++h) {            // eight k-chunks of fragments at a time
+                    f32x4 wv[8];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv[c][j], acc, 0, 0, 0);
-            }
+                    for (int c = 0; c < 8; ++c)
+                        wv[c] = 8 * h + c < KC
+                                    ? *reinterpret_cast<const f32x4 *>(Wm_p + (size_t)(nt * 16 + r16) * Hp + 16 * (8 * h + c) + 4 * g4)
+                                    : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int g = g4 * 4 + j;
-                if (g < nr) P[(size_t)rid[g] * Hp + wave * 16 + r16] = acc[j];
+                    for (int c = 0; c < 8; ++c) {
+                        if (8 * h + c >= KC) break;
+                        const f32x4 av = *reinterpret_cast<const f32x4 *>(A + (size_t)r16 * lda + Xp + 16 * (8 * h + c) + 4 * g4);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], wv[c][j], acc, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int g = g4 * 4 + j;
+                    if (g < nr) P[(size_t)rid[g] * Hp + nt * 16 + r16] = acc[j];
+                }
             }
         }
     }
 }
 
-template <int CELL>
+template <int CELL, int NW = GRU_NTW>
 __global__ __launch_bounds__(64 * GRU_WAVES) void k_gru(GruArgs G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gru_body<CELL>(G, smem, blockIdx.x, nullptr);
+    gru_body<CELL, NW>(G, smem, blockIdx.x, nullptr);
 }
 
 // The output layers and the GRU update in ONE launch (round 5).  The two kernels are independent but for the memory rows the
@@ -917,12 +928,14 @@ MemoryPlan zt::memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, i
     mp.msg = message_kernel(D, F, T, msg_choice);
     mp.out = held.present ? OutLaunch::front : OutLaunch::none;         // (a refused or empty update: launched on the way out)
     if (D <= 0 || msg_dim <= 0) { mp.refusal = MemRefusal::arg; return mp; }
-    if (D > 128) { mp.refusal = MemRefusal::d_large; return mp; }
+    if (!width_supported(D)) { mp.refusal = MemRefusal::d_large; return mp; }
     if (max_rows == 0) return mp;
     if (msg_dim > GRU_MAX_XH - round_up(D, 16)) { mp.refusal = MemRefusal::msg_wide; return mp; }
     GruPlan p;
     gru_plan(max_rows, D, msg_dim, p);
-    const bool hg_ok = held.hg == 1 || held.hg == 5 || held.hg == 10;
+    // (fused forms: D <= 128 only -- wider held-back output layers go in front of the GRU kernel)
+    const bool hg_ok = (held.hg == 1 || held.hg == 5 || held.hg == 10) && p.Hp <= 16 * GRU_NTW * GRU_WAVES &&
+                       round_up(held.D, 16) <= 16 * NTW * AGG_WAVES;
     const bool fits = max_rows <= GS_MAX_ROWS && (p.Xp + p.Hp) / 16 <= GS_WAVES * GS_MAXCH && 16 * (msg_dim + D) <= GS_STAGE * 256 &&
                       16 * p.Hp <= 7 * 256;
     mp.gru_tiles = (int)((max_rows + 15) / 16);
@@ -987,7 +1000,7 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
     switch (mp.refusal) {
     case MemRefusal::none: break;
     case MemRefusal::arg: set_error("%s: bad argument", name); return ZT_ERR_ARG;
-    case MemRefusal::d_large: set_error("%s: D=%d > 128 unsupported", name, D); return ZT_ERR_UNSUPPORTED;
+    case MemRefusal::d_large: set_error("%s: D=%d unsupported (D <= 128, or a multiple of 4 up to %d)", name, D, MAX_D); return ZT_ERR_UNSUPPORTED;
     case MemRefusal::msg_wide: set_error("%s: message width %d too large", name, msg_dim); return ZT_ERR_UNSUPPORTED;
     }
     if (mp.gru == GruForm::none) return ZT_OK;                           // no rows
@@ -1044,8 +1057,10 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
                 ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split<CELL>), mp.lds2));
                 k_gru_split<CELL><<<dim3(mp.grid, (unsigned)mp.NTg), 64 * GS_WAVES, mp.lds2, s>>>(GS);
             } else {
-                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru<CELL>), mp.lds));
-                k_gru<CELL><<<mp.grid, 64 * GRU_WAVES, mp.lds, s>>>(G);
+                // (128 < D: two hidden N-tiles per wave -- one workgroup still owns every column of its 16 rows)
+                const auto fn = mp.NTg > GRU_NTW * GRU_WAVES ? k_gru<CELL, GRU_NTW_WIDE> : k_gru<CELL>;
+                ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), mp.lds));
+                fn<<<mp.grid, 64 * GRU_WAVES, mp.lds, s>>>(G);
             }
             return ZT_OK;
         }

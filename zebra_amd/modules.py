@@ -605,6 +605,12 @@ class GraphDiffusionEmbedding(nn.Module):
                                       stream_ptr()), "zt_project_memory")
         self._ws_key = key
 
+    def fused_training_supported(self, N):
+        """Whether the fused HIP training kernels take this module's shape for N output rows."""
+        return lib().zt_agg_train_supported(C.c_int64(max(1, N)), C.c_int32(self.embedding_dimension),
+                                            C.c_int32(self.n_edge_features), C.c_int32(self.n_time_features),
+                                            C.c_int32(self.n_tppr), C.c_int32(self.k)) == 1
+
     def invalidate_projection(self):
         """For callers that write the memory table or fc1's weights behind torch's back (raw pointers): the
         projected table is rebuilt at its next use."""
@@ -734,7 +740,9 @@ class GraphDiffusionEmbedding(nn.Module):
                                           self.fc2_source.weight, self.fc2_source.bias)
         else:
             embeddings = self.transform_source(src_rows)
-        fused = getattr(self, "fused_training", True) and self.embedding_dimension <= 128
+        # the fused kernels where the library takes the training shape (zt_agg_train_supported: D <= 128, or a multiple of 4
+        # up to 256; k <= ZT_MAX_K_WIDE), else the torch composition below
+        fused = getattr(self, "fused_training", True) and self.fused_training_supported(nodes_d.numel())
         if fused:
             # the dropout of the hidden layer (self.drop, active in train mode) runs inside the kernels: a seed from
             # torch's CPU generator (reproducible under torch.manual_seed), the mask is never materialised
