@@ -386,15 +386,23 @@ __device__ __forceinline__ int mbcnt64(u64 m)      // bits of m below this lane
 // Exact top-k when ties decide (n <= 64, no NaN): numba's quicksort replayed on the value RANKS
 // (`lt` from topk_rank_reg), one segment at a time with everything about the segment in scalar
 // registers.  Lane p is position p and holds e = (rank << 8) | candidate.  Per partition: three
-// scalar lane reads + scalar compares for the median of three, two ballots for the scan stops, one
-// LDS round trip to pair the m-th i-stop with the m-th j-stop, one cross-lane permute for all the
-// swaps, scalar lane writes for the pivot.  Segments that lie wholly below the cut n-k are neither
-// partitioned nor ordered (partitions of disjoint ranges are independent).  Finished segments
-// (< 16 entries) get the stable rank = insertion sort with strict <.  Writes sel[0..k).
+// scalar lane reads + scalar compares for the median of three, two ballots for the scan stops, two
+// cross-lane permutes for all the swaps, scalar lane writes for the pivot.  Segments that lie wholly
+// below the cut n-k are neither partitioned nor ordered (partitions of disjoint ranges are independent).
+//
+// Finished segments (< 16 entries) are ordered by numba's insertion sort with strict <, a stable sort.
+// Nothing has to be ranked for that.  Once the partitions are done every position left of a segment
+// holds a rank <= every rank inside it and every position right of it a rank >= -- the segments left
+// alone below the cut included -- so the entry at position p with rank r ends at
+//     f = r + (entries of rank r at positions < p).
+// An entry whose rank nobody shares has f = r; the members of a tie group take one ballot and one
+// mbcnt per group.  The groups follow from the ranks nobody CLAIMED (a group of s members at rank g
+// leaves g+1 .. g+s-1 unclaimed): they are visited from the top, down to the cut; a group wholly below
+// the cut keeps f = r < n-k, which is all a dropped entry has to say.  No LDS, no segment bounds.
 // ---------------------------------------------------------------------------
-// sel != nullptr: writes sel[0..k).  sel == nullptr: returns in *f_out the final position of the candidate
-// *c_out this lane ends up holding (or -1 if that position is below the cut / not resolved).
-__device__ inline void topk_ties_reg(int lt, int n, int k, int *sel, SortLds &S, int *f_out = nullptr, int *c_out = nullptr,
+// sel != nullptr: writes sel[0..k) (LDS of this wave).  sel == nullptr: returns in *f_out the final position of the
+// candidate *c_out this lane ends up holding (a position below the cut n-k: dropped; lanes >= n: undefined).
+__device__ inline void topk_ties_reg(int lt, int n, int k, int *sel, int *f_out = nullptr, int *c_out = nullptr,
                                      int cand_id = -1)
 {
     // Everything about the segment being partitioned (lo, hi, the pivot, the stack of pending segments) is
@@ -404,15 +412,13 @@ __device__ inline void topk_ties_reg(int lt, int n, int k, int *sel, SortLds &S,
     const int p = lane_id();
     const int drop = ZT_U(n - k);
     int e = (lt << 8) | (cand_id >= 0 ? cand_id : p);   // (rank, candidate); the candidate defaults to the position
-    int mylo = p, myhi = p - 1;                     // finished segment holding position p (empty: none)
-    unsigned pend_lo = 0u, pend_hi = 0u;            // stack of segments still to partition, 16 bits each
+    // which ranks are claimed: every entry sends a 1 to the lane of its rank (the partitions move entries, not ranks:
+    // asked for here, looked at after them).  Lanes >= n (n < 64) send a 0 to lane 63, which is nobody's rank then.
+    const int rank_taken = push_i32(p < n ? 1 : 0, p < n ? lt : 63);
+    u64 pend = 0ull;                                // stack of segments still to partition (at most four), 16 bits each
     int depth = 0;
     int lo = 0, hi = ZT_U(n - 1);
-    bool work = true;
-    if (hi - lo < 15) {
-        if (p <= hi) { mylo = lo; myhi = hi; }
-        work = false;
-    }
+    bool work = hi - lo >= 15;
     while (work) {
         lo = ZT_U(lo); hi = ZT_U(hi);
         // ---- median of three (uniform values, scalar unit) ----
@@ -427,10 +433,11 @@ __device__ inline void topk_ties_reg(int lt, int n, int k, int *sel, SortLds &S,
         e = (p == mid ? eh : e);
         e = (p == hi ? em : e);                     // pivot stashed at `hi`
         // ---- stops of the two scans over lo .. hi-1 ----
+        // (masks stay on the scalar unit; inverse_ballot turns one into a lane predicate without an instruction)
         const int key = e >> 8;
         const u64 seg = (((1ull << hi) - 1ull) >> lo) << lo;          // bits lo .. hi-1 (hi <= 62)
         const u64 GE = __ballot(key >= pk) & seg, LE = __ballot(key <= pk) & seg;
-        const bool ge = (GE >> p) & 1ull, le = (LE >> p) & 1ull;
+        const bool ge = __builtin_amdgcn_inverse_ballot_w64(GE), le = __builtin_amdgcn_inverse_ballot_w64(LE);
         // Hoare's scans swap the m-th i-stop (ascending) with the m-th j-stop (descending) while the former lies
         // to the left.  Number of swaps: with a(x) = i-stops at positions <= x and b(x) = j-stops at positions
         // > x, pair m swaps iff some x has a(x) > m and b(x) > m, so S = max_x min(a(x), b(x)); a rises and b
@@ -438,77 +445,73 @@ __device__ inline void topk_ties_reg(int lt, int n, int k, int *sel, SortLds &S,
         const int nJ = __popcll(LE);
         const int mi = mbcnt64(GE), lb = mbcnt64(LE);                  // stops strictly below this position
         const int a_p = mi + (ge ? 1 : 0), b_p = nJ - lb - (le ? 1 : 0);
-        const u64 C = __ballot(((seg >> p) & 1ull) && a_p >= b_p);     // never empty: b(hi-1) = 0
-        const int px = ZT_U(__ffsll((long long)C) - 1);
-        const u64 below_px = (1ull << px) - 1ull;
-        const int a_prev = __popcll(GE & below_px), b_at = __popcll(LE & ~below_px & ~(1ull << px));
+        const u64 C = __ballot(a_p >= b_p) & seg;                      // never empty: b(hi-1) = 0
+        const int px = ZT_U(__builtin_ctzll(C));
+        // i-stops below px = mi there; j-stops above px = b there
+        const int a_prev = __builtin_amdgcn_readlane(mi, px), b_at = __builtin_amdgcn_readlane(b_p, px);
         const int Sw = ZT_U(a_prev > b_at ? a_prev : b_at);            // swaps of this partition
         // The swapped i-stops are the Sw lowest, the swapped j-stops the Sw highest, and every swapped i-stop
         // lies left of every swapped j-stop: the swaps REVERSE the sequence of elements at these 2*Sw
         // positions.  Element number t of that sequence goes to compact lane 2*Sw-1-t (push), then position
         // number t fetches compact lane t (pull): two register permutes, no lists in LDS.
         const int mj = nJ - 1 - lb;                                    // rank among the j-stops, from the top
-        const bool swi = ge && mi < Sw, swj = le && mj < Sw;
+        const u64 SWI = __ballot(mi < Sw) & GE, SWJ = __ballot(mj < Sw) & LE;
+        const bool swi = __builtin_amdgcn_inverse_ballot_w64(SWI), sw = __builtin_amdgcn_inverse_ballot_w64(SWI | SWJ);
         const int t = swi ? mi : 2 * Sw - 1 - mj;
-        const int staged = push_i32(e, (swi || swj) ? 2 * Sw - 1 - t : 63);
-        const int got = __shfl(staged, (swi || swj) ? t : p);
+        const int staged = push_i32(e, sw ? 2 * Sw - 1 - t : 63);
+        const int got = __builtin_amdgcn_ds_bpermute((sw ? t : p) << 2, staged);
         // where the i-scan ends: the first i-stop that did not swap, or the lowest swapped j-stop
         // (it received a >= pivot value), or `hi`
-        const u64 stay = GE & ~__ballot(swi), sj = __ballot(swj);
-        int ifin = stay ? __ffsll((long long)stay) - 1 : hi;
-        if (sj) { const int jl = __ffsll((long long)sj) - 1; ifin = jl < ifin ? jl : ifin; }
+        const u64 stay = GE & ~SWI;
+        int ifin = stay ? __builtin_ctzll(stay) : hi;
+        if (SWJ) { const int jl = __builtin_ctzll(SWJ); ifin = jl < ifin ? jl : ifin; }
         ifin = ZT_U(ifin);
-        e = (swi || swj) ? got : e;                 // all pair swaps at once
+        e = sw ? got : e;                           // all pair swaps at once
         const int x = __builtin_amdgcn_readlane(e, ifin);
         e = (p == ifin ? em : e);                   // pivot <-> ifin
         e = (p == hi ? x : e);
-        if (p == ifin) { mylo = p; myhi = p; }
         // ---- children: only those reaching the kept ranks matter ----
         const int lhi = ifin - 1, rlo = ifin + 1;
-        const bool lneed = lhi >= lo && lhi >= drop, rneed = hi >= rlo && hi >= drop;
-        const bool lpart = lneed && lhi - lo >= 15, rpart = rneed && hi - rlo >= 15;
-        if (lneed && !lpart && p >= lo && p <= lhi) { mylo = lo; myhi = lhi; }
-        if (rneed && !rpart && p >= rlo && p <= hi) { mylo = rlo; myhi = hi; }
+        const bool lpart = lhi >= drop && lhi - lo >= 15, rpart = hi >= drop && hi - rlo >= 15;
         if (lpart) {
             if (rpart) {                            // push the right child
-                pend_hi = (pend_hi << 16) | (pend_lo >> 16);
-                pend_lo = (pend_lo << 16) | (unsigned)(rlo | (hi << 8));
+                pend = (pend << 16) | (u64)(unsigned)(rlo | (hi << 8));
                 ++depth;
             }
             hi = lhi;
         } else if (rpart) {
             lo = rlo;
         } else if (depth > 0) {
-            lo = (int)(pend_lo & 0xffu); hi = (int)((pend_lo >> 8) & 0xffu);
-            pend_lo = (pend_lo >> 16) | (pend_hi << 16);
-            pend_hi >>= 16;
+            lo = (int)(pend & 0xffull); hi = (int)((pend >> 8) & 0xffull);
+            pend >>= 16;
             --depth;
         } else {
             work = false;
         }
     }
-#undef ZT_U
-    // ---- stable rank inside every finished segment that reaches the cut ----
-    if (p < n) S.r[p] = (e & ~0xff) | p;            // (rank, current position)
-    wave_sync();
-    if (myhi >= mylo) {
-        const int cp = (e & ~0xff) | p;
-        int rank = 0;
-        for (int q0 = mylo; q0 <= myhi; q0 += 8) {  // segments hold at most 15 entries
-            int x[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) x[t] = S.r[(q0 + t) <= myhi ? (q0 + t) : myhi];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) rank += ((q0 + t) <= myhi && x[t] < cp) ? 1 : 0;
-        }
-        const int f = mylo + rank;
-        if (sel != nullptr) { if (f >= drop) sel[f - drop] = e & 0xff; }
-        else *f_out = f >= drop ? f : -1;
-    } else if (sel == nullptr) {
-        *f_out = -1;
+    // ---- final positions: rank + same-rank entries to the left, tie group by tie group from the top ----
+    const int key = p < n ? e >> 8 : -1;                              // (lanes >= n are in no group)
+    int f = key;
+    const u64 nmask = n >= 64 ? ~0ull : (1ull << n) - 1ull;           // positions 0 .. n-1
+    const u64 claimed = __ballot(rank_taken != 0) & nmask;            // (rank 0 is always claimed)
+    u64 open = ~claimed & nmask;                                      // ranks 1 .. n-1 inside a tie group
+    while ((open >> drop) != 0ull) {
+        const int top = 63 - __builtin_clzll(open);                                   // the group's last rank
+        const int g = ZT_U(63 - __builtin_clzll(claimed & ((1ull << top) - 1ull)));  // its members' rank
+        const bool member = key == g;
+        const u64 members = __ballot(member);
+        const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(members >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)members, (unsigned)g));
+        f = member ? at : f;                                          // g + members to my left
+        open &= (1ull << g) - 1ull;
     }
-    if (sel == nullptr) *c_out = e & 0xff;
-    wave_sync();
+#undef ZT_U
+    if (sel != nullptr) {
+        if (p < n && f >= drop) sel[f - drop] = e & 0xff;
+        wave_sync();
+    } else {
+        *f_out = f;
+        *c_out = e & 0xff;
+    }
 }
 
 // max of x >= 0 over the wave (uniform result); same scheme as wave_or (0 is the identity)
@@ -565,7 +568,7 @@ __device__ inline int rank_pass(double v, u64 live, int n, int k, int *lt_out, b
 // ties_order: the quicksort replay.  `pos` = this lane's place in the candidate LIST (the reference's
 // dictionary order, 0..n-1: numba's argsort depends on it).  Returns the slot [0, k) this lane's candidate
 // takes in np.argsort(values)[-k:], or -1 if it is dropped.
-__device__ inline int ties_order(int lt, u64 live, int pos, int n, int k, SortLds &S)
+__device__ inline int ties_order(int lt, u64 live, int pos, int n, int k)
 {
     const int lane = lane_id();
     const int drop = n - k;
@@ -573,15 +576,29 @@ __device__ inline int ties_order(int lt, u64 live, int pos, int n, int k, SortLd
     // bring (rank, lane) into list order (lane p = position p) and replay
     const int e_at_pos = push_i32(mine ? ((lt << 8) | lane) : 0, mine ? pos : 63);
     int f, c;
-    topk_ties_reg(e_at_pos >> 8, n, k, nullptr, S, &f, &c, e_at_pos & 0xff);
+    topk_ties_reg(e_at_pos >> 8, n, k, nullptr, &f, &c, e_at_pos & 0xff);
     // lane p holds the candidate of lane c at final position f: tell lane c its slot
     const bool kept = lane < n && f >= drop;
     const int got = push_i32(kept ? f - drop + 1 : 0, kept ? c : 63);
     return (mine && lane != 63) ? got - 1 : -1;
 }
 
+// The same replay answering by list POSITION: sig[q] (LDS of this wave, >= n ints) = the slot of the candidate that stood
+// at position q, -1 if it is dropped.  The lane that ends up holding a candidate writes the answer; nothing travels back
+// to the candidate's lane.  The caller synchronises the wave before it reads sig.
+__device__ inline void ties_order_at(int lt, u64 live, int pos, int n, int k, int *sig)
+{
+    const int lane = lane_id();
+    const int drop = n - k;
+    const bool mine = (live >> lane) & 1ull;
+    const int lt_at_pos = push_i32(mine ? lt : 0, mine ? pos : 63);   // ranks into list order (lane p = position p)
+    int f, q;
+    topk_ties_reg(lt_at_pos, n, k, nullptr, &f, &q);                  // (the candidate's name is its position)
+    if (lane < n) sig[q] = f >= drop ? f - drop : -1;
+}
+
 // both steps at once.  Returns the path taken (0 ranks, 4 quicksort replay).
-__device__ inline int topk_reg(double v, u64 live, int pos, int n, int k, SortLds &S, int *out_slot)
+__device__ inline int topk_reg(double v, u64 live, int pos, int n, int k, int *out_slot)
 {
     int lt;
     bool keep;
@@ -589,7 +606,7 @@ __device__ inline int topk_reg(double v, u64 live, int pos, int n, int k, SortLd
         *out_slot = keep ? lt - (n - k) : -1;
         return 0;
     }
-    *out_slot = ties_order(lt, live, pos, n, k, S);
+    *out_slot = ties_order(lt, live, pos, n, k);
     return 4;
 }
 
@@ -769,7 +786,7 @@ __device__ inline int topk_select_wave(const double *a, int n, int k, int *sel, 
         if (__ballot(v != v) == 0ull) {
             int lt;
             if (topk_rank_reg(v, n, k, sel, &lt)) return 0;
-            topk_ties_reg(lt, n, k, sel, S);
+            topk_ties_reg(lt, n, k, sel);
             return 4;
         }
     }

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64) void k_test_topk(const double *__restrict__ val
         const double v = lane < n ? L.a[lane] : 0.0;
         int lt;
         (void)topk_rank_reg(v, n, k, L.sel, &lt);
-        topk_ties_reg(lt, n, k, L.sel, L.sort);
+        topk_ties_reg(lt, n, k, L.sel);
         path = 4;
     } else if (mode == 5 || mode == 6) {          // the register-resident selection of merge_pair_reg:
         // 5 = candidates in lanes [0, n); 6 = split like the merge: the first half in lanes [0, n1), the rest from lane 32
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void k_test_topk(const double *__restrict__ val
         const u64 live = __ballot(pos >= 0);
         const double v = pos >= 0 ? L.a[pos] : 0.0;
         int slot;
-        path = topk_reg(v, live, pos, n, k, L.sort, &slot);
+        path = topk_reg(v, live, pos, n, k, &slot);
         if (slot >= 0) L.sel[slot] = pos;
         wave_sync();
     } else if (mode == 3) {

@@ -425,10 +425,9 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     hint->norm_out = new_norm; hint->tpos = tpos;
     if (!final_out) {
         // ---- my own replay: final slot of every list POSITION (identity-free, see Mail) ----
-        const int slot_c = merge_order(L, lane, k, F, lane, &n_new, -1);
+        int *sig = L.sel;                                        // final slot by list position (the one I replayed on: pos_prov)
+        (void)merge_order(L, lane, k, F, lane, &n_new, -1, sig);
         CRIT(8);
-        int *sig = L.sel;                                        // final slot by list position
-        if (mine) sig[pos_prov] = slot_c;
         wave_sync();
         // ---- identities: where my candidate REALLY stood in the list ----
         if (unc_in != 0u) hub_order();

@@ -583,9 +583,8 @@ __device__ __attribute__((always_inline)) inline void process_edge(const zt_tppr
             WL(0, 8);
             if (!final_out) {
                 // ---- my own replay: final slot of every list POSITION (identity-free, see Mail) ----
-                const int slot_c = merge_order(L, lane, k, F, lane, &n_new, mo == 0 ? i : -1);
-                int *sig = L.sel;                                        // final slot by list position
-                if (mine) sig[pos_prov] = slot_c;
+                int *sig = L.sel;                                        // final slot by list position (the one I replayed on: pos_prov)
+                (void)merge_order(L, lane, k, F, lane, &n_new, mo == 0 ? i : -1, sig);
                 wave_sync();
                 // ---- identities: where my candidate REALLY stood in the list ----
                 if (unc_in != 0u) hub_order();

@@ -761,12 +761,20 @@ __device__ inline bool merge_front_fast(WaveLds &L, int lane, int k, const Row &
 
 // The ORDER half: posA = dictionary position of this lane's s1 entry (lanes < n1).  Returns the slot of this
 // lane's candidate in the new dictionary (-1: dropped / none); *n_new = its length.
-__device__ inline int merge_order(WaveLds &L, int lane, int k, Front &F, int posA, int *n_new, int g_stamp_i = -1)
+// With `sig` (LDS of this wave, 64 ints) the answer is filed by list POSITION instead -- sig[pos] = slot of the candidate at
+// position pos -- for a caller that looks it up under another position than the one it passed in (hub chains: the
+// positions are provisional); the caller synchronises the wave before it reads, and the value returned means nothing.
+__device__ inline int merge_order(WaveLds &L, int lane, int k, Front &F, int posA, int *n_new, int g_stamp_i = -1,
+                                  int *sig = nullptr)
 {
     const bool mine = (F.live >> lane) & 1ull;
     const int pos = lane < 32 ? posA : F.pos_tail;
     const int n = F.n;
-    if (F.mode == FR_NOPRUNE) { *n_new = n; return mine ? pos : -1; }
+    if (F.mode == FR_NOPRUNE) {
+        *n_new = n;
+        if (sig != nullptr && mine) sig[pos] = pos;
+        return mine ? pos : -1;
+    }
     *n_new = k;
     int slot;
     if (F.mode == FR_RANKS) {
@@ -782,9 +790,14 @@ __device__ inline int merge_order(WaveLds &L, int lane, int k, Front &F, int pos
         wave_sync();
         const int got = push_i32(lane < k ? lane + 1 : 0, who);
         slot = mine && lane != 63 ? got - 1 : -1;
+    } else if (sig != nullptr) {
+        ties_order_at(F.lt, F.live, pos, n, k, sig);              // :553-559 (second half), filed by the replay's own lanes
+        STAMP2(5);
+        return -1;
     } else {
-        slot = ties_order(F.lt, F.live, pos, n, k, L.sort);       // :553-559 (second half)
+        slot = ties_order(F.lt, F.live, pos, n, k);       // :553-559 (second half)
     }
+    if (sig != nullptr && mine) sig[pos] = slot;
     STAMP2(5);
     return slot;
 }
