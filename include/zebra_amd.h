@@ -666,6 +666,27 @@ int64_t zt_affinity_workspace_bytes(int64_t max_B, int32_t H);
 int zt_affinity(const float *emb_dev, int64_t B, int32_t H, const zt_affinity_weights *weights,
                 float *prob_dev, void *workspace_dev, int64_t ws_max_B, int32_t weights_ready,
                 void *stream);
+/* The same scorer for a TRAINING step, differentiable (csrc/scoring_train.hip): any H with H % 4 == 0 and
+ * 4 <= H <= 768 (ZT_ERR_UNSUPPORTED otherwise), any B >= 0 (B = 0: ZT_OK, nothing touched).  The parameters are read
+ * as they lie in the module (no packed copy, no weights_ready); emb_dev and the weight matrices are 16-byte aligned.
+ *   forward:  emb_dev [3B][H] -> prob_dev [2B] (the layout zt_affinity writes) and hid_dev [2B][H], the hidden rows
+ *             after the ReLU (pair rows: B positive, then B negative), kept for the backward.  One launch.
+ *   backward: from dprob_dev [2B] and the forward's prob_dev / hid_dev: d_emb_dev [3B][H], d_fc1_w_dev [H][2H],
+ *             d_fc1_b_dev [H], d_fc2_w_dev [H], d_fc2_b_dev [1], written, not accumulated.  An output that is not needed is
+ *             NULL and its work is skipped.  At most three launches, no host synchronisation, no atomics: every sum
+ *             has a fixed order, two runs give the same bits.
+ * workspace_dev (backward only): zt_affinity_train_workspace_bytes(max_B, H) bytes (-1 = H unsupported), sized for
+ * ws_max_B >= B; it holds d(hidden) [2B][H], d(score) [2B] and the partial products of the weight gradient. */
+int64_t zt_affinity_train_workspace_bytes(int64_t max_B, int32_t H);
+int zt_affinity_train_forward(const float *emb_dev, int64_t B, int32_t H,
+                              const zt_affinity_weights *weights, float *prob_dev, float *hid_dev,
+                              void *stream);
+int zt_affinity_train_backward(const float *emb_dev, int64_t B, int32_t H,
+                               const zt_affinity_weights *weights, const float *prob_dev,
+                               const float *hid_dev, const float *dprob_dev, float *d_emb_dev,
+                               float *d_fc1_w_dev, float *d_fc1_b_dev, float *d_fc2_w_dev,
+                               float *d_fc2_b_dev, void *workspace_dev, int64_t ws_max_B,
+                               void *stream);
 /* evaluation/evaluation.py:34-45 and train.py:218-227 without the host: out_dev[0..3) (float64) =
  * (average_precision_score, roc_auc_score, mean(pos >= neg)) of B positive and B negative scores, scikit-learn's
  * definitions (distinct thresholds, ties included); accumulate != 0 adds to out_dev.  2B <= 16384. */

@@ -32,6 +32,7 @@ SOURCES = {
     "train_ops.hip": [],
     "attention.hip": [],
     "scoring.hip": [],
+    "scoring_train.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],
 }

@@ -174,13 +174,20 @@ class ShardedTGN:
         sel = np.arange(e0, e1)
         s, d, n = tgn.compute_temporal_embeddings(source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs,
                                                   n_neighbors, True, edge_sel=sel)
-        score = tgn.affinity_score(torch.cat([s, s], dim=0), torch.cat([d, n])).squeeze(dim=0)
         m = e1 - e0
-        pos, neg = score[:m].sigmoid(), score[m:].sigmoid()
-        dev = pos.device
-        # criterion is a mean over its inputs (BCELoss): weight this rank's mean by its share of the batch
-        loss = (criterion(pos.squeeze(-1), torch.ones(m, device=dev)) +
-                criterion(neg.squeeze(-1), torch.zeros(m, device=dev))) * (m / float(B)) if m else score.sum() * 0.0
+        if m:
+            # this rank's rows came back as one [3m, H] block: the scorer of the plain step (TGN.score_train)
+            block = getattr(tgn, "_last_node_block", None)
+            if block is None or block.data_ptr() != s.data_ptr() or block.shape[0] != 3 * m or not block.is_contiguous():
+                block = torch.cat([s, d, n])
+            pos, neg = tgn.score_train(block)
+            dev = pos.device
+            # criterion is a mean over its inputs (BCELoss): weight this rank's mean by its share of the batch
+            loss = (criterion(pos.squeeze(-1), torch.ones(m, device=dev)) +
+                    criterion(neg.squeeze(-1), torch.zeros(m, device=dev))) * (m / float(B))
+        else:
+            score = tgn.affinity_score(torch.cat([s, s], dim=0), torch.cat([d, n])).squeeze(dim=0)
+            loss = score.sum() * 0.0
         loss.backward()
         allreduce_gradients(tgn.parameters(), self.group)
         return loss.detach()

@@ -296,6 +296,47 @@ class _HipLinear(torch.autograd.Function):
         return dx, dw, db
 
 
+class _HipLinkScore(torch.autograd.Function):
+    """prob [2B] = sigmoid(MergeLayer([src | src], [dst | neg])) for the [3B, H] embeddings of a batch -- the B positive
+    pairs, then the B negative ones -- with forward and backward on the HIP kernels of csrc/scoring_train.hip
+    (zt_affinity_train_forward / zt_affinity_train_backward): compute_edge_probabilities' scorer (model/tgn_model.py:185-188)
+    in a training step.  H % 4 == 0, 4 <= H <= 768 (tgn.link_score_plan); no double backward."""
+
+    @staticmethod
+    def forward(ctx, emb, fc1_w, fc1_b, fc2_w, fc2_b):
+        emb = emb.contiguous()
+        B, H = emb.shape[0] // 3, emb.shape[1]
+        if emb.shape[0] != 3 * B or tuple(fc1_w.shape) != (H, 2 * H):
+            raise ValueError("_HipLinkScore: emb [3B, H] and fc1.weight [H, 2H] expected")
+        par = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b)]
+        prob = torch.empty(2 * B, dtype=torch.float32, device=emb.device)
+        hid = torch.empty((2 * B, H), dtype=torch.float32, device=emb.device)
+        wt = _capi.AffinityWeights(*[ptr(t) for t in par])
+        check(lib().zt_affinity_train_forward(ptr(emb), C.c_int64(B), C.c_int32(H), C.byref(wt), ptr(prob), ptr(hid),
+                                              stream_ptr()), "zt_affinity_train_forward")
+        ctx.save_for_backward(emb, prob, hid, *par)
+        ctx.shapes = tuple(tuple(t.shape) for t in (fc1_w, fc1_b, fc2_w, fc2_b))
+        return prob
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dprob):
+        emb, prob, hid, w1, b1, w2, b2 = ctx.saved_tensors
+        B, H = emb.shape[0] // 3, emb.shape[1]
+        dev = emb.device
+        new = torch.zeros if B == 0 else torch.empty                    # (no pair: the kernels are not launched)
+        outs = [new(shape, dtype=torch.float32, device=dev) if need else None
+                for shape, need in zip((tuple(emb.shape),) + ctx.shapes, ctx.needs_input_grad)]
+        if B and any(o is not None for o in outs):
+            ws = torch.empty(int(lib().zt_affinity_train_workspace_bytes(C.c_int64(B), C.c_int32(H))), dtype=torch.uint8,
+                             device=dev)
+            wt = _capi.AffinityWeights(ptr(w1), ptr(b1), ptr(w2), ptr(b2))
+            check(lib().zt_affinity_train_backward(ptr(emb), C.c_int64(B), C.c_int32(H), C.byref(wt), ptr(prob), ptr(hid),
+                                                   ptr(dprob.contiguous()), *[ptr(o) for o in outs], ptr(ws), C.c_int64(B),
+                                                   stream_ptr()), "zt_affinity_train_backward")
+        return tuple(outs)
+
+
 def _cell_rows_forward(ctx, fwd, saved_cols, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32):
     U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
     dev = memory_t.device

@@ -15,7 +15,16 @@ import torch
 
 from . import _capi
 from ._capi import check, lib, ptr, stream_ptr
-from .modules import Memory, MergeLayer, TimeEncode, get_embedding_module, get_memory_updater
+from .modules import Memory, MergeLayer, TimeEncode, _HipLinkScore, get_embedding_module, get_memory_updater
+
+
+def link_score_plan(device_type, dtype, H, fused_scoring=True):
+    """Which scorer a training step runs (pure host code, in the style of the library's embed_kernel_plan): "hip" --
+    _HipLinkScore -- when ``fused_scoring`` is on, the embeddings are float32 on the GPU and the hidden width is one the
+    kernels take (H % 4 == 0, 4 <= H <= 768: zt_affinity_train_workspace_bytes); else "torch", MergeLayer's composition."""
+    if not fused_scoring or device_type != "cuda" or dtype != torch.float32:
+        return "torch"
+    return "hip" if (H % 4 == 0 and 4 <= H <= 768) else "torch"
 
 
 class TGN(torch.nn.Module):
@@ -71,6 +80,8 @@ class TGN(torch.nn.Module):
             num_nodes=self.n_nodes)
         hidden_dim = self.n_node_features * (len(args.alpha_list) + 1)
         self.affinity_score = MergeLayer(hidden_dim, hidden_dim, hidden_dim, 1)
+        # training: the scorer's forward and backward on the HIP kernels (score_train); False: torch's MergeLayer under autograd
+        self.fused_scoring = True
         # device scratch of the message-store kernel: last occurrence per node (all -1 between calls)
         self._scratch = torch.full((self.n_nodes,), -1, dtype=torch.int32, device=self.device)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -141,6 +152,23 @@ class TGN(torch.nn.Module):
         check(lib().zt_affinity(ptr(emb.contiguous()), C.c_int64(B), C.c_int32(emb.shape[1]), C.byref(w), ptr(prob), ptr(st["ws"]),
                                 C.c_int64(st["max_B"]), C.c_int32(1 if ready else 0), stream_ptr()), "zt_affinity")
         return prob
+
+    def _score_pairs(self, s, dd, n):
+        """The scorer as torch composes it (tgn_model.py:185-188): (pos [B, 1], neg [B, 1]) under autograd."""
+        n_samples = s.shape[0]
+        score = self.affinity_score(torch.cat([s, s], dim=0), torch.cat([dd, n])).squeeze(dim=0)
+        return score[:n_samples].sigmoid(), score[n_samples:].sigmoid()
+
+    def score_train(self, emb):
+        """(pos [B, 1], neg [B, 1]) = sigmoid(affinity_score([src | src], [dst | neg])) for the [3B, H] embeddings
+        [src | dst | neg] of a training batch, differentiable: csrc/scoring_train.hip through _HipLinkScore where
+        link_score_plan says so, else torch's composition."""
+        B = emb.shape[0] // 3
+        a = self.affinity_score
+        if link_score_plan(emb.device.type, emb.dtype, emb.shape[1], getattr(self, "fused_scoring", True)) == "hip":
+            prob = _HipLinkScore.apply(emb, a.fc1.weight, a.fc1.bias, a.fc2.weight, a.fc2.bias)
+            return prob[:B].unsqueeze(1), prob[B:].unsqueeze(1)
+        return self._score_pairs(emb[:B], emb[B:2 * B], emb[2 * B:])
 
     def enable_scoring(self, on=True):
         """With the native pipeline: every whole-batch step also scores its 2B pairs behind its aggregation
@@ -558,6 +586,7 @@ class TGN(torch.nn.Module):
             with torch.no_grad():
                 self.store_messages_device(src_d, dst_d, ts_d, eidx_d)
         self._last_node_embedding = node_embedding if edge_sel is None else None
+        self._last_node_block = node_embedding                           # [3 n_samples, H]: what the three slices are views of
         return (node_embedding[:n_samples], node_embedding[n_samples:2 * n_samples], node_embedding[2 * n_samples:])
 
     def compute_edge_probabilities(self, source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs,
@@ -575,8 +604,12 @@ class TGN(torch.nn.Module):
                 full = torch.cat([s, dd, n])
             prob = self.score_device(full)
             return prob[:n_samples].unsqueeze(1), prob[n_samples:].unsqueeze(1)
-        score = self.affinity_score(torch.cat([s, s], dim=0), torch.cat([dd, n])).squeeze(dim=0)
-        return score[:n_samples].sigmoid(), score[n_samples:].sigmoid()
+        if train and link_score_plan(s.device.type, s.dtype, s.shape[1], getattr(self, "fused_scoring", True)) == "hip":
+            full = getattr(self, "_last_node_block", None)               # the [3B, H] block s / dd / n are slices of
+            if full is None or full.data_ptr() != s.data_ptr() or full.shape[0] != 3 * n_samples or not full.is_contiguous():
+                full = torch.cat([s, dd, n])
+            return self.score_train(full)
+        return self._score_pairs(s, dd, n)
 
     def update_memory(self, memory, positives):
         with torch.no_grad():
