@@ -82,7 +82,10 @@ int zt_stream_destroy(void *stream);
                                  * launch groups then taper towards the end of the batches in sight); ZT_RELEASE_LAUNCH_FULL: the
                                  * same without the taper (uniform launches for counter collection, which serialises kernels and so
                                  * cannot run a release by member: tools/profile_round.sh) */
-#define ZT_CHOICE_COUNT 7
+#define ZT_CHOICE_SCORE 7       /* zt_affinity and the pipeline's scoring: ZT_SCORE_LATENCY, ZT_SCORE_TILED (the kernels specialised for
+                                 * hidden widths 200 and 300; at any other width: the library's pick), ZT_SCORE_GENERIC_LATENCY,
+                                 * ZT_SCORE_GENERIC_TILED (any width zt_affinity takes, 200 and 300 included) */
+#define ZT_CHOICE_COUNT 8
 #define ZT_AGG_GENERIC 1
 #define ZT_OUT_TILED 1
 #define ZT_OUT_LATENCY 2
@@ -100,6 +103,10 @@ int zt_stream_destroy(void *stream);
 #define ZT_RELEASE_LAUNCH_FULL 3
 #define ZT_MSG_ONE 1
 #define ZT_MSG_TWO 2
+#define ZT_SCORE_LATENCY 1
+#define ZT_SCORE_TILED 2
+#define ZT_SCORE_GENERIC_LATENCY 3
+#define ZT_SCORE_GENERIC_TILED 4
 int zt_set_kernel_choice(int32_t which, int32_t value);
 
 /* Per-kernel timing with HIP events recorded on the launch stream (replaces
@@ -658,8 +665,13 @@ typedef struct {
 } zt_affinity_weights;           /* device pointers */
 
 /* TGN.compute_edge_probabilities' scorer (model/tgn_model.py:185-188):
- *   emb_dev [3B][H] = the batch's embeddings [src | dst | neg], H = D * (n_tppr + 1) in {200, 300};
+ *   emb_dev [3B][H] = the batch's embeddings [src | dst | neg], H = D * (n_tppr + 1): any H with H % 4 == 0 and
+ *                     4 <= H <= 768 -- the widths the training scorer below takes (ZT_ERR_UNSUPPORTED otherwise);
  *   prob_dev [2B]   = sigmoid(fc2(relu(fc1([src | dst])))) for the B positive pairs, then the same for (src, neg).
+ * Hidden widths 200 and 300 (D = 100 with one or two T-PPR models) run kernels specialised for them, every other width
+ * two generic ones (K and N run over H at run time); by batch size a latency-organised form or a tiled one
+ * (ZT_CHOICE_SCORE pins the form).  No float atomics: two calls give the same bits.  emb_dev and fc1_w are 16-byte
+ * aligned.
  * workspace_dev: zt_affinity_workspace_bytes(max_B, H) bytes (-1 = H unsupported), sized for ws_max_B >= B;
  * weights_ready as for zt_embed (0 also clears the workspace's tile counters: use it for a fresh workspace). */
 int64_t zt_affinity_workspace_bytes(int64_t max_B, int32_t H);

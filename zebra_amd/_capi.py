@@ -37,6 +37,8 @@ SYMBOLS = [
 # zt_set_kernel_choice selectors / values (include/zebra_amd.h)
 CHOICE_AGGREGATE, CHOICE_EMBED_OUT, CHOICE_GRU, CHOICE_MESSAGES, CHOICE_TPPR_CHAIN, CHOICE_TPPR_PREPASS = 0, 1, 2, 3, 4, 5
 CHOICE_GROUP_RELEASE = 6
+CHOICE_SCORE = 7
+SCORE_LATENCY, SCORE_TILED, SCORE_GENERIC_LATENCY, SCORE_GENERIC_TILED = 1, 2, 3, 4
 RELEASE_MEMBER, RELEASE_LAUNCH, RELEASE_LAUNCH_FULL = 1, 2, 3
 PREPASS_LAUNCHES, PREPASS_COOP = 1, 2                          # PREPASS_COOP: removed; see DESIGN.md section 5
 CHAIN_SINGLE, CHAIN_PAIRED, CHAIN_SPINE, CHAIN_DUO = 1, 2, 3, 4   # PAIRED / SPINE / DUO: removed; see DESIGN.md section 5

@@ -96,6 +96,22 @@ struct MemoryPlan {
 // Pure host code (no HIP calls).  F, T: the message's edge-feature and time widths; the choices: ZT_CHOICE_GRU, ZT_CHOICE_MESSAGES
 MemoryPlan memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, int T, int gru_choice, int msg_choice,
                               const HeldOut &held);
+// The eval link scorer's kernel for one batch (scoring.hip: affinity_kernel_plan).  latency = k_affinity<KC> (one wave per
+// 16-edge tile and N-tile, weights in registers), tiled = k_affinity_tiled<KC, ET> (ET edges per workgroup staged in LDS): the two
+// specialised forms of round_up16(H) = 16 KC in {208, 304}; gen_latency = k_affinity_gen, gen_tiled = k_affinity_gen_tiled: any
+// H % 4 == 0, 4 <= H <= 768 (K and N run over H at run time).  Every form computes the same function; they differ in how the
+// float32 sums associate.  The values are the ZT_SCORE_* of ZT_CHOICE_SCORE.
+enum class AffForm { refused = 0, latency = 1, tiled = 2, gen_latency = 3, gen_tiled = 4 };
+struct AffinityPlan {
+    AffForm form;
+    int KC, ET;            // the specialised forms' template arguments (0 for the generic ones)
+    unsigned gx, gy;       // grid
+    unsigned threads;
+    size_t lds;            // dynamic LDS
+};
+// Pure host code (no HIP calls).  A function of (B, H, choice) alone -- never of the workspace's max_B: the pipeline and a direct
+// call pick the same kernel for the same batch.  choice: ZT_CHOICE_SCORE (a form the width cannot take: the library's pick)
+AffinityPlan affinity_kernel_plan(int64_t B, int H, int choice);
 // The output layers of an embed call, held back (embed_ex: `defer`) so that gru_update_ex can launch them in ONE kernel with the
 // GRU update (k_out_gru, memory_update.hip): the two are independent apart from the memory rows the source path reads --
 // the GRU half waits for those reads before it writes (a gate in the GRU workspace whose whole state is device memory: a

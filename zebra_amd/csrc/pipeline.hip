@@ -404,8 +404,8 @@ extern "C" int zt_pipeline_set_scoring(zt_pipeline *p, const zt_affinity_weights
         set_error("zt_pipeline_set_scoring: NULL buffer");
         return ZT_ERR_ARG;
     }
-    if (zt_affinity_workspace_bytes(p->d.max_B, p->d.D * (p->d.M + 1)) < 0) {
-        set_error("zt_pipeline_set_scoring: hidden width %d unsupported", p->d.D * (p->d.M + 1));
+    if (zt::affinity_kernel_plan(p->d.max_B, p->d.D * (p->d.M + 1), 0).form == zt::AffForm::refused) {
+        set_error("zt_pipeline_set_scoring: hidden width %d unsupported (H %% 4 == 0 and 4 <= H <= 768)", p->d.D * (p->d.M + 1));
         return ZT_ERR_UNSUPPORTED;
     }
     p->aff = *weights; p->aff_ws = workspace_dev; p->prob = prob_dev;

@@ -16,11 +16,19 @@
 // per tile, reset by that wave) adds them first to last -- a fixed order, so the probabilities do not depend on which
 // wave finishes when -- and applies fc2's bias and the sigmoid.
 //
+// The two kernels of that organisation (k_affinity, k_affinity_tiled) are specialised for the reference's default width: hidden
+// widths 200 and 300 (round_up16(H) = 16 KC, KC = 13 or 19 a template argument: weights and accumulators live in registers).
+// Every other width the training scorer takes (H % 4 == 0, 4 <= H <= 768: D = 172 or 256 with one or two T-PPR models) runs
+// two generic kernels in which K and N run over H at run time: k_affinity_gen (latency form: the weights are streamed, not
+// kept) and k_affinity_gen_tiled (the training scorer's forward, scoring_fwd.hpp, without the hidden rows).  Which kernel a
+// batch takes is decided in ONE place, affinity_kernel_plan (host code).
+//
 // zt_link_metrics replaces the per-batch scikit-learn calls of evaluation/evaluation.py:34-45 and train.py:218-227
 // (average_precision_score, roc_auc_score, accuracy of argmax) with ONE single-workgroup kernel: bitonic sort of the 2B
 // scores in LDS, two scans (true positives; start of every run of equal scores) and the two curve sums over the distinct
 // thresholds in float64, ties handled as scikit-learn does (zebra_amd/evaluation.py states the definitions).
 #include "common.hpp"
+#include "scoring_fwd.hpp"
 
 using namespace zt;
 
@@ -238,6 +246,123 @@ __global__ __launch_bounds__(256, ET == 16 ? 2 : 1) void k_affinity_tiled(const 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// any hidden width: H % 4 == 0, 4 <= H <= 768
+// ---------------------------------------------------------------------------------------------------------
+// U k-chunks of 16 of k_affinity_gen, from chunk c (chunks beyond NT: clamped addresses, zero operands): the wave's 16 rows of
+// the packed W_a / W_b and its three embedding rows, every load of the round issued before the round's first MFMA
+constexpr int AG_U = 8;
+template <int U>
+__device__ __forceinline__ void gen_chunks(int c, int NT, int g4, int H, bool rin, const float *__restrict__ wa_row,
+                                           const float *__restrict__ wb_row, const float *__restrict__ ps, const float *__restrict__ pd,
+                                           const float *__restrict__ pn, f32x4 &au, f32x4 &ap, f32x4 &ang)
+{
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 wa[U], wb[U], as[U], ad[U], an[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const bool live = c + u < NT;
+        const int k = 16 * (live ? c + u : NT - 1) + 4 * g4;            // < Hp: inside the padded weight rows
+        const bool kin = k < H;                                         // H % 4 == 0: all four columns or none
+        const int ke = kin ? k : H - 4;                                 // (the loads: unconditional, from clamped addresses)
+        const f32x4 va = *reinterpret_cast<const f32x4 *>(wa_row + k), vb = *reinterpret_cast<const f32x4 *>(wb_row + k);
+        const f32x4 vs = *reinterpret_cast<const f32x4 *>(ps + ke), vd = *reinterpret_cast<const f32x4 *>(pd + ke);
+        const f32x4 vn = *reinterpret_cast<const f32x4 *>(pn + ke);
+        const bool ok = live && kin && rin;
+        wa[u] = live ? va : zero4;
+        wb[u] = live ? vb : zero4;
+        as[u] = ok ? vs : zero4;
+        ad[u] = ok ? vd : zero4;
+        an[u] = ok ? vn : zero4;
+    }
+    __builtin_amdgcn_sched_barrier(0);                                   // (or the scheduler sinks every load to its first use)
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            au = __builtin_amdgcn_mfma_f32_16x16x4f32(as[u][j], wa[u][j], au, 0, 0, 0);
+            ap = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[u][j], wb[u][j], ap, 0, 0, 0);
+            ang = __builtin_amdgcn_mfma_f32_16x16x4f32(an[u][j], wb[u][j], ang, 0, 0, 0);
+        }
+}
+
+// Generic latency form (small batches): one wave per (16-edge tile, N-tile), as k_affinity.  At the batch sizes it serves a wave
+// sees ONE tile, so weights kept in registers would buy nothing (and NT = 48 chunks of two matrices would not fit): the wave
+// streams its 16 rows of the packed, zero-padded W_a / W_b [Hp][Hp] in rounds of AG_U k-chunks beside the embedding rows.  The
+// N-tiles' partial scores meet in the same part / counters workspace; the last wave to arrive adds the NT = Hp / 16 partials (up
+// to 48) first to last and resets the counter.  No float atomics: two launches give the same bits.
+__global__ __launch_bounds__(64) void k_affinity_gen(const float *__restrict__ emb, long long B, int H, const float *__restrict__ packed,
+                                                     const float *__restrict__ fc2_b, float *part, int *counters, float *__restrict__ prob)
+{
+    const int Hp = round_up16(H), NT = Hp / 16;
+    const int lane = threadIdx.x, r16 = lane & 15, g4 = lane >> 4;
+    const int nt = blockIdx.y, col = 16 * nt + r16;                      // col < Hp: the padded rows are zero
+    const float *Wa = packed, *Wb = packed + (size_t)Hp * Hp, *b1p = Wb + (size_t)Hp * Hp, *w2p = b1p + Hp;
+    const float *wa_row = Wa + (size_t)col * Hp, *wb_row = Wb + (size_t)col * Hp;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const float b1v = b1p[col], w2v = w2p[col], b2v = fc2_b[0];
+    const long long tiles = (B + 15) / 16, Bp = tiles * 16;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long e0 = t * 16;
+        const bool rin = e0 + r16 < B;
+        const float *ps = emb + (size_t)(rin ? e0 + r16 : 0) * H, *pd = ps + (size_t)B * H, *pn = pd + (size_t)B * H;
+        f32x4 au = zero4, ap = zero4, ang = zero4;
+        for (int c = 0; c < NT; c += AG_U) gen_chunks<AG_U>(c, NT, g4, H, rin, wa_row, wb_row, ps, pd, pn, au, ap, ang);
+        // lane (column col, edges 4 g4 + j): relu(fc1) x fc2's weight, summed over the wave's 16 columns
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float hp = au[j] + ap[j] + b1v, hn = au[j] + ang[j] + b1v;
+            hp = (hp > 0.f ? hp : 0.f) * w2v;
+            hn = (hn > 0.f ? hn : 0.f) * w2v;
+            hp += dpp_f<0x128>(hp); hp += dpp_f<0x124>(hp); hp += dpp_f<0x122>(hp); hp += dpp_f<0x121>(hp);
+            hn += dpp_f<0x128>(hn); hn += dpp_f<0x124>(hn); hn += dpp_f<0x122>(hn); hn += dpp_f<0x121>(hn);
+            if (r16 == 0) {                                              // (lane 0 of the row: ITS association of the 16 terms)
+                part[((size_t)nt * 2 + 0) * Bp + e0 + 4 * g4 + j] = hp;
+                part[((size_t)nt * 2 + 1) * Bp + e0 + 4 * g4 + j] = hn;
+            }
+        }
+        __threadfence();
+        int done = 0;
+        if (lane == 0) done = atomicAdd(&counters[t], 1);
+        done = __builtin_amdgcn_readfirstlane(done);
+        if (done == NT - 1) {                                            // the last N-tile of this tile to arrive
+            __threadfence();
+            if (lane < 32) {
+                const int e = lane & 15, which = lane >> 4;
+                float sc = 0.f;
+                for (int q0 = 0; q0 < NT; q0 += 8) {                     // eight partials requested before the first is looked at
+                    float pv[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int q = q0 + i < NT ? q0 + i : NT - 1;
+                        pv[i] = __int_as_float(ld_agent(reinterpret_cast<const int *>(part + ((size_t)q * 2 + which) * Bp + e0 + e)));
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        if (q0 + i < NT) sc += pv[i];
+                }
+                sc += b2v;
+                if (e0 + e < B) prob[(size_t)which * B + e0 + e] = 1.f / (1.f + expf(-sc));
+            }
+            if (lane == 0) atomicExch(&counters[t], 0);                 // ready for the next launch
+        }
+    }
+}
+
+// Generic tiled form (large batches).  k_affinity_tiled cannot be stretched: at NT = 48 its acc[3][NQ] beside the double-buffered
+// weights exceed the 256 registers its launch bounds allow.  This is the training scorer's forward (scoring_fwd.hpp: sixteen
+// waves own 16 edges, their 48 rows staged in LDS once, wave w takes N-tiles w, w + 16, ... with three accumulators, partials
+// added in wave order) without the hidden rows.  It reads the MODULE'S OWN parameters (fc1.weight [H][2H] as it lies, 16-byte
+// aligned), not the packed copy: the body is the training kernel's, instruction for instruction, and a weight is read once per
+// workgroup either way.
+__global__ __launch_bounds__(SCORE_THREADS) void k_affinity_gen_tiled(const float *__restrict__ emb, long long B, int H,
+                                                                      const float *__restrict__ fc1_w, const float *__restrict__ fc1_b,
+                                                                      const float *__restrict__ fc2_w, const float *__restrict__ fc2_b,
+                                                                      float *__restrict__ prob)
+{
+    score_fwd_body<false>(emb, B, H, fc1_w, fc1_b, fc2_w, fc2_b, prob, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // metrics
 // ---------------------------------------------------------------------------------------------------------
 constexpr int MT_THREADS = 1024;
@@ -353,12 +478,63 @@ void aff_plan(int64_t max_B, int H, AffPlan &p)
     p.total = o;
 }
 
+// where the generic forms switch (tools/score_eval_time.py)
+constexpr long long SPEC_TILED_MIN = 512, SPEC_ET32_MIN = 8192 + 1, GEN_TILED_MIN = 512;
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
+
+// The one place that says which kernel scores a batch, with which launch parameters (common.hpp)
+AffinityPlan zt::affinity_kernel_plan(int64_t B, int H, int choice)
+{
+    AffinityPlan ap{AffForm::refused, 0, 0, 0u, 0u, 0u, 0};
+    if (!score_width_ok(H) || B < 0) return ap;
+    const int Hp = round_up16(H);
+    const bool spec = Hp == 208 || Hp == 304;                             // H = D (n_tppr + 1), D = 100, n_tppr in {1, 2}
+    // the library's pick: the specialised kernels where they exist.  Small batches: the latency-organised form; large ones: the
+    // tiled one (all give the same probabilities to rounding; where the switches sit: tools/score_eval_time.py)
+    AffForm form = spec ? (B >= SPEC_TILED_MIN ? AffForm::tiled : AffForm::latency)
+                        : (B >= GEN_TILED_MIN ? AffForm::gen_tiled : AffForm::gen_latency);
+    // a pinned form that cannot take the width falls back to the pick above
+    if (choice == ZT_SCORE_GENERIC_LATENCY) form = AffForm::gen_latency;
+    else if (choice == ZT_SCORE_GENERIC_TILED) form = AffForm::gen_tiled;
+    else if (choice == ZT_SCORE_LATENCY && spec) form = AffForm::latency;
+    else if (choice == ZT_SCORE_TILED && spec) form = AffForm::tiled;
+    ap.form = form;
+    const long long tiles = (B + 15) / 16;
+    switch (form) {
+    case AffForm::latency:
+    case AffForm::gen_latency:
+        // tiles x N-tiles waves; beyond ~3 waves per SIMD the waves stride over tiles (the specialised form: with their weights in registers)
+        ap.KC = form == AffForm::latency ? Hp / 16 : 0;
+        ap.gx = (unsigned)(tiles < 160 ? tiles : 160);
+        ap.gy = (unsigned)(Hp / 16);
+        ap.threads = 64;
+        break;
+    case AffForm::tiled:
+        // 16 edges per workgroup while that fills the chip once (two workgroups fit a CU), 32 beyond
+        ap.KC = Hp / 16;
+        ap.ET = B < SPEC_ET32_MIN ? 16 : 32;
+        ap.lds = ((size_t)3 * ap.ET * (Hp + 4) + 4 * 2 * ap.ET) * 4;
+        ap.gx = (unsigned)((B + ap.ET - 1) / ap.ET);
+        ap.gy = 1;
+        ap.threads = 256;
+        break;
+    default:
+        ap.lds = score_fwd_lds(H);
+        ap.gx = (unsigned)tiles;
+        ap.gy = 1;
+        ap.threads = SCORE_THREADS;
+        break;
+    }
+    return ap;
+}
 
 extern "C" int64_t zt_affinity_workspace_bytes(int64_t max_B, int32_t H)
 {
     if (max_B <= 0 || H <= 0) return -1;
-    if (H % 4 != 0 || (round_up16(H) != 208 && round_up16(H) != 304)) return -1;     // H = D (n_tppr + 1), D = 100, n_tppr in {1, 2}
+    if (affinity_kernel_plan(max_B, H, 0).form == AffForm::refused) return -1;
     AffPlan p;
     aff_plan(max_B, H, p);
     return (int64_t)p.total;
@@ -371,11 +547,16 @@ extern "C" int zt_affinity(const float *emb_dev, int64_t B, int32_t H, const zt_
         set_error("zt_affinity: bad argument");
         return ZT_ERR_ARG;
     }
-    if (zt_affinity_workspace_bytes(ws_max_B > 0 ? ws_max_B : 1, H) < 0) {
-        set_error("zt_affinity: H=%d unsupported (H = 200 or 300)", H);
+    const AffinityPlan kp = affinity_kernel_plan(B, H, kernel_choice(ZT_CHOICE_SCORE));
+    if (kp.form == AffForm::refused) {
+        set_error("zt_affinity: H=%d unsupported (H %% 4 == 0 and 4 <= H <= %d)", H, SCORE_MAX_H);
         return ZT_ERR_UNSUPPORTED;
     }
     if (B == 0) return ZT_OK;
+    if (kp.form == AffForm::gen_tiled && (!aligned16(emb_dev) || !aligned16(wt->fc1_w))) {
+        set_error("zt_affinity: the embeddings and fc1's weight are read as 16-byte vectors");
+        return ZT_ERR_ARG;
+    }
     AffPlan p;
     aff_plan(ws_max_B, H, p);
     hipStream_t s = (hipStream_t)stream;
@@ -386,31 +567,38 @@ extern "C" int zt_affinity(const float *emb_dev, int64_t B, int32_t H, const zt_
         k_pack_affinity<<<(n + 255) / 256, 256, 0, s>>>(wt->fc1_w, wt->fc1_b, wt->fc2_w, H, p.Hp, packed);
         ZT_HIP(hipMemsetAsync(ws + p.off_cnt, 0, (size_t)((ws_max_B + 15) / 16) * 4, s));   // tile counters (self-resetting afterwards)
     }
-    const long long tiles = (B + 15) / 16;
-    // tiles x N-tiles waves; beyond ~3 waves per SIMD the waves stride over tiles with their weights in registers
-    const dim3 grid((unsigned)(tiles < 160 ? tiles : 160), (unsigned)(p.Hp / 16));
+    const dim3 grid(kp.gx, kp.gy);
     float *part = reinterpret_cast<float *>(ws + p.off_part);
     int *cnt = reinterpret_cast<int *>(ws + p.off_cnt);
-    // small batches: the latency-organised kernel; large ones: the tiled one (both give the same probabilities to rounding;
-    // where the switch sits: tools/exp/score_bench.py)
-    constexpr long long tiled_min = 512;
     ZT_PROF_BEGIN(s, P_SCORE);
-    if (B >= tiled_min) {
-        // 16 edges per workgroup while that fills the chip once (two workgroups fit a CU), 32 beyond
-        const int et = B <= 16 * 512 ? 16 : 32;
-        const size_t lds = ((size_t)3 * et * (p.Hp + 4) + 4 * 2 * et) * 4;
-        const int ki = (p.Hp == 304 ? 0 : 1) * 2 + (et == 16 ? 0 : 1);
-        const void *fns[4] = {reinterpret_cast<const void *>(k_affinity_tiled<19, 16>), reinterpret_cast<const void *>(k_affinity_tiled<19, 32>),
-                              reinterpret_cast<const void *>(k_affinity_tiled<13, 16>), reinterpret_cast<const void *>(k_affinity_tiled<13, 32>)};
-        ZT_HIP(set_dynamic_lds(fns[ki], lds));
-        const unsigned wgs = (unsigned)((B + et - 1) / et);
-        if (ki == 0)      k_affinity_tiled<19, 16><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
-        else if (ki == 1) k_affinity_tiled<19, 32><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
-        else if (ki == 2) k_affinity_tiled<13, 16><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
-        else              k_affinity_tiled<13, 32><<<wgs, 256, lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
-    } else if (p.Hp == 304) k_affinity<19><<<grid, 64, 0, s>>>(emb_dev, B, H, packed, wt->fc2_b, part, cnt, prob_dev);
-    else                    k_affinity<13><<<grid, 64, 0, s>>>(emb_dev, B, H, packed, wt->fc2_b, part, cnt, prob_dev);
+    int rc = ZT_OK;
+    switch (kp.form) {
+    case AffForm::latency:
+        rc = dispatch<13, 19>(kp.KC, [&](auto kc) {
+            k_affinity<kc.value><<<grid, kp.threads, 0, s>>>(emb_dev, B, H, packed, wt->fc2_b, part, cnt, prob_dev);
+            return (int)ZT_OK;
+        });
+        break;
+    case AffForm::tiled:
+        rc = dispatch<13, 19>(kp.KC, [&](auto kc) {
+            return dispatch<16, 32>(kp.ET, [&](auto et) {
+                const void *fn = reinterpret_cast<const void *>(k_affinity_tiled<kc.value, et.value>);
+                ZT_HIP(set_dynamic_lds(fn, kp.lds));
+                k_affinity_tiled<kc.value, et.value><<<grid, kp.threads, kp.lds, s>>>(emb_dev, B, H, packed, wt->fc2_b, prob_dev);
+                return (int)ZT_OK;
+            });
+        });
+        break;
+    case AffForm::gen_latency:
+        k_affinity_gen<<<grid, kp.threads, 0, s>>>(emb_dev, B, H, packed, wt->fc2_b, part, cnt, prob_dev);
+        break;
+    default:
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_affinity_gen_tiled), kp.lds));
+        k_affinity_gen_tiled<<<grid, kp.threads, kp.lds, s>>>(emb_dev, B, H, wt->fc1_w, wt->fc1_b, wt->fc2_w, wt->fc2_b, prob_dev);
+        break;
+    }
     ZT_PROF_END(s, P_SCORE);
+    if (rc != ZT_OK) return rc;
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

@@ -41,6 +41,10 @@ int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, in
 int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F, int32_t T, int32_t gru_choice,
                         int32_t msg_choice, int32_t held, int32_t out_form, int32_t hg, int32_t out_D, int32_t out_M,
                         int32_t gx, int64_t out_N, int32_t same_memory, int64_t *out);
+/* Test hook: the eval link scorer's kernel for one batch (zt::affinity_kernel_plan, host code only).  choice: the
+ * ZT_CHOICE_SCORE selection.  out[7] = form (0 refused, 1 latency, 2 tiled, 3 generic latency, 4 generic tiled: the ZT_SCORE_*
+ * values), KC, ET (the specialised forms' template arguments, else 0), grid x, grid y, threads per workgroup, dynamic LDS. */
+int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64_t *out);
 
 #ifdef __cplusplus
 }

@@ -140,3 +140,12 @@ extern "C" int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim,
     for (int i = 0; i < 14; ++i) out[i] = v[i];
     return ZT_OK;
 }
+
+extern "C" int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64_t *out)
+{
+    if (!out) return ZT_ERR_ARG;
+    const AffinityPlan ap = affinity_kernel_plan(B, H, choice);
+    const int64_t v[7] = {(int64_t)ap.form, ap.KC, ap.ET, ap.gx, ap.gy, ap.threads, (int64_t)ap.lds};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return ZT_OK;
+}

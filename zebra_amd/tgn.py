@@ -116,7 +116,8 @@ class TGN(torch.nn.Module):
     def _affinity_state(self, max_B, who="direct"):
         """(workspace, weights struct, weights_ready) of the HIP scorer for one CONSUMER -- "direct": score_device, which
         packs the weights in the call that finds them changed; "pipe": the native pipeline, which packs them in its next
-        whole-batch step, on its own stream -- ; None when the hidden width has no kernel.  Each consumer has its own
+        whole-batch step, on its own stream -- ; None when the hidden width has no kernel (zt_affinity_workspace_bytes: H % 4 == 0
+        and 4 <= H <= 768, the training scorer's widths).  Each consumer has its own
         workspace (packed weights, partial scores, arrival counters) and its own packed-for key: the two pack at different
         times and run on different streams (round-4 advisor)."""
         a = self.affinity_score
@@ -141,7 +142,8 @@ class TGN(torch.nn.Module):
     @torch.no_grad()
     def score_device(self, emb):
         """sigmoid(affinity_score([src | src], [dst | neg])) for the [3B, H] embeddings of a batch -> float32 [2B]:
-        the B positive probabilities, then the B negative ones (compute_edge_probabilities' tail, eval mode)."""
+        the B positive probabilities, then the B negative ones (compute_edge_probabilities' tail, eval mode).  zt_affinity for
+        every hidden width it takes (H % 4 == 0, 4 <= H <= 768); torch's MergeLayer for the others."""
         B = emb.shape[0] // 3
         st = self._affinity_state(B)
         if st is None:
@@ -172,7 +174,8 @@ class TGN(torch.nn.Module):
 
     def enable_scoring(self, on=True):
         """With the native pipeline: every whole-batch step also scores its 2B pairs behind its aggregation
-        (zt_pipeline_set_scoring); ``last_prob()`` returns the last step's probabilities."""
+        (zt_pipeline_set_scoring); ``last_prob()`` returns the last step's probabilities.  ValueError where the hidden width
+        has no HIP scorer (H % 4 != 0 or H > 768): the native step has no torch fallback."""
         self._score_on = bool(on)
         self._pipe_scoring_sync(force=True)
 
