@@ -460,11 +460,16 @@ int zt_rnn_update(float *memory_dev, float *last_update_dev,
 /*   compact rows of a training step.                                          */
 /* ------------------------------------------------------------------------ */
 /* C[M][N] = op(A)[M][K] op(B)[K][N] (+ C if accumulate), row-major float32;
- * op(A)(m, k) = trans_a ? A[k * lda + m] : A[m * lda + k], likewise B. */
+ * op(A)(m, k) = trans_a ? A[k * lda + m] : A[m * lda + k], likewise B.  All four
+ * (trans_a, trans_b) forms exist.  A and B may be NULL when K == 0 (C = 0, or C kept
+ * if accumulate); M == 0 or N == 0 writes nothing.  A leading dimension smaller than
+ * the row it strides over -- lda < (trans_a ? M : K), ldb < (trans_b ? K : N),
+ * ldc < N -- is refused with ZT_ERR_ARG before any launch (rows would overlap). */
 int zt_gemm_f32(const float *A_dev, const float *B_dev, float *C_dev, int64_t M, int64_t N,
                 int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t trans_a,
                 int32_t trans_b, int32_t accumulate, void *stream);
-/* out[c] (+)= sum over rows of X[r][c] (bias gradients). */
+/* out[c] (+)= sum over rows of X[r][c] (bias gradients); rows == 0: zeros, or out kept
+ * if accumulate.  ldx < cols is refused with ZT_ERR_ARG before any launch. */
 int zt_colsum_f32(const float *X_dev, int64_t rows, int64_t cols, int64_t ldx, float *out_dev,
                   int32_t accumulate, void *stream);
 /* The batch's own rows of the lazily updated memory -- get_updated_memory(...)[nodes]

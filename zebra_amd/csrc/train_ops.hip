@@ -267,6 +267,13 @@ extern "C" int zt_gemm_f32(const float *A_dev, const float *B_dev, float *C_dev,
         set_error("zt_gemm_f32: bad argument");
         return ZT_ERR_ARG;
     }
+    // a leading dimension below the row it strides over makes rows overlap: two workgroups then write the same C, or the
+    // operand read is not the matrix the caller means -- refused here, before any launch
+    if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N) {
+        set_error("zt_gemm_f32: leading dimension smaller than the row (lda %lld, ldb %lld, ldc %lld for M %lld, N %lld, K %lld)",
+                  (long long)lda, (long long)ldb, (long long)ldc, (long long)M, (long long)N, (long long)K);
+        return ZT_ERR_ARG;
+    }
     return gemm(A_dev, B_dev, C_dev, M, N, K, lda, ldb, ldc, trans_a != 0, trans_b != 0, accumulate != 0, (hipStream_t)stream);
 }
 
@@ -274,6 +281,10 @@ extern "C" int zt_colsum_f32(const float *X_dev, int64_t rows, int64_t cols, int
                              void *stream)
 {
     if (rows < 0 || cols < 0 || (cols > 0 && (!out_dev || (rows > 0 && !X_dev)))) { set_error("zt_colsum_f32: bad argument"); return ZT_ERR_ARG; }
+    if (ldx < cols) {        // (rows that overlap: the sums would be of other elements than the caller's matrix)
+        set_error("zt_colsum_f32: leading dimension smaller than the row (ldx %lld for cols %lld)", (long long)ldx, (long long)cols);
+        return ZT_ERR_ARG;
+    }
     if (cols == 0) return ZT_OK;
     k_colsum<<<(unsigned)((cols + 63) / 64), 64 * CS_WAVES, 0, (hipStream_t)stream>>>(X_dev, rows, cols, ldx, out_dev, accumulate != 0);
     ZT_LAUNCH_CHECK();
