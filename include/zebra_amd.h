@@ -251,9 +251,58 @@ int zt_csr_find_before(const zt_csr *c, int32_t v, double t, int64_t *count,
                        int32_t *nbr_host, int32_t *eid_host, double *ts_host,
                        int64_t cap);
 
+/* The pruning query has two forms (the reference bounds neither --n_degree nor
+ * --n_layer, train.py:25,28; a walk emits width + width^2 + ... + width^depth
+ * states per query):
+ *   lds        the candidate list and the frontier of a query live in LDS, one
+ *              wavefront per query: up to 1280 states and a frontier
+ *              (width^(depth-1)) of up to 512 entries.  Needs no preparation.
+ *   workspace  the same arrays live in a slab of device memory that the CSR
+ *              handle holds (zt_csr_reserve_pruning): up to
+ *              ZT_PRUNE_WS_MAX_STATES states.  One workgroup per slab takes
+ *              queries worker, worker + grid, ...
+ * Both are bit-identical to the reference.  zt_prune_plan is where the form is
+ * decided (host code only, no GPU call); the query entry points and the
+ * reservation go through it. */
+#define ZT_PRUNE_FORM_REFUSED 0
+#define ZT_PRUNE_FORM_LDS 1
+#define ZT_PRUNE_FORM_WORKSPACE 2
+#define ZT_PRUNE_WS_MAX_STATES (1 << 18) /* sum_{d<=depth} width^d of the workspace form (50 x 3 = 127 550, 10 x 5 = 111 110) */
+#define ZT_PRUNE_WS_MAX_SLABS 768        /* slabs of one reservation: what an MI355X keeps resident -- 256 compute units x 3
+                                          * workgroups of 256 threads (the kernel's 140 vector registers: 3 waves per SIMD) */
+#define ZT_PRUNE_PLAN_FIELDS 10
+/* out[ZT_PRUNE_PLAN_FIELDS], all int64:
+ *   [0] form               ZT_PRUNE_FORM_*
+ *   [1] cap_c              states a query may emit: sum width^d (saturated at ZT_PRUNE_WS_MAX_STATES + 1 when refused for it)
+ *   [2] cap_f              widest frontier: width^(depth-1)
+ *   [3] models per launch  more models run as several launches
+ *   [4] slab_bytes         workspace: bytes of one slab (0 for lds)
+ *   [5] slabs              workspace: min(max_bytes / slab_bytes, ZT_PRUNE_WS_MAX_SLABS); 0 -> refused
+ *   [6] grid               workspace: workgroups of a launch at most (= slabs; a launch takes min(queries, slabs));
+ *                          lds: 0 (a launch takes ceil(queries / 4))
+ *   [7] threads            per workgroup
+ *   [8] lds_bytes          per workgroup (lds: dynamic; workspace: static)
+ *   [9] states             = [1]
+ * ZT_ERR_ARG for non-positive width / depth / n_models / k, a negative max_bytes or NULL out; else ZT_OK -- a refused form
+ * is an answer, not a failure (zt_last_error says why). */
+int zt_prune_plan(int32_t width, int32_t depth, int32_t n_models, int32_t k, int64_t max_bytes, int64_t *out);
+/* Plans the workspace form for (width, depth, n_models, k) and allocates slabs x slab_bytes of device memory on the handle
+ * (slabs: as many as fit max_bytes, at most ZT_PRUNE_WS_MAX_SLABS).  A later call replaces the reservation.  A shape the
+ * lds form takes reserves nothing (an earlier reservation stays) and returns ZT_OK.  ZT_ERR_UNSUPPORTED: max_bytes below
+ * one slab (the message names the bytes one slab needs), or a shape beyond ZT_PRUNE_WS_MAX_STATES.  A reservation covers
+ * every query whose cap_c and cap_f are within the reserved ones, at any k and any number of models (more models than it
+ * was planned for run as several launches).  The workspace serves one launch at a time: a launch records an event on its
+ * stream and the next launch, if on another stream, waits for it on the device -- no host synchronisation and no
+ * allocation inside a query call.  Calls on one handle are not thread-safe against each other. */
+int zt_csr_reserve_pruning(zt_csr *c, int32_t width, int32_t depth, int32_t n_models, int32_t k, int64_t max_bytes);
+/* Frees the reservation (after the launches that use it); zt_csr_destroy does so too. */
+int zt_csr_release_pruning(zt_csr *c);
+
 /* NeighborFinder.get_pruned_topk (utils/util.py:185-276): rows whose
  * dictionary is empty are left untouched, all others fully written (the
- * reference mutates caller-owned arrays in place). */
+ * reference mutates caller-owned arrays in place).  A shape beyond the lds
+ * form needs a reservation that covers it on the handle, else
+ * ZT_ERR_UNSUPPORTED. */
 int zt_pruned_topk(const zt_csr *c, const int32_t *q_nodes_dev,
                    const double *q_ts_dev, int64_t nq, int32_t width,
                    int32_t depth, double alpha, double beta, int32_t k,

@@ -8,6 +8,10 @@
 // states are merged keeping the reference's dictionary order (first
 // occurrence) and its left-to-right float64 summation order; selection uses
 // the exact numba argsort semantics.
+//
+// Walks that do not fit LDS take the workspace form, k_pruned_topk_ws: the same
+// query over a slab of device memory the handle reserves, one workgroup per slab.
+// prune_plan decides between the two.
 #include "numba_sort.hpp"
 
 #include <algorithm>
@@ -25,6 +29,13 @@ struct zt_csr {
     std::vector<long long> h_indptr;
     std::vector<int> h_nbr, h_eid;
     std::vector<double> h_ts;
+    // the workspace form's reservation (zt_csr_reserve_pruning); the query entry points take the handle const
+    mutable void *ws = nullptr;              // device: ws_slabs x ws_slab_bytes
+    long long ws_slab_bytes = 0;
+    int ws_slabs = 0, ws_cap_c = 0, ws_cap_f = 0, ws_models = 0;
+    hipEvent_t ws_event = nullptr;           // recorded after every workspace launch
+    mutable hipStream_t ws_stream = nullptr; // the stream of the last one
+    mutable bool ws_used = false;
 };
 
 namespace {
@@ -342,6 +353,399 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
     }
 }
 
+// ---------------------------------------------------------------------------
+// The workspace form: the same query with its per-query arrays in a slab of device memory (zt_csr_reserve_pruning), for
+// walks that do not fit LDS (the reference bounds neither --n_degree nor --n_layer).  Persistent: worker = one WORKGROUP of
+// WS_THREADS threads, one slab each, queries worker, worker + grid, ...  A workgroup rather than a wavefront: a walk of
+// 10^4..10^5 states is latency-bound on global memory, and four waves keep four times the loads in flight per slab (slabs
+// are megabytes each, so slabs, not lanes, are what a budget runs out of); the barrier between stages and a 256-bin LDS
+// histogram for the selection come with it.  Stage by stage the semantics are k_pruned_topk's; what differs is how the
+// two quadratic steps are done:
+//   merge   first occurrences through a hash table in the slab: a slot is claimed for a (edge, node) key by compare-and-swap
+//           and keeps the SMALLEST list index of its key (atomicMin), which does not depend on who inserts first;
+//   select  the cut (k-th largest value) by an 8-bit-per-pass radix select on the float64 patterns -- weights are positive
+//           and finite, where pattern order is value order --, then ranks by counting among the k candidates at or above
+//           it.  A tie group that reaches the kept ranks (or a NaN / negative pattern) takes the literal replay
+//           numba_argsort_seq over all n, on one lane: n log n, correct first.
+// A slab is reused from query to query: every array is written before it is read within a query (the hash table is
+// cleared over the slots this query uses).
+// ---------------------------------------------------------------------------
+constexpr int WS_THREADS = 256;
+constexpr int WS_WAVES = WS_THREADS / WAVE;
+struct WsLds {                                // k_pruned_topk_ws's LDS: the selection's scratch
+    double cval[256];                         // the candidates at or above the cut: value,
+    int cidx[256];                            // list index
+    int sel[256];                             // the kept set, in output order
+    int hist[256];                            // radix select: one pass's bins
+    int stk[96];                              // numba_argsort_seq's stack
+    int wt[WS_WAVES];                         // block_scan_excl
+    int bin, want, cnt;
+};
+constexpr int WS_STATIC_LDS = (int)sizeof(WsLds);
+constexpr u64 WS_EMPTY = ~0ull;              // no (edge, node) key: edge ids are < 2^31
+
+__host__ __device__ inline size_t ws_table_slots(long long n)           // power of two, load factor <= 1/2
+{
+    size_t t = 64;
+    while (t < 2 * (size_t)n) t <<= 1;
+    return t;
+}
+__host__ __device__ inline size_t ws_slab_bytes(int cap_c, int cap_f, int M)
+{
+    const size_t b = (2 + (size_t)M) * align16((size_t)cap_c * 8) + align16((size_t)cap_c * 4) + 3 * align16((size_t)cap_f * 4) +
+                     (1 + (size_t)M) * align16((size_t)cap_f * 8) + align16(ws_table_slots(cap_c) * 8) + align16(ws_table_slots(cap_c) * 4);
+    return (b + 255) & ~(size_t)255;
+}
+
+struct PruneSlab {
+    u64 *key;               // [cap_c] the LDS form's arrays ...
+    double *ts;             // [cap_c]
+    double *w;              // [M][cap_c]
+    int *perm;              // [cap_c] owner entry (walk) / hash slot, then first occurrence (merge) / the replay's permutation
+    int *f_cnt, *f_off, *f_ngh;   // [cap_f]
+    long long *f_lo;        // [cap_f]
+    double *f_base;         // [M][cap_f]
+    u64 *h_key;             // [slots] ... and the merge's hash table: the key that owns the slot
+    int *h_first;           // [slots] smallest list index of that key
+};
+
+__device__ inline PruneSlab carve_slab(char *base, int cap_c, int cap_f, int M)
+{
+    PruneSlab L;
+    char *p = base;
+    L.key = reinterpret_cast<u64 *>(p); p += align16((size_t)cap_c * 8);
+    L.ts = reinterpret_cast<double *>(p); p += align16((size_t)cap_c * 8);
+    L.w = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_c * 8);
+    L.perm = reinterpret_cast<int *>(p); p += align16((size_t)cap_c * 4);
+    L.f_cnt = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
+    L.f_off = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
+    L.f_ngh = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
+    L.f_lo = reinterpret_cast<long long *>(p); p += align16((size_t)cap_f * 8);
+    L.f_base = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_f * 8);
+    L.h_key = reinterpret_cast<u64 *>(p); p += align16(ws_table_slots(cap_c) * 8);
+    L.h_first = reinterpret_cast<int *>(p);
+    return L;
+}
+
+// exclusive scan of v over the workgroup (thread order) and its total; wt: WS_WAVES ints of LDS.  Two barriers.
+__device__ inline int block_scan_excl(int v, int *wt, int *total)
+{
+    const int lane = lane_id(), wv = threadIdx.x / WAVE;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == WAVE - 1) wt[wv] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < WS_WAVES; ++q) { const int t = wt[q]; base += q < wv ? t : 0; tot += t; }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
+    const long long *__restrict__ indptr, const int *__restrict__ nbr, const int *__restrict__ eid,
+    const double *__restrict__ ats, long long num_nodes, const int *__restrict__ q_nodes,
+    const double *__restrict__ q_ts, long long nq, int width, int depth, PruneModels pm, int k,
+    int *out_nodes, int *out_eidx, float *out_dt, float *out_w, long long out_stride, int *status, int cap_c, int cap_f,
+    int slab_models, char *slabs, long long slab_bytes, int zero_empty)
+{
+    __shared__ WsLds S;
+    const int M = pm.M;
+    const PruneSlab L = carve_slab(slabs + (size_t)blockIdx.x * (size_t)slab_bytes, cap_c, cap_f, slab_models);
+    const size_t wst = align16((size_t)cap_c * 8) / 8, bst = align16((size_t)cap_f * 8) / 8;   // model strides (doubles)
+    const int tid = threadIdx.x, lane = lane_id();
+    for (long long qi = blockIdx.x; qi < nq; qi += gridDim.x) {        // (every branch below is uniform over the workgroup)
+        __syncthreads();                                               // the previous query's LDS and slab reads are done
+        const int qn = q_nodes[qi];
+        const double qt = q_ts[qi];
+        if (qn < 0 || qn >= num_nodes) {
+            if (tid == 0) atomicExch(status, ZT_ERR_RANGE);
+            if (zero_empty)
+                for (int m = 0; m < M; ++m) {
+                    const long long ob = (long long)m * out_stride + qi * k;
+                    for (int j = tid; j < k; j += WS_THREADS) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
+                }
+            continue;
+        }
+
+        // ---- the walk: k_pruned_topk's, level by level, over the workgroup ----
+        int n_cand = 0, fr_lo = 0, nf = 1;
+        for (int dep = 0; dep < depth; ++dep) {
+            // find_before of every frontier entry: a P-ary search by P lanes of one wave per entry
+            const int P = nf == 1 ? 64 : (nf == 2 ? 32 : (nf <= 4 ? 16 : 8));
+            const int epc = WS_THREADS / P;
+            const int g = tid / P, gl = lane / P, j = lane % P;
+            const u64 gmask = P == 64 ? ~0ull : ((1ull << P) - 1ull);
+            for (int f0 = 0; f0 < nf; f0 += epc) {
+                const int f = f0 + g;
+                const bool act = f < nf;
+                const int node = !act ? 0 : (dep == 0 ? qn : (int)(unsigned)(L.key[fr_lo + f] & 0xffffffffull));
+                const double t = !act ? 0.0 : (dep == 0 ? qt : L.ts[fr_lo + f]);
+                const long long lo0 = act ? indptr[node] : 0, hi0 = act ? indptr[node + 1] : 0;
+                long long lo = lo0, hi = hi0;                           // the answer (first index with ts >= t) is in [lo, hi]
+                while (__ballot(lo < hi) != 0ull) {
+                    const long long n = hi - lo;
+                    const bool open = lo < hi;
+                    const bool pred = open && ats[lo + (n * j) / P] < t;
+                    const int c = __popcll((__ballot(pred) >> (gl * P)) & gmask);
+                    if (open) {
+                        if (c == 0) hi = lo;
+                        else {
+                            const long long nlo = lo + (n * (c - 1)) / P + 1;
+                            hi = c < P ? lo + (n * c) / P : hi;
+                            lo = nlo;
+                        }
+                    }
+                }
+                if (act && j == 0) {
+                    const long long n_ngh = lo - lo0;
+                    L.f_ngh[f] = (int)n_ngh;
+                    L.f_lo[f] = lo0;
+                    L.f_cnt[f] = (int)(n_ngh < width ? n_ngh : width);
+                }
+            }
+            __syncthreads();
+            // exclusive scan of f_cnt
+            int n_new = 0;
+            for (int f0 = 0; f0 < nf; f0 += WS_THREADS) {
+                const int f = f0 + tid;
+                const int c = f < nf ? L.f_cnt[f] : 0;
+                int tot;
+                const int ex = block_scan_excl(c, S.wt, &tot);
+                if (f < nf) L.f_off[f] = n_new + ex;
+                n_new += tot;
+            }
+            if (n_new == 0) break;                                      // :234-235
+            if (n_cand + n_new > cap_c || nf > cap_f) break;            // (cannot happen: the plan's caps are sums of width^d)
+            __syncthreads();
+            // per entry and model: weight of its most recent neighbour (:208-209); who owns which new state
+            for (int f = tid; f < nf; f += WS_THREADS) {
+                const int c = L.f_cnt[f], o = n_cand + L.f_off[f];
+                if (c > 0) {
+                    const long long n_ngh = L.f_ngh[f];
+                    for (int m = 0; m < M; ++m) {
+                        const double alpha = pm.alpha[m], beta = pm.beta[m];
+                        const double qw = dep == 0 ? 1.0 : L.w[m * wst + fr_lo + f];
+                        const double norm = beta / (1.0 - beta) * (1.0 - numba_int_pow(beta, n_ngh));   // :208
+                        L.f_base[m * bst + f] = (alpha != 0.0 && dep == 0) ? qw * (1.0 - alpha) * beta / norm * alpha
+                                                                           : qw * (1.0 - alpha) * beta / norm;   // :209
+                    }
+                    for (int z = 0; z < c; ++z) L.perm[o + z] = f;
+                }
+            }
+            __syncthreads();
+            // the new states, most recent first (:211-232): one lane per (entry, z)
+            for (int i = tid; i < n_new; i += WS_THREADS) {
+                const int f = L.perm[n_cand + i];
+                const int z = i - L.f_off[f];
+                const long long p = L.f_lo[f] + L.f_ngh[f] - (z + 1);
+                L.key[n_cand + i] = ((u64)(unsigned)eid[p] << 32) | (u64)(unsigned)nbr[p];
+                L.ts[n_cand + i] = ats[p];
+                for (int m = 0; m < M; ++m) {
+                    const double beta = pm.beta[m];
+                    double weight = L.f_base[m * bst + f];
+                    for (int q = 0; q < z; ++q) weight = weight * beta;             // weight *= beta after every state
+                    L.w[m * wst + n_cand + i] = weight;
+                }
+            }
+            __syncthreads();
+            fr_lo = n_cand;
+            nf = n_new;
+            n_cand += n_new;
+        }
+        if (n_cand == 0) {                                              // :241-242, row untouched (zero_empty: written as zeros)
+            if (zero_empty)
+                for (int m = 0; m < M; ++m) {
+                    const long long ob = (long long)m * out_stride + qi * k;
+                    for (int j = tid; j < k; j += WS_THREADS) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
+                }
+            continue;
+        }
+
+        // ---- merge duplicate states: dict[state] += weight in occurrence order (:222-225) ----
+        // perm[c] = first occurrence of c's state.  The table's words are written by atomics and read back past the L1.
+        {
+            const int tsz = (int)ws_table_slots(n_cand);
+            const unsigned hmask = (unsigned)tsz - 1u;
+            for (int s = tid; s < tsz; s += WS_THREADS) { st_agent(&L.h_key[s], WS_EMPTY); st_agent(&L.h_first[s], 0x7fffffff); }
+            __syncthreads();
+            for (int c = tid; c < n_cand; c += WS_THREADS) {
+                const u64 kc = L.key[c];
+                unsigned h = (unsigned)((kc * 0x9E3779B97F4A7C15ull) >> 40) & hmask;
+                for (;;) {
+                    const u64 prev = atomicCAS(&L.h_key[h], WS_EMPTY, kc);
+                    if (prev == WS_EMPTY || prev == kc) break;
+                    h = (h + 1u) & hmask;
+                }
+                atomicMin(&L.h_first[h], c);
+                L.perm[c] = (int)h;
+            }
+            __syncthreads();
+        }
+        int dup = 0, mis = 0;
+        for (int c = tid; c < n_cand; c += WS_THREADS) {
+            const int fi = ld_agent(&L.h_first[L.perm[c]]);
+            mis |= (fi != c && L.ts[fi] != L.ts[c]) ? 1 : 0;
+            dup |= fi != c ? 1 : 0;
+            L.perm[c] = fi;
+        }
+        mis = __syncthreads_or(mis);
+        if (mis) {
+            // the dictionary key is (edge, node, time): equal (edge, node) with different times cannot come out of one
+            // adjacency, but if it ever does, redo the search comparing the time on every hit (the LDS form's fallback)
+            dup = 0;
+            for (int c = tid; c < n_cand; c += WS_THREADS) {
+                const u64 kc = L.key[c];
+                const double tc = L.ts[c];
+                int fi = c;
+                for (int q = 0; q < c; ++q)
+                    if (L.key[q] == kc && L.ts[q] == tc) { fi = q; break; }
+                L.perm[c] = fi;
+                dup |= fi != c ? 1 : 0;
+            }
+        }
+        const bool any_dup = __syncthreads_or(dup) != 0;
+        int nd = n_cand;
+        if (any_dup) {
+            // a leader's value is the left-to-right sum of its occurrences: later occurrences are added in index order by
+            // ONE wave, lane m doing model m (a lane's accesses to one address execute in program order)
+            if (tid < WAVE) {
+                for (int c0 = 0; c0 < n_cand; c0 += WAVE) {
+                    const int c = c0 + lane;
+                    const int pc = c < n_cand ? L.perm[c] : c;
+                    u64 dm = __ballot(pc != c);
+                    while (dm != 0ull) {
+                        const int sl = __ffsll((long long)dm) - 1;
+                        dm &= dm - 1ull;
+                        const int cc = c0 + sl;
+                        const int lead = __shfl(pc, sl);
+                        if (lane < M) L.w[lane * wst + lead] = L.w[lane * wst + lead] + L.w[lane * wst + cc];
+                    }
+                }
+            }
+            __syncthreads();
+            // compact the leaders in order (dictionary insertion order): a chunk's reads come before the scan's barriers, its
+            // writes after them, and land at or below the chunk (pos <= c)
+            nd = 0;
+            for (int c0 = 0; c0 < n_cand; c0 += WS_THREADS) {
+                const int c = c0 + tid;
+                const bool lead = c < n_cand && L.perm[c] == c;
+                const u64 kc = lead ? L.key[c] : 0;
+                const double tc = lead ? L.ts[c] : 0.0;
+                double wc[PR_MAX_MODELS];
+#pragma unroll
+                for (int m = 0; m < PR_MAX_MODELS; ++m) wc[m] = (lead && m < M) ? L.w[m * wst + c] : 0.0;
+                int tot;
+                const int ex = block_scan_excl(lead ? 1 : 0, S.wt, &tot);
+                if (lead) {
+                    const int pos = nd + ex;
+                    L.key[pos] = kc; L.ts[pos] = tc;
+#pragma unroll
+                    for (int m = 0; m < PR_MAX_MODELS; ++m) if (m < M) L.w[m * wst + pos] = wc[m];
+                }
+                nd += tot;
+            }
+            __syncthreads();
+        }
+
+        // ---- select and emit (:240-276), model by model ----
+        for (int m = 0; m < M; ++m) {
+            const long long ob = (long long)m * out_stride + qi * k;
+            const double *wm = L.w + m * wst;
+            if (nd <= k) {
+                for (int j = tid; j < k; j += WS_THREADS) {
+                    const bool a = j < nd;
+                    out_nodes[ob + j] = a ? (int)(unsigned)(L.key[j] & 0xffffffffull) : 0;
+                    out_eidx[ob + j] = a ? (int)(unsigned)(L.key[j] >> 32) : 0;
+                    out_w[ob + j] = a ? (float)wm[j] : 0.f;
+                    const float tsf = a ? (float)L.ts[j] : 0.f;
+                    out_dt[ob + j] = (float)(qt - (double)tsf);
+                }
+                continue;
+            }
+            // np.argsort(values)[-k:] in numba's order (topk_select_any's contract, numba_sort.hpp)
+            const int drop = nd - k;
+            int odd = 0;                                                // a pattern whose order is not its value's: negative, NaN
+            for (int c = tid; c < nd; c += WS_THREADS) {
+                const double v = wm[c];
+                odd |= ((u64)__double_as_longlong(v) >> 63) != 0ull || v != v ? 1 : 0;
+            }
+            bool slow = __syncthreads_or(odd) != 0;
+            if (!slow) {
+                // the cut: the k-th largest pattern, eight bits per pass
+                u64 prefix = 0ull, pmask = 0ull;
+                int want = k, eq_cut = 0;
+                for (int shift = 56; shift >= 0; shift -= 8) {
+                    S.hist[tid] = 0;
+                    __syncthreads();
+                    for (int c = tid; c < nd; c += WS_THREADS) {
+                        const u64 b = (u64)__double_as_longlong(wm[c]);
+                        if ((b & pmask) == prefix) atomicAdd(&S.hist[(int)((b >> shift) & 255ull)], 1);
+                    }
+                    __syncthreads();
+                    if (tid == 0) {
+                        int acc = 0, b = 255;
+                        for (; b > 0; --b) {
+                            if (acc + S.hist[b] >= want) break;
+                            acc += S.hist[b];
+                        }
+                        S.bin = b; S.want = want - acc;
+                    }
+                    __syncthreads();
+                    prefix |= (u64)S.bin << shift;
+                    pmask |= 255ull << shift;
+                    want = S.want;
+                    eq_cut = S.hist[S.bin];
+                    __syncthreads();
+                }
+                // `want` of the eq_cut values equal to the cut are kept: more than one of them is a tie group that reaches the
+                // kept ranks
+                slow = eq_cut > 1;
+                if (!slow) {
+                    if (tid == 0) S.cnt = 0;
+                    __syncthreads();
+                    for (int c = tid; c < nd; c += WS_THREADS) {
+                        const double v = wm[c];
+                        if ((u64)__double_as_longlong(v) >= prefix) {   // exactly k of them
+                            const int pos = atomicAdd(&S.cnt, 1);
+                            if (pos < 256) { S.cidx[pos] = c; S.cval[pos] = v; }
+                        }
+                    }
+                    __syncthreads();
+                    int tie = 0;
+                    if (tid < k) {
+                        const double v = S.cval[tid];
+                        int lt = 0, eq = 0;
+                        for (int q = 0; q < k; ++q) { const double x = S.cval[q]; lt += x < v ? 1 : 0; eq += x == v ? 1 : 0; }
+                        tie = eq > 1 ? 1 : 0;
+                        if (!tie) S.sel[lt] = S.cidx[tid];               // rank among all nd = drop + lt
+                    }
+                    slow = __syncthreads_or(tie) != 0;
+                }
+            }
+            if (slow) {
+                if (tid == 0) numba_argsort_seq(wm, nd, L.perm, S.stk);
+                __syncthreads();
+                for (int q = tid; q < k; q += WS_THREADS) S.sel[q] = L.perm[drop + q];
+                __syncthreads();
+            }
+            for (int j = tid; j < k; j += WS_THREADS) {
+                const int c = S.sel[j];
+                out_nodes[ob + j] = (int)(unsigned)(L.key[c] & 0xffffffffull);
+                out_eidx[ob + j] = (int)(unsigned)(L.key[c] >> 32);
+                out_w[ob + j] = (float)wm[c];
+                out_dt[ob + j] = (float)(qt - (double)(float)L.ts[c]);
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace
 
 static int csr_upload(zt_csr *c)
@@ -450,6 +854,7 @@ extern "C" int zt_csr_export(const zt_csr *c, int64_t *indptr, int32_t *nbr, int
 extern "C" int zt_csr_destroy(zt_csr *c)
 {
     if (!c) return ZT_OK;
+    (void)zt_csr_release_pruning(c);
     (void)hipFree(c->indptr); (void)hipFree(c->nbr); (void)hipFree(c->eid); (void)hipFree(c->ts);
     delete c;
     return ZT_OK;
@@ -470,19 +875,142 @@ extern "C" int zt_csr_find_before(const zt_csr *c, int32_t v, double t, int64_t 
     return ZT_OK;
 }
 
+// Which form a pruning query of this shape takes and what it needs: the ONE place that decides (pruned_launch, the
+// reservation and zt_prune_plan all come here).  Host code, no GPU call.
+struct PrunePlan {
+    int form;                    // ZT_PRUNE_FORM_*
+    long long cap_c, cap_f;      // states a query may emit (sum width^d), widest frontier (width^(depth-1))
+    int models;                  // per launch
+    long long slab_bytes, slabs;
+    int grid, threads;
+    long long lds;
+};
+
+static PrunePlan prune_plan(int width, int depth, int n_models, int k, long long max_bytes)
+{
+    PrunePlan p = {};
+    long long cap = 0, lvl = 1, front = 1;
+    for (int d = 0; d < depth; ++d) {
+        front = lvl; lvl *= width; cap += lvl;
+        if (cap > ZT_PRUNE_WS_MAX_STATES) { cap = (long long)ZT_PRUNE_WS_MAX_STATES + 1; break; }
+    }
+    p.cap_c = cap; p.cap_f = front;
+    if (k > ZT_MAX_K_WIDE || cap > ZT_PRUNE_WS_MAX_STATES) {
+        set_error("zt_pruned_topk: k=%d width=%d depth=%d exceeds what the pruning query takes "
+                  "(k<=%d, sum width^d<=%d)", k, width, depth, ZT_MAX_K_WIDE, (int)ZT_PRUNE_WS_MAX_STATES);
+        p.form = ZT_PRUNE_FORM_REFUSED;
+        return p;
+    }
+    if (cap <= MAX_CAND && front <= MAX_FRONT) {
+        // as many models per launch as the workgroup's LDS allows (at least one)
+        int mm = n_models < PR_MAX_MODELS ? n_models : PR_MAX_MODELS;
+        while (mm > 1 && prune_lds_bytes((int)cap, (int)front, mm, k) * PR_WAVES > 64 * 1024) --mm;
+        p.form = ZT_PRUNE_FORM_LDS;
+        p.models = mm;
+        p.threads = WAVE * PR_WAVES;
+        p.lds = (long long)(prune_lds_bytes((int)cap, (int)front, mm, k) * PR_WAVES);
+        return p;
+    }
+    p.form = ZT_PRUNE_FORM_WORKSPACE;
+    p.models = n_models < PR_MAX_MODELS ? n_models : PR_MAX_MODELS;
+    p.slab_bytes = (long long)ws_slab_bytes((int)cap, (int)front, p.models);
+    p.slabs = max_bytes / p.slab_bytes;
+    if (p.slabs > ZT_PRUNE_WS_MAX_SLABS) p.slabs = ZT_PRUNE_WS_MAX_SLABS;
+    p.grid = (int)p.slabs;
+    p.threads = WS_THREADS;
+    p.lds = (long long)WS_STATIC_LDS;
+    if (p.slabs == 0) {
+        set_error("zt_csr_reserve_pruning: width=%d depth=%d models=%d needs %lld bytes for one slab, the budget is %lld",
+                  width, depth, p.models, p.slab_bytes, max_bytes);
+        p.form = ZT_PRUNE_FORM_REFUSED;
+    }
+    return p;
+}
+
+extern "C" int zt_prune_plan(int32_t width, int32_t depth, int32_t n_models, int32_t k, int64_t max_bytes, int64_t *out)
+{
+    if (width <= 0 || depth <= 0 || n_models <= 0 || k <= 0 || max_bytes < 0 || !out) {
+        set_error("zt_prune_plan: bad argument");
+        return ZT_ERR_ARG;
+    }
+    const PrunePlan p = prune_plan(width, depth, n_models, k, max_bytes);
+    out[0] = p.form; out[1] = p.cap_c; out[2] = p.cap_f; out[3] = p.models; out[4] = p.slab_bytes; out[5] = p.slabs;
+    out[6] = p.grid; out[7] = p.threads; out[8] = p.lds; out[9] = p.cap_c;
+    return ZT_OK;
+}
+
+extern "C" int zt_csr_release_pruning(zt_csr *c)
+{
+    if (!c) return ZT_OK;
+    if (c->ws) {
+        if (c->ws_used) ZT_HIP(hipEventSynchronize(c->ws_event));      // the launches that use it
+        ZT_HIP(hipFree(c->ws));
+    }
+    if (c->ws_event) ZT_HIP(hipEventDestroy(c->ws_event));
+    c->ws = nullptr; c->ws_event = nullptr; c->ws_stream = nullptr; c->ws_used = false;
+    c->ws_slab_bytes = 0; c->ws_slabs = c->ws_cap_c = c->ws_cap_f = c->ws_models = 0;
+    return ZT_OK;
+}
+
+extern "C" int zt_csr_reserve_pruning(zt_csr *c, int32_t width, int32_t depth, int32_t n_models, int32_t k, int64_t max_bytes)
+{
+    if (!c || width <= 0 || depth <= 0 || n_models <= 0 || k <= 0 || max_bytes < 0) {
+        set_error("zt_csr_reserve_pruning: bad argument");
+        return ZT_ERR_ARG;
+    }
+    const PrunePlan p = prune_plan(width, depth, n_models, k, max_bytes);
+    if (p.form == ZT_PRUNE_FORM_REFUSED) return ZT_ERR_UNSUPPORTED;
+    if (p.form == ZT_PRUNE_FORM_LDS) return ZT_OK;                     // nothing to reserve
+    int rc = zt_csr_release_pruning(c);
+    if (rc != ZT_OK) return rc;
+    ZT_HIP(hipMalloc(&c->ws, (size_t)p.slabs * (size_t)p.slab_bytes));
+    if (hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming) != hipSuccess) {
+        (void)hipFree(c->ws); c->ws = nullptr; c->ws_event = nullptr;
+        set_error("zt_csr_reserve_pruning: hipEventCreateWithFlags failed");
+        return ZT_ERR_HIP;
+    }
+    c->ws_slab_bytes = p.slab_bytes; c->ws_slabs = (int)p.slabs;
+    c->ws_cap_c = (int)p.cap_c; c->ws_cap_f = (int)p.cap_f; c->ws_models = p.models;
+    return ZT_OK;
+}
+
 // one launch for up to PR_MAX_MODELS models; out arrays are [M][nq][k]
 static int pruned_launch(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
                          int32_t depth, int M, const double *alpha, const double *beta, int32_t k, int32_t *on, int32_t *oe,
                          float *od, float *ow, int32_t *status_dev, hipStream_t s, bool zero_empty = false)
 {
-    long long cap = 0, lvl = 1, front = 1;
-    for (int d = 0; d < depth; ++d) { front = lvl; lvl *= width; cap += lvl; if (cap > MAX_CAND) break; }
-    if (k > ZT_MAX_K_WIDE || cap > MAX_CAND || front > MAX_FRONT) {
-        set_error("zt_pruned_topk: k=%d width=%d depth=%d exceeds the LDS-resident limits "
-                  "(k<=%d, sum width^d<=%d)", k, width, depth, ZT_MAX_K_WIDE, MAX_CAND);
-        return ZT_ERR_UNSUPPORTED;
+    const PrunePlan plan = prune_plan(width, depth, M, k, 0x7fffffffffffffffll);
+    if (plan.form == ZT_PRUNE_FORM_REFUSED) return ZT_ERR_UNSUPPORTED;
+    if (plan.form == ZT_PRUNE_FORM_WORKSPACE) {
+        if (!c->ws || plan.cap_c > c->ws_cap_c || plan.cap_f > c->ws_cap_f) {
+            set_error("zt_pruned_topk: k=%d width=%d depth=%d exceeds the LDS-resident limits (k<=%d, sum width^d<=%d) and the "
+                      "handle holds no workspace that covers it: use a narrower walk or reserve a workspace: "
+                      "zt_csr_reserve_pruning", k, width, depth, ZT_MAX_K_WIDE, MAX_CAND);
+            return ZT_ERR_UNSUPPORTED;
+        }
+        // the workspace serves one launch at a time: behind the previous one, on whatever stream that ran
+        if (c->ws_used && c->ws_stream != s) ZT_HIP(hipStreamWaitEvent(s, c->ws_event, 0));
+        const int grid = (int)(nq < c->ws_slabs ? nq : c->ws_slabs);
+        for (int m0 = 0; m0 < M;) {
+            const int mm = M - m0 < c->ws_models ? M - m0 : c->ws_models;
+            PruneModels pm;
+            pm.M = mm;
+            for (int q = 0; q < mm; ++q) { pm.alpha[q] = alpha[m0 + q]; pm.beta[q] = beta[m0 + q]; }
+            const size_t o = (size_t)m0 * nq * k;
+            ZT_PROF_BEGIN(s, P_PRUNE);
+            k_pruned_topk_ws<<<grid, WS_THREADS, 0, s>>>(c->indptr, c->nbr, c->eid, c->ts, c->N, q_nodes_dev, q_ts_dev, nq, width,
+                                                         depth, pm, k, on + o, oe + o, od + o, ow + o, (long long)nq * k,
+                                                         status_dev, c->ws_cap_c, c->ws_cap_f, c->ws_models, (char *)c->ws,
+                                                         c->ws_slab_bytes, zero_empty ? 1 : 0);
+            ZT_PROF_END(s, P_PRUNE);
+            ZT_LAUNCH_CHECK();
+            m0 += mm;
+        }
+        ZT_HIP(hipEventRecord(c->ws_event, s));
+        c->ws_stream = s; c->ws_used = true;
+        return ZT_OK;
     }
-    const int cap_c = (int)cap, cap_f = (int)front;
+    const int cap_c = (int)plan.cap_c, cap_f = (int)plan.cap_f;
 #ifdef ZT_DIAG
     static const int dbg_stop = getenv("ZT_PRUNE_STOP") ? atoi(getenv("ZT_PRUNE_STOP")) : 0;   // diagnostic builds only (WRONG results): 1 walk only, 2 + merge
 #else

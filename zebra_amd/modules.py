@@ -581,7 +581,15 @@ class GraphDiffusionEmbedding(nn.Module):
         return ([a for a in on.cpu().numpy()], [a for a in oe.cpu().numpy()], [a for a in od.cpu().numpy()],
                 [a for a in ow.cpu().numpy()])
 
+    def ensure_pruning_workspace(self):
+        """A walk beyond the LDS form of the pruning query (the reference bounds neither --n_degree nor --n_layer) runs over a
+        device workspace the finder holds: make sure the finder about to be queried -- it changes under
+        TGN.set_neighbor_finder -- has one for this module's (width, depth, n_tppr, k).  Cheap when it has."""
+        self.neighbor_finder.ensure_pruning(self.width, self.depth, self.n_tppr, self.k,
+                                            getattr(self.args, "pruning_workspace_bytes", 1 << 30))
+
     def pruning_topk_device(self, nodes_d, ts_d, check_status=True):
+        self.ensure_pruning_workspace()
         n = nodes_d.numel()
         on = torch.zeros((self.n_tppr, n, self.k), dtype=torch.int32, device=self.device)
         oe = torch.zeros_like(on)

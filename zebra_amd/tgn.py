@@ -326,6 +326,7 @@ class TGN(torch.nn.Module):
         if em.tppr_strategy == "streaming":
             d.tppr = em.tppr_finder._live.h
         else:
+            em.ensure_pruning_workspace()               # the side stream's query takes the workspace form through this handle
             d.csr = em.neighbor_finder._h
             d.width, d.depth = em.width, em.depth
             for q, (a, bb) in enumerate(zip(em.alpha_list, em.beta_list)):

@@ -344,6 +344,7 @@ class NeighborFinder:
         self._ts = np.empty(self._e2, np.float64)
         check(lib().zt_csr_export(self._h, ptr(self._indptr), ptr(self._nbr), ptr(self._eid), ptr(self._ts)))
         self._status = torch.zeros(1, dtype=torch.int32, device=self._dev)
+        self._reserved = None                # plan of the pruning workspace this finder holds (reserve_pruning)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -375,6 +376,45 @@ class NeighborFinder:
         lo, hi = self._indptr[src_idx], self._indptr[src_idx + 1]
         i = int(np.searchsorted(self._ts[lo:hi], cut_time))
         return self._nbr[lo:lo + i], self._eid[lo:lo + i], self._ts[lo:lo + i]
+
+    # ---- walks that do not fit LDS: the workspace form (csrc/tppr_prune.hip: k_pruned_topk_ws) ----
+    @staticmethod
+    def pruning_plan(width, depth, n_models=1, k=20, max_bytes=1 << 30):
+        """What a pruning query of this shape runs as (zt_prune_plan: host code, no GPU call): dict(form = "lds" |
+        "workspace" | "refused", cap_c, cap_f, models_per_launch, slab_bytes, slabs, grid, threads, lds_bytes, states)."""
+        out = (C.c_int64 * 10)()
+        check(lib().zt_prune_plan(C.c_int32(width), C.c_int32(depth), C.c_int32(n_models), C.c_int32(k),
+                                  C.c_int64(max_bytes), out), "zt_prune_plan")
+        d = dict(zip(("form", "cap_c", "cap_f", "models_per_launch", "slab_bytes", "slabs", "grid", "threads", "lds_bytes",
+                      "states"), [int(x) for x in out]))
+        d["form"] = ("refused", "lds", "workspace")[d["form"]]
+        return d
+
+    def reserve_pruning(self, width, depth, n_models=1, k=20, max_bytes=1 << 30):
+        """Reserves the device workspace a (width, depth) walk beyond the LDS form needs (zt_csr_reserve_pruning): as many
+        slabs as fit ``max_bytes``.  A later call replaces the reservation; a shape the LDS form takes reserves nothing.
+        ValueError when ``max_bytes`` is below one slab or the shape is beyond the workspace form.  Returns the plan."""
+        check(lib().zt_csr_reserve_pruning(self._h, C.c_int32(width), C.c_int32(depth), C.c_int32(n_models), C.c_int32(k),
+                                           C.c_int64(max_bytes)), "zt_csr_reserve_pruning")
+        plan = self.pruning_plan(width, depth, n_models, k, max_bytes)
+        if plan["form"] == "workspace":
+            self._reserved = plan
+        return plan
+
+    def release_pruning(self):
+        check(lib().zt_csr_release_pruning(self._h), "zt_csr_release_pruning")
+        self._reserved = None
+
+    def ensure_pruning(self, width, depth, n_models, k, max_bytes=1 << 30):
+        """Makes sure this finder can answer (width, depth) queries: reserves a workspace when the plan says so and the
+        reservation it holds does not cover the shape."""
+        plan = self.pruning_plan(width, depth, n_models, k, max_bytes)
+        if plan["form"] != "workspace":
+            return plan                                            # lds: nothing to do; refused: the query says why
+        r = getattr(self, "_reserved", None)
+        if r is None or r["cap_c"] < plan["cap_c"] or r["cap_f"] < plan["cap_f"]:
+            return self.reserve_pruning(width, depth, n_models, k, max_bytes)
+        return r
 
     def pruned_topk_device(self, nodes_d, ts_d, width, depth, alpha, beta, k, on, oe, od, ow, check_status=True):
         check(lib().zt_pruned_topk(self._h, ptr(nodes_d), ptr(ts_d), C.c_int64(nodes_d.numel()), C.c_int32(width),
