@@ -755,9 +755,26 @@ int zt_affinity_train_backward(const float *emb_dev, int64_t B, int32_t H,
                                void *stream);
 /* evaluation/evaluation.py:34-45 and train.py:218-227 without the host: out_dev[0..3) (float64) =
  * (average_precision_score, roc_auc_score, mean(pos >= neg)) of B positive and B negative scores, scikit-learn's
- * definitions (distinct thresholds, ties included); accumulate != 0 adds to out_dev.  2B <= 16384. */
+ * definitions (distinct thresholds, ties included); accumulate != 0 adds to out_dev.  One single-workgroup kernel in one of
+ * two forms: up to 8192 pairs the 2B scores are sorted together as 64-bit (key | label) words; from 8193 to 16384 pairs the
+ * positive and the negative 32-bit keys are sorted as two runs and walked together (the 64-bit layout would not fit the
+ * 160 KB of LDS).  Float64 sums in a fixed order, no float atomics: two calls give the same bits.  B > 16384:
+ * ZT_ERR_UNSUPPORTED before any device call.  zt_link_metrics_plan is where the form is decided (host code only). */
 int zt_link_metrics(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev,
                     int32_t accumulate, void *stream);
+#define ZT_METRICS_FORM_REFUSED 0
+#define ZT_METRICS_FORM_SINGLE 1 /* one bitonic sort of 2B 64-bit (key | label) words */
+#define ZT_METRICS_FORM_SPLIT 2  /* positives and negatives sorted as two runs of 32-bit keys */
+#define ZT_METRICS_MAX_B 16384
+#define ZT_METRICS_PLAN_FIELDS 4
+/* out[ZT_METRICS_PLAN_FIELDS], all int64:
+ *   [0] form        ZT_METRICS_FORM_*  (refused: B <= 0 or B > ZT_METRICS_MAX_B; the other fields are 0 then)
+ *   [1] threads     of the one workgroup
+ *   [2] n2          keys in LDS, padding included (single: the next power of two >= max(1024, 2B); split: twice the next
+ *                   power of two >= B)
+ *   [3] lds_bytes   dynamic LDS (single: 8 n2; split: 4 n2)
+ * ZT_ERR_ARG for NULL out; else ZT_OK -- a refused form is an answer, not a failure. */
+int zt_link_metrics_plan(int64_t B, int64_t *out);
 /* The scorer as the tail of the native step: with non-NULL weights every zt_pipeline_step_ahead over a WHOLE batch
  * (rows [0, 3B)) also scores that batch's 2B pairs behind its aggregation (main stream).  prob_dev: [2][2 * max_B]
  * floats, consecutive steps alternate between the halves.  workspace_dev as for
@@ -766,6 +783,19 @@ int zt_link_metrics(const float *pos_dev, const float *neg_dev, int64_t B, doubl
 int zt_pipeline_set_scoring(zt_pipeline *p, const zt_affinity_weights *weights, void *workspace_dev,
                             float *prob_dev);
 int zt_pipeline_last_scores(zt_pipeline *p, void *stream, float **prob_out, int64_t *B_out);
+/* The metrics as the tail of the scorer: with non-NULL sum_dev every SCORED step (scoring on, a whole batch) is followed by
+ * the zt_link_metrics kernel over that step's probabilities -- the first B floats of its half of prob_dev against the next B.
+ * The kernel ADDS the batch's (AP, AUC, accuracy) to sum_dev [3] (float64; the caller zeroes it) and, where per_batch_dev
+ * [cap][3] is given, writes them to row i, i = the batches measured since this call.  It runs on the message stream behind the
+ * scorer, never on the main stream; all of them on that one stream, in batch order: a run gives the same bits every time.
+ * The main stream waits for a half's metrics kernel before the scorer rewrites that half two steps later.
+ * NULL sum_dev: off (zt_pipeline_set_scoring with NULL weights turns it off as well).  Refused before anything is enqueued:
+ * scoring off, cap < 0 (ZT_ERR_ARG); max_B > ZT_METRICS_MAX_B, an exchange attached -- a sharded step is never scored --
+ * (ZT_ERR_UNSUPPORTED); and, by the step itself, a scored step that would write row cap (ZT_ERR_ARG).
+ * zt_pipeline_metrics: makes `stream` wait for the last metrics kernel enqueued and returns in *n_out the batches measured
+ * since the set call (the counterpart of zt_pipeline_last_scores). */
+int zt_pipeline_set_metrics(zt_pipeline *p, double *sum_dev, double *per_batch_dev, int64_t cap);
+int zt_pipeline_metrics(zt_pipeline *p, void *stream, int64_t *n_out);
 
 /* ------------------------------------------------------------------------ */
 /* One-node multi-GPU exchange of touched rows.  The reference  */

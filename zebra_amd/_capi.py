@@ -32,6 +32,7 @@ SYMBOLS = [
     "zt_exchange_unique_id", "zt_exchange_create", "zt_exchange_set_tables", "zt_exchange_destroy", "zt_pipeline_set_exchange",
     "zt_rnn_update", "zt_rnn_train_forward", "zt_rnn_train_backward", "zt_pipeline_set_cell",
     "zt_affinity_train_workspace_bytes", "zt_affinity_train_forward", "zt_affinity_train_backward",
+    "zt_link_metrics_plan", "zt_pipeline_set_metrics", "zt_pipeline_metrics",
 ]
 
 
@@ -47,6 +48,8 @@ AGG_GENERIC = 1
 OUT_TILED, OUT_LATENCY, OUT_PERSIST = 1, 2, 3
 GRU_TILE, GRU_SPLIT = 1, 2
 CELL_GRU, CELL_RNN = 0, 1                                       # zt_pipeline_set_cell
+METRICS_FORM_REFUSED, METRICS_FORM_SINGLE, METRICS_FORM_SPLIT = 0, 1, 2   # zt_link_metrics_plan
+METRICS_MAX_B = 16384
 MSG_ONE, MSG_TWO = 1, 2
 
 
@@ -166,6 +169,13 @@ def check(rc, what=""):
     if rc in (ZT_ERR_ARG, ZT_ERR_UNSUPPORTED):
         raise ValueError(text)
     raise ZebraError(text)
+
+
+def link_metrics_plan(B):
+    """zt_link_metrics_plan: which form of the metrics kernel takes B pairs and how it is launched (host code only)."""
+    out = (C.c_int64 * 4)()
+    check(lib().zt_link_metrics_plan(C.c_int64(B), out), "zt_link_metrics_plan")
+    return dict(form=int(out[0]), threads=int(out[1]), n2=int(out[2]), lds_bytes=int(out[3]))
 
 
 def ptr(t):

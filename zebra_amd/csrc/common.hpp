@@ -112,6 +112,24 @@ struct AffinityPlan {
 // Pure host code (no HIP calls).  A function of (B, H, choice) alone -- never of the workspace's max_B: the pipeline and a direct
 // call pick the same kernel for the same batch.  choice: ZT_CHOICE_SCORE (a form the width cannot take: the library's pick)
 AffinityPlan affinity_kernel_plan(int64_t B, int H, int choice);
+// The link-metrics kernel for B positive and B negative scores (scoring.hip: link_metrics_plan).  single = k_link_metrics (the 2B
+// scores as u64 (key | label) in one bitonic sort, n2 = the padded length, 8 bytes each); split = k_link_metrics_split (the B
+// positive and the B negative 32-bit keys sorted as two runs of n2 / 2 each, 4 bytes per key, then walked together).  One
+// workgroup either way.  The values are the ZT_METRICS_FORM_* of zt_link_metrics_plan.
+enum class MetForm { refused = 0, single = 1, split = 2 };
+constexpr int64_t METRICS_SINGLE_MAX_B = 8192, METRICS_MAX_B = 16384;
+struct MetricsPlan {
+    MetForm form;
+    unsigned threads;
+    int n2;                // keys in LDS (padding included)
+    size_t lds;            // dynamic LDS
+};
+// Pure host code (no HIP calls): refused for B <= 0 and beyond METRICS_MAX_B pairs
+MetricsPlan link_metrics_plan(int64_t B);
+// zt_link_metrics with a second destination: row (or NULL) receives the batch's three values whatever `accumulate` does to out
+// (the metrics tail of the native step, pipeline.hip: the running sum and the per-batch table from one launch)
+int link_metrics_launch(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int accumulate, double *row_dev,
+                        hipStream_t stream);
 // The output layers of an embed call, held back (embed_ex: `defer`) so that gru_update_ex can launch them in ONE kernel with the
 // GRU update (k_out_gru, memory_update.hip): the two are independent apart from the memory rows the source path reads --
 // the GRU half waits for those reads before it writes (a gate in the GRU workspace whose whole state is device memory: a

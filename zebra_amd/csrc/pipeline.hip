@@ -91,6 +91,16 @@ struct zt_pipeline {
     hipEvent_t scored[2];
     int score_n;               // scorings enqueued so far (parity = which half / which event)
     int64_t score_B;           // batch size of the last one
+    // zt_pipeline_set_metrics: the metrics kernel (scoring.hip) behind every scoring, on the MESSAGE stream -- idle from `msgs_done`
+    // until the next step's message build, which is ready long before the aggregation that needs it ends.  Not on the main
+    // stream, whose chain bounds the small-batch steps, and not on a stream of its own ("Hardware
+    // queues").  One stream, batch order: the sums are added in batch order.  met_done[h] is recorded behind the kernel that
+    // reads half h of `prob`; the main stream waits for it before the scorer rewrites that half two steps later.
+    double *met_sum, *met_rows;   // [3] running sums (NULL: off); [met_cap][3] per batch, or NULL
+    int64_t met_cap, met_n;       // rows of met_rows; batches measured since zt_pipeline_set_metrics
+    hipEvent_t met_done[2];
+    bool met_pending[2];          // a metrics kernel on half h has been enqueued and the main stream has not waited for it since
+    int met_last;                 // the half of the last metrics kernel enqueued (-1: none)
     zt_exchange *xchg;         // zt_pipeline_set_exchange: the row exchange of a multi-GPU run at the end of every step (or NULL)
     // Failure latch in host-mapped memory (as zt_tppr's): a bounded in-kernel wait of the step's own kernels that gives up
     // (the gate of k_out_gru / k_out_gru2, memory_update.hip) writes ZT_ERR_TIMEOUT here at system scope, and the NEXT step
@@ -335,6 +345,9 @@ extern "C" int zt_pipeline_create(zt_pipeline **out, const zt_pipeline_desc *des
     ZT_HIP(hipEventCreateWithFlags(&p->msgs_done, hipEventDisableTiming | zt::sync_event_flags()));
     ZT_HIP(hipEventCreateWithFlags(&p->scored[0], hipEventDisableTiming | zt::sync_event_flags()));
     ZT_HIP(hipEventCreateWithFlags(&p->scored[1], hipEventDisableTiming | zt::sync_event_flags()));
+    ZT_HIP(hipEventCreateWithFlags(&p->met_done[0], hipEventDisableTiming | zt::sync_event_flags()));
+    ZT_HIP(hipEventCreateWithFlags(&p->met_done[1], hipEventDisableTiming | zt::sync_event_flags()));
+    p->met_last = -1;
     ZT_HIP(hipStreamCreateWithFlags(&p->plan_s, hipStreamNonBlocking));
     ZT_HIP(hipEventCreateWithFlags(&p->entry, hipEventDisableTiming | zt::sync_event_flags()));
     // a slot holds one batch of max_B edges, or a group of smaller ones up to what one T-PPR launch covers
@@ -371,6 +384,7 @@ extern "C" int zt_pipeline_destroy(zt_pipeline *p)
     (void)hipStreamDestroy(p->side); (void)hipStreamDestroy(p->main_s); (void)hipStreamDestroy(p->plan_s);
     (void)hipStreamDestroy(p->msg_s);
     (void)hipEventDestroy(p->scored[0]); (void)hipEventDestroy(p->scored[1]);
+    (void)hipEventDestroy(p->met_done[0]); (void)hipEventDestroy(p->met_done[1]);
     (void)hipEventDestroy(p->entry); (void)hipEventDestroy(p->step_begin); (void)hipEventDestroy(p->msgs_done);
     if (p->latch_host) (void)hipHostFree(p->latch_host);
     delete p;
@@ -399,7 +413,7 @@ extern "C" int zt_pipeline_set_stats(zt_pipeline *p, float *avg_topk_dev)
 extern "C" int zt_pipeline_set_scoring(zt_pipeline *p, const zt_affinity_weights *weights, void *workspace_dev, float *prob_dev)
 {
     if (!p) return ZT_ERR_ARG;
-    if (weights == nullptr) { p->aff_on = false; return ZT_OK; }
+    if (weights == nullptr) { p->aff_on = false; p->met_sum = nullptr; p->met_rows = nullptr; return ZT_OK; }   // (no scores: no metrics tail)
     if (!workspace_dev || !prob_dev || !weights->fc1_w || !weights->fc1_b || !weights->fc2_w || !weights->fc2_b) {
         set_error("zt_pipeline_set_scoring: NULL buffer");
         return ZT_ERR_ARG;
@@ -421,6 +435,34 @@ extern "C" int zt_pipeline_last_scores(zt_pipeline *p, void *stream, float **pro
     ZT_HIP(hipStreamWaitEvent((hipStream_t)stream, p->scored[par], 0));
     *prob_out = p->prob + (size_t)par * 2 * p->d.max_B;
     if (B_out) *B_out = p->score_B;
+    return ZT_OK;
+}
+
+extern "C" int zt_pipeline_set_metrics(zt_pipeline *p, double *sum_dev, double *per_batch_dev, int64_t cap)
+{
+    if (!p) { set_error("zt_pipeline_set_metrics: NULL pipeline"); return ZT_ERR_ARG; }
+    // (a kernel already enqueued keeps its event: the main stream still waits for it before its half is rewritten)
+    if (sum_dev == nullptr) { p->met_sum = nullptr; p->met_rows = nullptr; p->met_cap = 0; p->met_n = 0; return ZT_OK; }
+    if (!p->aff_on) { set_error("zt_pipeline_set_metrics: scoring is off (zt_pipeline_set_scoring first)"); return ZT_ERR_ARG; }
+    if (cap < 0 || (per_batch_dev != nullptr && cap == 0)) { set_error("zt_pipeline_set_metrics: a per-batch table of %lld rows", (long long)cap); return ZT_ERR_ARG; }
+    if (p->d.max_B > zt::METRICS_MAX_B) {
+        set_error("zt_pipeline_set_metrics: batches of up to %lld pairs, the metrics kernel takes at most %lld", (long long)p->d.max_B,
+                  (long long)zt::METRICS_MAX_B);
+        return ZT_ERR_UNSUPPORTED;
+    }
+    if (p->xchg != nullptr) {
+        set_error("zt_pipeline_set_metrics: an exchange is attached (a sharded step scores nothing)");
+        return ZT_ERR_UNSUPPORTED;
+    }
+    p->met_sum = sum_dev; p->met_rows = per_batch_dev; p->met_cap = per_batch_dev ? cap : 0; p->met_n = 0;
+    return ZT_OK;
+}
+
+extern "C" int zt_pipeline_metrics(zt_pipeline *p, void *stream, int64_t *n_out)
+{
+    if (!p) { set_error("zt_pipeline_metrics: NULL pipeline"); return ZT_ERR_ARG; }
+    if (p->met_last >= 0) ZT_HIP(hipStreamWaitEvent((hipStream_t)stream, p->met_done[p->met_last], 0));
+    if (n_out) *n_out = p->met_n;
     return ZT_OK;
 }
 
@@ -481,6 +523,12 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
     const bool pruning = d.csr != nullptr;
     const bool whole = row_lo == 0 && row_hi == 3 * B;
     const int want = pruning ? 1 : p->group;
+    const bool scored = n_rows > 0 && p->aff_on && whole, measured = scored && p->met_sum != nullptr;
+    if (measured && p->met_rows != nullptr && p->met_n >= p->met_cap) {      // (before anything of this step is enqueued)
+        set_error("zt_pipeline_step: the per-batch metrics table has %lld rows and this step is batch %lld", (long long)p->met_cap,
+                  (long long)p->met_n);
+        return ZT_ERR_ARG;
+    }
     // the shard of a LATER batch is the same fraction of its rows (callers shard every batch alike)
     auto shard_of = [&](int64_t Bn, int64_t *lo, int64_t *hi) {
         *lo = Bn == B ? row_lo : (row_lo * 3 * Bn) / (3 * B);
@@ -632,8 +680,13 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
                            n_rows > 0 ? &p->out_gru : nullptr, p->cell);
     if (rc != ZT_OK) return rc;
     p->gru_ready = true;
-    if (n_rows > 0 && p->aff_on && whole) {      // compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written
+    if (scored) {                                // compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written
         const int par = p->score_n & 1;
+        float *prob = p->prob + (size_t)par * 2 * d.max_B;
+        if (p->met_pending[par]) {               // the metrics kernel of two steps ago still reads this half
+            ZT_HIP(hipStreamWaitEvent(p->main_s, p->met_done[par], 0));
+            p->met_pending[par] = false;
+        }
         rc = zt_affinity(out_emb_dev, B, d.D * (d.M + 1), &p->aff, p->prob + (size_t)par * 2 * d.max_B, p->aff_ws, d.max_B,
                          p->aff_ready ? 1 : 0, p->main_s);
         if (rc != ZT_OK) return rc;
@@ -641,6 +694,15 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
         p->aff_ready = true;
         p->score_n++;
         p->score_B = B;
+        if (measured) {                          // AP / AUC / accuracy of these 2B probabilities, beside the next step (message stream)
+            ZT_HIP(hipStreamWaitEvent(p->msg_s, p->scored[par], 0));
+            rc = zt::link_metrics_launch(prob, prob + B, B, p->met_sum, 1, p->met_rows ? p->met_rows + 3 * p->met_n : nullptr, p->msg_s);
+            if (rc != ZT_OK) return rc;
+            ZT_HIP(hipEventRecord(p->met_done[par], p->msg_s));
+            p->met_pending[par] = true;
+            p->met_last = par;
+            p->met_n++;
+        }
     }
     if (d.proj_table != nullptr && wm_p == nullptr) {
         char *gw = reinterpret_cast<char *>(d.gru_ws);

@@ -26,7 +26,9 @@
 // zt_link_metrics replaces the per-batch scikit-learn calls of evaluation/evaluation.py:34-45 and train.py:218-227
 // (average_precision_score, roc_auc_score, accuracy of argmax) with ONE single-workgroup kernel: bitonic sort of the 2B
 // scores in LDS, two scans (true positives; start of every run of equal scores) and the two curve sums over the distinct
-// thresholds in float64, ties handled as scikit-learn does (zebra_amd/evaluation.py states the definitions).
+// thresholds in float64, ties handled as scikit-learn does (zebra_amd/evaluation.py states the definitions).  Beyond 8192
+// pairs a second form sorts the positives' and the negatives' 32-bit keys as two runs (k_link_metrics_split); which form a
+// batch takes is decided in ONE place, link_metrics_plan (host code).
 #include "common.hpp"
 #include "scoring_fwd.hpp"
 
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_affinity_gen_tiled(const floa
 // metrics
 // ---------------------------------------------------------------------------------------------------------
 constexpr int MT_THREADS = 1024;
-constexpr int MT_MAX = 16384;            // scores per call (2B): 128 KB of LDS keys
+constexpr int MT_MAX = 16384;            // scores per call (2B) of the single form: 128 KB of LDS keys
 
 // float -> unsigned whose ascending order is the DESCENDING order of the floats (NaN-free scores)
 __device__ __forceinline__ unsigned desc_key(float x)
@@ -377,7 +379,7 @@ __device__ __forceinline__ unsigned desc_key(float x)
 }
 
 __global__ __launch_bounds__(MT_THREADS) void k_link_metrics(const float *__restrict__ pos, const float *__restrict__ neg, int B,
-                                                             int n2, double *out, int accumulate)
+                                                             int n2, double *out, int accumulate, double *row)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64 *key = reinterpret_cast<u64 *>(smem);                             // [n2] (score key << 32) | label
@@ -462,6 +464,84 @@ __global__ __launch_bounds__(MT_THREADS) void k_link_metrics(const float *__rest
         c /= (double)B;
         if (accumulate) { out[0] += a; out[1] += u; out[2] += c; }
         else { out[0] = a; out[1] = u; out[2] = c; }
+        if (row != nullptr) { row[0] = a; row[1] = u; row[2] = c; }
+    }
+}
+
+// first index of an ascending run a[0 .. n) whose key is >= v (lower) / > v (upper)
+__device__ __forceinline__ int run_lower(const unsigned *a, int n, unsigned v)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
+    return lo;
+}
+__device__ __forceinline__ int run_upper(const unsigned *a, int n, unsigned v)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
+    return lo;
+}
+
+// The wide form (8192 < B <= 16384 pairs): 2B u64 words do not fit the 160 KB of LDS, 2B 32-bit keys do.  The label leaves the
+// key: the B positive keys and the B negative keys are sorted as TWO runs (each padded to m2, one bitonic network over both:
+// a compare-exchange partner i ^ j, j < m2, never leaves its half) and the curves are read off the pair.  Per distinct score
+// the sums need only how many positives and how many negatives lie at or above it -- a position in the score's own run and a
+// binary search in the other; the order inside a run of equal scores never matters.  The terms are k_link_metrics' own, in the
+// same float64 expressions.  A threshold that no positive score takes adds (R_n - R_{n-1}) P_n = 0 to the average precision,
+// one that no negative score takes adds a trapezoid of width 0 to the AUC: the positives' distinct keys carry the first sum,
+// the negatives' the second.  Thread t takes elements t, t + 1024, ... of both runs; lanes, waves and thread 0 add in a fixed
+// order as above.
+__global__ __launch_bounds__(MT_THREADS) void k_link_metrics_split(const float *__restrict__ pos, const float *__restrict__ neg, int B,
+                                                                   int m2, double *out, int accumulate, double *row)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned *key = reinterpret_cast<unsigned *>(smem);                   // [2 m2]: the positives' keys, then the negatives'
+    __shared__ double red[3][MT_THREADS / 64];
+    const int tid = threadIdx.x, n2 = 2 * m2;
+    for (int i = tid; i < n2; i += MT_THREADS) {
+        const int q = i & (m2 - 1);
+        key[i] = q < B ? desc_key(i < m2 ? pos[q] : neg[q]) : 0xffffffffu; // padding sorts last (and is never looked at)
+    }
+    __syncthreads();
+    for (int k = 2; k <= m2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n2; i += MT_THREADS) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned a = key[i], b = key[l];
+                    const bool up = ((i & (m2 - 1)) & k) == 0;            // (the last stage, k = m2: both halves ascending)
+                    if ((a > b) == up) { key[i] = b; key[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    const unsigned *kp = key, *kn = key + m2;
+    const double np_ = (double)B, nn_ = (double)B;
+    double ap = 0.0, auc = 0.0, acc = 0.0;
+    for (int i = tid; i < B; i += MT_THREADS) {
+        const unsigned v = kp[i];
+        if (i == B - 1 || kp[i + 1] != v) {                               // the last positive of a distinct score
+            const double tps = (double)(i + 1), tb = (double)run_lower(kp, B, v), fps = (double)run_upper(kn, B, v);
+            ap += (tps / np_ - tb / np_) * (tps / (tps + fps));
+        }
+        const unsigned u = kn[i];
+        if (i == B - 1 || kn[i + 1] != u) {                               // the last negative of a distinct score
+            const double fps = (double)(i + 1), fb = (double)run_lower(kn, B, u);
+            const double tb = (double)run_lower(kp, B, u), tps = (double)run_upper(kp, B, u);
+            auc += (fps / nn_ - fb / nn_) * (tps / np_ + tb / np_) * 0.5;
+        }
+        acc += pos[i] >= neg[i] ? 1.0 : 0.0;
+    }
+    for (int d = 32; d > 0; d >>= 1) { ap += __shfl_down(ap, d); auc += __shfl_down(auc, d); acc += __shfl_down(acc, d); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ap; red[1][tid >> 6] = auc; red[2][tid >> 6] = acc; }
+    __syncthreads();
+    if (tid == 0) {
+        double a = 0.0, u = 0.0, c = 0.0;
+        for (int q = 0; q < MT_THREADS / 64; ++q) { a += red[0][q]; u += red[1][q]; c += red[2][q]; }
+        c /= (double)B;
+        if (accumulate) { out[0] += a; out[1] += u; out[2] += c; }
+        else { out[0] = a; out[1] = u; out[2] = c; }
+        if (row != nullptr) { row[0] = a; row[1] = u; row[2] = c; }
     }
 }
 
@@ -603,16 +683,58 @@ extern "C" int zt_affinity(const float *emb_dev, int64_t B, int32_t H, const zt_
     return ZT_OK;
 }
 
+// The one place that says which metrics kernel takes B pairs, with which launch parameters (common.hpp)
+MetricsPlan zt::link_metrics_plan(int64_t B)
+{
+    static_assert(2 * METRICS_SINGLE_MAX_B == MT_MAX, "the single form's u64 keys: 128 KB of LDS");
+    MetricsPlan mp{MetForm::refused, 0u, 0, 0u};
+    if (B <= 0 || B > METRICS_MAX_B) return mp;
+    mp.threads = MT_THREADS;
+    if (B <= METRICS_SINGLE_MAX_B) {
+        mp.form = MetForm::single;
+        mp.n2 = MT_THREADS;                                               // >= one element per thread keeps the chunks simple
+        while (mp.n2 < 2 * B) mp.n2 <<= 1;
+        mp.lds = (size_t)mp.n2 * 8;
+    } else {
+        mp.form = MetForm::split;
+        int m2 = MT_THREADS;
+        while (m2 < B) m2 <<= 1;
+        mp.n2 = 2 * m2;
+        mp.lds = (size_t)mp.n2 * 4;
+    }
+    return mp;
+}
+
+extern "C" int zt_link_metrics_plan(int64_t B, int64_t *out)
+{
+    if (!out) { set_error("zt_link_metrics_plan: NULL out"); return ZT_ERR_ARG; }
+    const MetricsPlan mp = link_metrics_plan(B);
+    out[0] = (int64_t)mp.form; out[1] = mp.threads; out[2] = mp.n2; out[3] = (int64_t)mp.lds;
+    return ZT_OK;
+}
+
+int zt::link_metrics_launch(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int accumulate, double *row_dev,
+                            hipStream_t stream)
+{
+    if (!pos_dev || !neg_dev || !out_dev || B <= 0) { set_error("zt_link_metrics: bad argument"); return ZT_ERR_ARG; }
+    const MetricsPlan mp = link_metrics_plan(B);
+    if (mp.form == MetForm::refused) {
+        set_error("zt_link_metrics: %lld pairs per call, at most %lld", (long long)B, (long long)METRICS_MAX_B);
+        return ZT_ERR_UNSUPPORTED;
+    }
+    if (mp.form == MetForm::single) {
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_link_metrics), mp.lds));
+        k_link_metrics<<<1, mp.threads, mp.lds, stream>>>(pos_dev, neg_dev, (int)B, mp.n2, out_dev, accumulate, row_dev);
+    } else {
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_link_metrics_split), mp.lds));
+        k_link_metrics_split<<<1, mp.threads, mp.lds, stream>>>(pos_dev, neg_dev, (int)B, mp.n2 / 2, out_dev, accumulate, row_dev);
+    }
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
 extern "C" int zt_link_metrics(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int32_t accumulate,
                                void *stream)
 {
-    if (!pos_dev || !neg_dev || !out_dev || B <= 0) { set_error("zt_link_metrics: bad argument"); return ZT_ERR_ARG; }
-    if (2 * B > MT_MAX) { set_error("zt_link_metrics: %lld scores per call, at most %d", (long long)(2 * B), MT_MAX); return ZT_ERR_UNSUPPORTED; }
-    int n2 = MT_THREADS;                                                  // >= one element per thread keeps the chunks simple
-    while (n2 < 2 * B) n2 <<= 1;
-    const size_t lds = (size_t)n2 * 8;
-    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_link_metrics), lds));
-    k_link_metrics<<<1, MT_THREADS, lds, (hipStream_t)stream>>>(pos_dev, neg_dev, (int)B, n2, out_dev, accumulate);
-    ZT_LAUNCH_CHECK();
-    return ZT_OK;
+    return link_metrics_launch(pos_dev, neg_dev, B, out_dev, accumulate, nullptr, (hipStream_t)stream);
 }

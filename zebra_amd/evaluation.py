@@ -65,11 +65,13 @@ def accuracy(pos, neg):
 
 def link_metrics(pos, neg, out=None):
     """(average_precision, roc_auc, accuracy) of one batch as a float64[3] tensor on the scores' device.  CUDA scores of
-    up to 8192 pairs go through ONE HIP kernel (zt_link_metrics, csrc/scoring.hip: bitonic sort in LDS + the two curve
-    sums; ``out`` given: the values are ADDED to it there, no extra op); anything else through the torch ops above --
-    the same definitions, which the CPU tests hold against scikit-learn and the GPU tests against each other."""
+    up to 16384 pairs go through ONE HIP kernel (zt_link_metrics, csrc/scoring.hip: bitonic sort in LDS + the two curve
+    sums, in the form zt_link_metrics_plan picks -- one sort of (key | label) words up to 8192 pairs, the positives and the
+    negatives as two sorted runs beyond; ``out`` given: the values are ADDED to it there, no extra op); anything else through
+    the torch ops above -- the same definitions, which the CPU tests hold against scikit-learn and the GPU tests against each
+    other."""
     pos, neg = pos.reshape(-1), neg.reshape(-1)
-    if pos.is_cuda and pos.dtype == torch.float32 and neg.dtype == torch.float32 and 0 < pos.numel() == neg.numel() <= 8192:
+    if pos.is_cuda and pos.dtype == torch.float32 and neg.dtype == torch.float32 and 0 < pos.numel() == neg.numel() <= 16384:
         import ctypes as C
         from ._capi import check, lib, ptr, stream_ptr
         acc = out if out is not None else torch.zeros(3, dtype=torch.float64, device=pos.device)
@@ -84,9 +86,18 @@ def link_metrics(pos, neg, out=None):
 
 
 @torch.no_grad()
-def eval_edge_prediction(model, negative_edge_sampler, data, n_neighbors, batch_size):
+def eval_edge_prediction(model, negative_edge_sampler, data, n_neighbors, batch_size, native=False):
     """evaluation/evaluation.py:7-48 with the same protocol and return value (mean AP, mean AUC, mean
-    accuracy over the batches); probabilities and metrics stay on the device, the host reads once."""
+    accuracy over the batches); probabilities and metrics stay on the device, the host reads once.
+
+    ``native=True``: the whole pass as ONE native call (TGN.run_device with the scorer and the metrics tail of the step,
+    zt_pipeline_set_metrics) instead of a Python iteration, a staging copy and a host synchronisation per batch.  It needs a
+    model with ``enable_pipeline()`` (RuntimeError otherwise; batches of at most the pipeline's ``max_batch``) and turns
+    scoring and metrics on if they are off.  The negatives are drawn batch by batch first, in the same order (the sampler's
+    RandomState sequence is the loop's); the T-PPR and step status words are checked once at the end.  The ``average_topk``
+    statistics the stepwise pass collects for the embedding module are not collected in this mode."""
+    if native:
+        return _eval_edge_prediction_native(model, negative_edge_sampler, data, batch_size)
     assert negative_edge_sampler.seed is not None
     negative_edge_sampler.reset_random_state()
     model = model.eval()
@@ -102,4 +113,39 @@ def eval_edge_prediction(model, negative_edge_sampler, data, n_neighbors, batch_
             acc = torch.zeros(3, dtype=torch.float64, device=pos.device)
         link_metrics(pos, neg, out=acc)
     out = (acc / nb).cpu().numpy()
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+@torch.no_grad()
+def _eval_edge_prediction_native(model, negative_edge_sampler, data, batch_size):
+    from . import _capi
+    assert negative_edge_sampler.seed is not None
+    negative_edge_sampler.reset_random_state()
+    model = model.eval()
+    if getattr(model, "_pipe", None) is None:
+        raise RuntimeError("eval_edge_prediction(native=True) needs a model with enable_pipeline()")
+    n = data.n_interactions
+    nb = math.ceil(n / batch_size)
+    if nb == 0:
+        return float("nan"), float("nan"), float("nan")
+    cuts = [(b * batch_size, min(n, (b + 1) * batch_size)) for b in range(nb)]
+    negatives = np.concatenate([np.asarray(negative_edge_sampler.sample(e - s)[1]) for s, e in cuts])
+    if not getattr(model, "_score_on", False):
+        model.enable_scoring()
+    if not getattr(model, "_met_on", False):
+        model.enable_metrics()
+    with torch.cuda.stream(model.main_stream):
+        model.metrics(reset=True)
+        split = _capi.to_device(model.device, [np.ascontiguousarray(data.sources[:n], np.int32),
+                                               np.ascontiguousarray(data.destinations[:n], np.int32),
+                                               np.ascontiguousarray(negatives, np.int32),
+                                               np.ascontiguousarray(data.timestamps[:n], np.float64),
+                                               np.ascontiguousarray(data.edge_idxs[:n], np.int64)])
+        batches = [tuple(x[s:e] for x in split) for s, e in cuts]        # the ragged last one included
+        model.run_device(model.prepare_run(batches), out=None)
+        total, measured, _ = model.metrics()
+        out = (total / nb).cpu().numpy()                                 # (the one host synchronisation of the pass)
+    model.check_status()
+    if measured != nb:
+        raise RuntimeError("%d of %d batches were measured" % (measured, nb))
     return float(out[0]), float(out[1]), float(out[2])

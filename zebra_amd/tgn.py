@@ -177,6 +177,8 @@ class TGN(torch.nn.Module):
         (zt_pipeline_set_scoring); ``last_prob()`` returns the last step's probabilities.  ValueError where the hidden width
         has no HIP scorer (H % 4 != 0 or H > 768): the native step has no torch fallback."""
         self._score_on = bool(on)
+        if not on:
+            self._met_on = False                         # (zt_pipeline_set_scoring with NULL weights turns the tail off too)
         self._pipe_scoring_sync(force=True)
 
     def last_prob(self):
@@ -186,6 +188,70 @@ class TGN(torch.nn.Module):
         check(lib().zt_pipeline_last_scores(self._pipe, stream_ptr(), C.byref(out), C.byref(B)), "zt_pipeline_last_scores")
         off = (out.value - self._prob_buf.data_ptr()) // 4
         return self._prob_buf[off: off + 2 * B.value]
+
+    def enable_metrics(self, on=True, per_batch=0):
+        """With the native pipeline and ``enable_scoring()``: every scored step is followed by the link-metrics kernel on its
+        2B probabilities (zt_pipeline_set_metrics; on the pipeline's message stream, off the main stream's chain), which adds
+        the batch's (AP, AUC, accuracy) to a float64 [3] accumulator this model owns and, for ``per_batch`` > 0, writes them to
+        row i of a [per_batch, 3] table, i counting the batches since this call.  ``metrics()`` returns them.  RuntimeError
+        without a pipeline or without scoring; ValueError where the library refuses (``max_batch`` beyond 16384 pairs, an
+        exchange attached); a step that would write row ``per_batch`` makes ``run_device`` / ``step_device`` raise ValueError
+        before it is enqueued."""
+        if not on:
+            self._met_on = False
+            if getattr(self, "_pipe", None) is not None:
+                check(lib().zt_pipeline_set_metrics(self._pipe, None, None, C.c_int64(0)), "zt_pipeline_set_metrics")
+                # the tensors go back to the allocator behind the last kernel that writes them
+                check(lib().zt_pipeline_metrics(self._pipe, stream_ptr(), None), "zt_pipeline_metrics")
+            self._met_sum = self._met_rows = None
+            return
+        if getattr(self, "_pipe", None) is None:
+            raise RuntimeError("enable_metrics needs enable_pipeline()")
+        if not getattr(self, "_score_on", False):
+            raise RuntimeError("enable_metrics needs enable_scoring()")
+        if int(per_batch) < 0:
+            raise ValueError("per_batch must be >= 0")
+        check(lib().zt_pipeline_metrics(self._pipe, stream_ptr(), None), "zt_pipeline_metrics")      # (as above, for the old ones)
+        self._met_sum = torch.zeros(3, dtype=torch.float64, device=self.device)
+        self._met_rows = torch.zeros((int(per_batch), 3), dtype=torch.float64, device=self.device) if per_batch > 0 else None
+        self._met_on = True
+        try:
+            self._pipe_metrics_sync()
+        except Exception:
+            self._met_on = False
+            self._met_sum = self._met_rows = None
+            raise
+
+    def _pipe_metrics_sync(self):
+        """(Re-)arm the metrics tail on the pipeline at hand: accumulator and table zeroed, the batch counter at 0."""
+        if getattr(self, "_pipe", None) is None or not getattr(self, "_met_on", False):
+            return
+        self._met_sum.zero_()
+        if self._met_rows is not None:
+            self._met_rows.zero_()
+        check(lib().zt_pipeline_set_metrics(self._pipe, ptr(self._met_sum), ptr(self._met_rows),
+                                            C.c_int64(0 if self._met_rows is None else self._met_rows.shape[0])),
+              "zt_pipeline_set_metrics")
+        cur = torch.cuda.current_stream(self.device)
+        if cur.cuda_stream != self.main_stream.cuda_stream:      # the steps that follow are ordered behind the zeroing
+            self.main_stream.wait_stream(cur)
+
+    def metrics(self, reset=False):
+        """(sum, n, per_batch) of the batches measured since ``enable_metrics`` (or the last reset): the float64 [3] sums of
+        (AP, AUC, accuracy), the number of batches n (an int the library counts on the host) and the [n, 3] rows of the
+        per-batch table or None -- device tensors, valid on the caller's current stream (zt_pipeline_metrics makes it wait for
+        the last metrics kernel); no host synchronisation.  Without ``reset`` they are the live buffers, which later steps go
+        on writing; ``reset=True`` returns copies, then zeroes the accumulator and the counter on that stream."""
+        if getattr(self, "_pipe", None) is None or not getattr(self, "_met_on", False):
+            raise RuntimeError("metrics() needs enable_metrics()")
+        n = C.c_int64()
+        check(lib().zt_pipeline_metrics(self._pipe, stream_ptr(), C.byref(n)), "zt_pipeline_metrics")
+        n = int(n.value)
+        total, rows = self._met_sum, (self._met_rows[:n] if self._met_rows is not None else None)
+        if reset:
+            total, rows = total.clone(), (rows.clone() if rows is not None else None)
+            self._pipe_metrics_sync()
+        return total, n, rows
 
     def _pipe_scoring_sync(self, force=False):
         if getattr(self, "_pipe", None) is None:
@@ -235,6 +301,7 @@ class TGN(torch.nn.Module):
         self._pipe_refresh(create=True)
         self._pipe_score_set = False
         self._pipe_scoring_sync(force=True)
+        self._pipe_metrics_sync()
 
     # -- multi-GPU: the row exchange INSIDE the native step (csrc/exchange.hip); SURVEY.md 8e
     def enable_exchange(self, rank, world, transport="rccl", with_messages=False, group=None, shm_name=None):
@@ -528,18 +595,25 @@ class TGN(torch.nn.Module):
             self.store_messages_device(src_d, dst_d, ts_d, eidx_d, pos_range=positions)
             self.memory_updater.update_device(self.memory, nodes_d[: 2 * B], 2 * B)      # [src | dst], flagged once each
         if check_status:
-            if em.tppr_strategy == "streaming":
-                em.tppr_finder.check_status()
-            st = int(self._status.item()) or (int(em._status.item()) if em._status is not None else 0)
-            if st != 0:
-                self._status.zero_()
-                if em._status is not None:
-                    em._status.zero_()
-                if st == _capi.ZT_ERR_TIMEOUT:
-                    raise _capi.ZebraError("a kernel of the step gave up a bounded in-kernel wait (status %d): the step's memory "
-                                           "update is incomplete" % st)
-                raise IndexError("node / edge id out of range (status %d)" % st)
+            self.check_status()
         return emb
+
+    def check_status(self):
+        """The T-PPR handle's latch and the step kernels' status words, read on the host (a synchronisation): IndexError for an
+        id out of range, ZebraError for a bounded in-kernel wait that gave up; the words are cleared.  ``step_device(check_status=
+        True)`` ends with it; after ``run_device`` call it once."""
+        em = self.embedding_module
+        if em.tppr_strategy == "streaming":
+            em.tppr_finder.check_status()
+        st = int(self._status.item()) or (int(em._status.item()) if em._status is not None else 0)
+        if st != 0:
+            self._status.zero_()
+            if em._status is not None:
+                em._status.zero_()
+            if st == _capi.ZT_ERR_TIMEOUT:
+                raise _capi.ZebraError("a kernel of the step gave up a bounded in-kernel wait (status %d): the step's memory "
+                                       "update is incomplete" % st)
+            raise IndexError("node / edge id out of range (status %d)" % st)
 
     # ------------------------------------------------------------------ reference surface
     def compute_temporal_embeddings(self, source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs,
