@@ -117,6 +117,36 @@ def test_wide_walk_vs_oracle(env, width, depth, k, beta):
         assert (np.count_nonzero(want[3], axis=1) == k).any()      # some rows are full
 
 
+# the LDS form at the top of its range, on the same queries: shape -> (largest walk, largest dictionary), computed on the CPU
+LDS_SHAPES = {(35, 2): (1260, 1243), (2, 9): (1022, 980)}
+
+
+@pytest.mark.parametrize("width,depth", list(LDS_SHAPES))
+def test_lds_form_below_the_switch(env, width, depth):
+    """The walk the two forms share, held to the oracle on the LDS side of the switch too: 35 x 2 fills 1 260 of the LDS
+    form's 1 280 states (36 x 2 is the workspace's first shape), 2 x 9 walks nine levels with a frontier of 256."""
+    import torch
+    k = 20
+    assert env.nf.pruning_plan(width, depth, 1, k)["form"] == "lds"
+    walk, dic = _walk_sizes(env.nf, env.q, env.qt, width, depth)
+    print("%d x %d: largest walk %d, largest dictionary %d" % (width, depth, walk, dic))
+    assert (walk, dic) == LDS_SHAPES[(width, depth)]
+    for beta in (0.5, 0.95):
+        got = _outs(len(env.q), k)
+        assert env.nf.get_pruned_topk(env.q, env.qt, width, depth, 0.1, beta, k, *got) is None
+        _same(got, env.ref(width, depth, 0.1, beta, k), "(%d x %d, beta=%g)" % (width, depth, beta))
+    if (width, depth) == (35, 2):                                  # two models in one call, against the single-model answers
+        dev = torch.device("cuda")
+        q, qt = torch.from_numpy(env.q).to(dev), torch.from_numpy(env.qt).to(dev)
+        on = torch.zeros((2, len(env.q), k), dtype=torch.int32, device=dev)
+        oe, od = torch.zeros_like(on), torch.zeros((2, len(env.q), k), dtype=torch.float32, device=dev)
+        ow = torch.zeros_like(od)
+        env.nf.pruned_topk_multi_device(q, qt, width, depth, [0.1, 0.1], [0.5, 0.95], k, on, oe, od, ow)
+        for m, beta in enumerate((0.5, 0.95)):
+            got = [x[m].cpu().numpy() for x in (on, oe, od, ow)]
+            _same(got, env.ref(width, depth, 0.1, beta, k), "(model %d of 2)" % m)
+
+
 @pytest.mark.parametrize("M", [2, 5])
 @pytest.mark.parametrize("width,depth", [(11, 3), (20, 3)])
 def test_models_share_one_walk(env, M, width, depth):

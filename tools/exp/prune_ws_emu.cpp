@@ -1,9 +1,11 @@
 // k_pruned_topk_ws (zebra_amd/csrc/tppr_prune.hip) run as HOST code, for checking the kernel's logic where no GPU is at hand:
 // one workgroup at a time, 256 std::threads, std::barrier for __syncthreads and for the wave operations (__ballot, __shfl,
-// __shfl_up rendezvous over the 64 threads of a wave), GCC atomics for the device atomics.  kernel_body.inc is cut out of the
-// kernel source by prune_ws_emu.py, which also writes the inputs (*.bin: CSR, queries, models, the oracle's outputs) and runs
-// this program; it prints the number of output words that differ from the oracle's.  It says nothing about speed, and nothing
-// about what only the device can get wrong (memory ordering between waves, launch plumbing): tests/test_prune_wide_gpu.py does.
+// __shfl_up rendezvous over the 64 threads of a wave), GCC atomics for the device atomics.  The walk and what else the two
+// forms share is csrc/prune_walk.hpp, included as it is; kernel_body.inc (the kernel with its merge and selection, and the
+// sequential sort it falls back to) is cut out of the sources by prune_ws_emu.py, which also writes the inputs (*.bin: CSR,
+// queries, models, the oracle's outputs) and runs this program; it prints the number of output words that differ from the
+// oracle's.  It says nothing about speed, and nothing about what only the device can get wrong (memory ordering between
+// waves, launch plumbing): tests/test_prune_wide_gpu.py does.
 #include <atomic>
 #include <barrier>
 #include <cmath>
@@ -34,6 +36,7 @@ static std::atomic<int> orv{0};
 inline int lane_id() { return threadIdx.x & 63; }
 inline int wv() { return threadIdx.x / 64; }
 inline void __syncthreads() { blk.arrive_and_wait(); }
+inline void wave_sync() {}                    // (WaveGroup's barrier: the LDS form's group, not run here)
 inline int __syncthreads_or(int v) { blk.arrive_and_wait(); if (v) orv.fetch_or(1); blk.arrive_and_wait(); int r = orv.load(); blk.arrive_and_wait(); if (threadIdx.x == 0) orv = 0; blk.arrive_and_wait(); return r; }
 inline u64 __ballot(bool p) { auto &b = *wb[wv()]; b.arrive_and_wait(); if (p) bal[wv()].fetch_or(1ull << lane_id()); b.arrive_and_wait(); u64 r = bal[wv()].load(); b.arrive_and_wait(); if (lane_id() == 0) bal[wv()] = 0; b.arrive_and_wait(); return r; }
 inline int __shfl(int v, int src) { auto &b = *wb[wv()]; shv[wv()][lane_id()] = v; b.arrive_and_wait(); int r = shv[wv()][src]; b.arrive_and_wait(); return r; }
@@ -49,6 +52,7 @@ inline void st_agent(u64 *p, u64 v) { __atomic_store_n(p, v, __ATOMIC_SEQ_CST); 
 inline void st_agent(int *p, int v) { __atomic_store_n(p, v, __ATOMIC_SEQ_CST); }
 inline int ld_agent(const int *p) { return __atomic_load_n(p, __ATOMIC_SEQ_CST); }
 namespace {
+#include "prune_walk.hpp"
 #include "kernel_body.inc"
 }
 template <class T> std::vector<T> rd(const char *fn) { FILE *f = fopen(fn, "rb"); if (!f) { perror(fn); exit(2); } fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET); std::vector<T> v(n / sizeof(T)); if (fread(v.data(), 1, n, f) != (size_t)n) exit(2); fclose(f); return v; }

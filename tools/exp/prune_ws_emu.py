@@ -24,15 +24,12 @@ DT = (np.int32, np.int32, np.float32, np.float32)
 
 
 def kernel_body():
-    """the device code the kernel needs, cut out of the sources"""
+    """the device code the kernel needs beyond csrc/prune_walk.hpp, cut out of the sources"""
     src = open(os.path.join(ROOT, "zebra_amd", "csrc", "tppr_prune.hip")).read()
     ns = open(os.path.join(ROOT, "zebra_amd", "csrc", "numba_sort.hpp")).read()
     cut = lambda s, a, b: s[s.index(a):s.index(b)]
     return (cut(ns, "__device__ __forceinline__ bool lt_f", "// LDS scratch of the wave-parallel sort") +
-            cut(src, "constexpr int PR_WAVES = 4;", "// Per-wave LDS block, carved from dynamic shared memory") +
-            cut(src, "__host__ __device__ inline size_t align16", "// (sel: 64 entries for k <= ZT_MAX_K") +
-            cut(src, "// numba pow(float64, int64)", "// NeighborFinder.get_pruned_topk (utils/util.py:185-276) for every (alpha, beta)") +
-            cut(src, "constexpr int WS_THREADS = 256;", "}  // namespace\n\nstatic int csr_upload"))
+            cut(src, "struct WsLds {", "}  // namespace\n\nstatic int csr_upload"))
 
 
 def main():
@@ -52,6 +49,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "kernel_body.inc"), "w").write(kernel_body())
         subprocess.run(["g++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", d,
+                        "-I", os.path.join(ROOT, "zebra_amd", "csrc"),
                         os.path.join(ROOT, "tools", "exp", "prune_ws_emu.cpp"), "-o", os.path.join(d, "emu")], check=True)
         w = lambda name, arr: arr.tofile(os.path.join(d, name + ".bin"))
         w("indptr", np.cumsum(indptr).astype(np.int64)); w("nbr", oth2[order]); w("eid", e2[order]); w("ts", t2[order])

@@ -1,17 +1,15 @@
 // Static adjacency (CSR) + pruning T-PPR ("PPI", reference utils/util.py:90-276).
 // Compile with -ffp-contract=off (bit-exact float64, see tppr_stream.hip).
 //
-// One wavefront per query row, all (alpha, beta) models in one walk.  The BFS
-// frontier and the insertion-ordered candidate list live in LDS; find_before is
-// a P-ary search by P lanes per frontier entry; the CSR tails of a whole level
-// are read by one lane per (entry, z) pair, most recent first.  Duplicate
-// states are merged keeping the reference's dictionary order (first
-// occurrence) and its left-to-right float64 summation order; selection uses
-// the exact numba argsort semantics.
-//
-// Walks that do not fit LDS take the workspace form, k_pruned_topk_ws: the same
-// query over a slab of device memory the handle reserves, one workgroup per slab.
-// prune_plan decides between the two.
+// One query row = one walk of the adjacency for all (alpha, beta) models, a merge of duplicate states that keeps the
+// reference's dictionary order (first occurrence) and its left-to-right float64 summation order, and a selection with the
+// exact numba argsort semantics.  Two kernels answer it; prune_plan decides between them:
+//   k_pruned_topk     the LDS form: one wavefront per query, the list in LDS;
+//   k_pruned_topk_ws  the workspace form, for walks that do not fit LDS: one workgroup per slab of device memory the
+//                     handle reserves.
+// The list layout, the walk, the duplicate sum and the row writers are the same code for both (prune_walk.hpp, over a
+// wavefront or a workgroup); each kernel has its own merge (all pairs / hash table) and selection (numba_sort.hpp's
+// wave-parallel argsort / radix select), which are different algorithms for different sizes.
 #include "numba_sort.hpp"
 
 #include <algorithm>
@@ -40,86 +38,25 @@ struct zt_csr {
 
 namespace {
 
+#include "prune_walk.hpp"     // (in here: its names are this file's own)
+
 constexpr int PR_WAVES = 4;           // queries per workgroup
 constexpr int MAX_CAND = 1280;        // sum_{d<=depth} width^d
 constexpr int MAX_FRONT = 512;        // width^(depth-1)
-constexpr int PR_MAX_MODELS = 4;      // (alpha, beta) models sharing one walk; more run as several launches
 
-struct PruneModels {
-    int M;
-    double alpha[PR_MAX_MODELS], beta[PR_MAX_MODELS];
-};
-
-// Per-wave LDS block, carved from dynamic shared memory; sized at launch from
-// the actual (width, depth, models) so that small configurations keep occupancy high.
-struct PruneLds {
-    u64 *key;               // [cap_c] candidate states in BFS (= dictionary insertion) order
-    double *ts;             // [cap_c]
-    double *w;              // [M][cap_c] weight of every occurrence, per model
-    int *perm;              // [cap_c] owner frontier entry of a new state (walk) / first occurrence (merge) / sort scratch
-    int *sel;               // 64 (k <= ZT_MAX_K) or 256
-    int *stk;               // 96
-    int *f_cnt;             // [cap_f] per frontier entry: number of states it emits
-    int *f_off;             // [cap_f] exclusive scan of f_cnt
-    int *f_ngh;             // [cap_f] find_before count
-    long long *f_lo;        // [cap_f] start of the entry's adjacency
-    double *f_base;         // [M][cap_f] weight of the entry's most recent neighbour
-    SortLds *sort;          // wave-parallel exact argsort scratch (n <= 128)
-};
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
+// Per-wave LDS block, carved from dynamic shared memory: the list, then sel, stk and the sort's scratch; sized at launch
+// from the actual (width, depth, models) so that small configurations keep occupancy high.
 // (sel: 64 entries for k <= ZT_MAX_K -- the tuned configurations keep their LDS footprint --, 256 for the wider k)
 __host__ __device__ inline size_t prune_sel_words(int k) { return k <= 64 ? 64 : 256; }
 __host__ __device__ inline size_t prune_lds_bytes(int cap_c, int cap_f, int M, int k)
 {
-    return (2 + (size_t)M) * align16((size_t)cap_c * 8) + align16((size_t)cap_c * 4) + align16(prune_sel_words(k) * 4) + align16(96 * 4) +
-           3 * align16((size_t)cap_f * 4) + (1 + (size_t)M) * align16((size_t)cap_f * 8) + align16(sizeof(SortLds));
+    return prune_list_bytes(cap_c, cap_f, M) + align16(prune_sel_words(k) * 4) + align16(96 * 4) + align16(sizeof(SortLds));
 }
 
-__device__ inline PruneLds carve(char *base, int cap_c, int cap_f, int M, int k)
-{
-    PruneLds L;
-    char *p = base;
-    L.key = reinterpret_cast<u64 *>(p); p += align16((size_t)cap_c * 8);
-    L.ts = reinterpret_cast<double *>(p); p += align16((size_t)cap_c * 8);
-    L.w = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_c * 8);
-    L.perm = reinterpret_cast<int *>(p); p += align16((size_t)cap_c * 4);
-    L.sel = reinterpret_cast<int *>(p); p += align16(prune_sel_words(k) * 4);
-    L.stk = reinterpret_cast<int *>(p); p += align16(96 * 4);
-    L.f_cnt = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_off = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_ngh = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_lo = reinterpret_cast<long long *>(p); p += align16((size_t)cap_f * 8);
-    L.f_base = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_f * 8);
-    L.sort = reinterpret_cast<SortLds *>(p);
-    return L;
-}
-
-// numba pow(float64, int64) (numba/cpython/numbers.py:207-243)
-__device__ __forceinline__ double numba_int_pow(double a, long long b)
-{
-    if (b > 0x10000) return pow(a, (double)b);
-    double r = 1.0;
-    long long e = b;
-    while (e != 0) {
-        if (e & 1) r *= a;
-        e >>= 1;
-        a *= a;
-    }
-    return r;
-}
-
-// NeighborFinder.get_pruned_topk (utils/util.py:185-276) for every (alpha, beta) model at once: ONE wavefront per
-// query row walks the adjacency once -- which states are reached depends on (node, time) only -- and carries one
-// weight per model along.
-//   find_before (np.searchsorted, :152-154): a P-ary search by P lanes per frontier entry (P = 64 for the single
-//     entry of level 0, 8 when a level has many) -- log_P(degree) dependent round trips instead of log_2, once per
-//     entry;
-//   the <= width most recent neighbours of all entries of a level (:211-232): one lane per (entry, z) pair, so the
-//     tails come in as one coalesced round of loads;
-//   duplicate states (dict[state] += w in occurrence order, :222-225), exact numba argsort selection (:240-276)
-//     per model.
+// The LDS form: ONE wavefront per query row.  The walk, then
+//   duplicate states (dict[state] += w in occurrence order, :222-225): first occurrences by an all-pairs scan with
+//     broadcast reads;
+//   exact numba argsort selection (:240-276) per model.
 __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
     const long long *__restrict__ indptr, const int *__restrict__ nbr, const int *__restrict__ eid,
     const double *__restrict__ ats, long long num_nodes, const int *__restrict__ q_nodes,
@@ -129,8 +66,14 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M = pm.M;
-    const PruneLds L = carve(smem + (threadIdx.x / WAVE) * prune_lds_bytes(cap_c, cap_f, M, k), cap_c, cap_f, M, k);
-    const size_t wst = align16((size_t)cap_c * 8) / 8, bst = align16((size_t)cap_f * 8) / 8;   // model strides (doubles)
+    char *blk = smem + (threadIdx.x / WAVE) * prune_lds_bytes(cap_c, cap_f, M, k);
+    const PruneList L = carve_list(blk, cap_c, cap_f, M);
+    int *sel = reinterpret_cast<int *>(blk + prune_list_bytes(cap_c, cap_f, M));   // 64 (k <= ZT_MAX_K) or 256
+    int *stk = sel + prune_sel_words(k);                                           // 96
+    SortLds *sort = reinterpret_cast<SortLds *>(stk + 96);      // wave-parallel exact argsort scratch (n <= 128)
+    const WaveGroup grp;
+    const PruneOut O = {out_nodes, out_eidx, out_dt, out_w, out_stride};
+    const size_t wst = L.wst;
     const int lane = lane_id();
     const long long qi = (long long)blockIdx.x * PR_WAVES + threadIdx.x / WAVE;
     if (qi >= nq) return;
@@ -138,117 +81,12 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
     const double qt = q_ts[qi];
     if (qn < 0 || qn >= num_nodes) {
         if (lane == 0) atomicExch(status, ZT_ERR_RANGE);
-        // (zero_empty: nobody cleared the slot -- the row would keep the previous group's neighbours and the aggregation of
-        //  this step, whose caller may never look at the status word, would consume them: an empty row instead)
-        if (zero_empty)
-            for (int m = 0; m < M; ++m) {
-                const long long ob = (long long)m * out_stride + qi * k;
-                for (int j = lane; j < k; j += WAVE) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
-            }
+        if (zero_empty) zero_row(grp, O, M, qi, k);
         return;
     }
-
-    // frontier of level `dep` = the states level dep-1 appended: candidates [fr_lo, fr_lo + nf); level 0: the query
-    int n_cand = 0, fr_lo = 0, nf = 1;
-    for (int dep = 0; dep < depth; ++dep) {
-        // ---- find_before of every frontier entry: P lanes per entry ----
-        const int P = nf == 1 ? 64 : (nf == 2 ? 32 : (nf <= 4 ? 16 : 8));
-        const int epc = WAVE / P;                                   // entries per pass
-        const int g = lane / P, j = lane % P;
-        const u64 gmask = P == 64 ? ~0ull : ((1ull << P) - 1ull);
-        for (int f0 = 0; f0 < nf; f0 += epc) {
-            const int f = f0 + g;
-            const bool act = f < nf;
-            const int node = !act ? 0 : (dep == 0 ? qn : (int)(unsigned)(L.key[fr_lo + f] & 0xffffffffull));
-            const double t = !act ? 0.0 : (dep == 0 ? qt : L.ts[fr_lo + f]);
-            const long long lo0 = act ? indptr[node] : 0, hi0 = act ? indptr[node + 1] : 0;
-            long long lo = lo0, hi = hi0;                           // the answer (first index with ts >= t) is in [lo, hi]
-            while (__ballot(lo < hi) != 0ull) {
-                const long long n = hi - lo;
-                const bool open = lo < hi;
-                const bool pred = open && ats[lo + (n * j) / P] < t;               // probes at lo + floor(n * j / P)
-                const int c = __popcll((__ballot(pred) >> (g * P)) & gmask);       // true for a prefix of the probes
-                if (open) {
-                    if (c == 0) hi = lo;
-                    else {
-                        const long long nlo = lo + (n * (c - 1)) / P + 1;
-                        hi = c < P ? lo + (n * c) / P : hi;
-                        lo = nlo;
-                    }
-                }
-            }
-            if (act && j == 0) {
-                const long long n_ngh = lo - lo0;
-                L.f_ngh[f] = (int)n_ngh;                            // < 2^31: entries of one node
-                L.f_lo[f] = lo0;
-                L.f_cnt[f] = (int)(n_ngh < width ? n_ngh : width);
-            }
-        }
-        wave_sync();
-        // ---- exclusive scan of f_cnt ----
-        int n_new = 0;
-        for (int f0 = 0; f0 < nf; f0 += WAVE) {
-            const int f = f0 + lane;
-            const int c = f < nf ? L.f_cnt[f] : 0;
-            int inc = c;
-#pragma unroll
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const int o = __shfl_up(inc, d);
-                if (lane >= d) inc += o;
-            }
-            if (f < nf) L.f_off[f] = n_new + inc - c;
-            n_new += __shfl(inc, WAVE - 1);
-        }
-        if (n_new == 0) break;                                      // :234-235
-        // ---- per entry and model: weight of its most recent neighbour (:208-209); who owns which new state ----
-        for (int f0 = 0; f0 < nf; f0 += WAVE) {
-            const int f = f0 + lane;
-            if (f < nf) {
-                const int c = L.f_cnt[f], o = n_cand + L.f_off[f];
-                if (c > 0) {
-                    const long long n_ngh = L.f_ngh[f];
-                    for (int m = 0; m < M; ++m) {
-                        const double alpha = pm.alpha[m], beta = pm.beta[m];
-                        const double qw = dep == 0 ? 1.0 : L.w[m * wst + fr_lo + f];
-                        const double norm = beta / (1.0 - beta) * (1.0 - numba_int_pow(beta, n_ngh));   // :208
-                        L.f_base[m * bst + f] = (alpha != 0.0 && dep == 0) ? qw * (1.0 - alpha) * beta / norm * alpha
-                                                                           : qw * (1.0 - alpha) * beta / norm;   // :209
-                    }
-                    for (int z = 0; z < c; ++z) L.perm[o + z] = f;
-                }
-            }
-        }
-        wave_sync();
-        // ---- the new states, most recent first (:211-232): one lane per (entry, z) ----
-        for (int i0 = 0; i0 < n_new; i0 += WAVE) {
-            const int i = i0 + lane;
-            if (i < n_new) {
-                const int f = L.perm[n_cand + i];
-                const int z = i - L.f_off[f];
-                const long long p = L.f_lo[f] + L.f_ngh[f] - (z + 1);
-                L.key[n_cand + i] = ((u64)(unsigned)eid[p] << 32) | (u64)(unsigned)nbr[p];
-                L.ts[n_cand + i] = ats[p];
-                for (int m = 0; m < M; ++m) {
-                    const double beta = pm.beta[m];
-                    double weight = L.f_base[m * bst + f];
-                    for (int q = 0; q < z; ++q) weight = weight * beta;             // weight *= beta after every state
-                    L.w[m * wst + n_cand + i] = weight;
-                }
-            }
-        }
-        wave_sync();
-        fr_lo = n_cand;
-        nf = n_new;
-        n_cand += n_new;
-    }
+    const int n_cand = prune_walk(grp, indptr, nbr, eid, ats, qn, qt, width, depth, pm, cap_c, cap_f, L);
     if (n_cand == 0) {                                              // :241-242, row untouched
-        // (zero_empty: the caller's output arrays are not cleared beforehand -- pipeline.hip: a memset in front of every
-        //  query is a packet on the T-PPR stream, ~6 us of every C4 step -- so an empty row is written here, as zeros)
-        if (zero_empty)
-            for (int m = 0; m < M; ++m) {
-                const long long ob = (long long)m * out_stride + qi * k;
-                for (int j = lane; j < k; j += WAVE) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
-            }
+        if (zero_empty) zero_row(grp, O, M, qi, k);
         return;
     }
     if (dbg_stop == 1) { if (lane == 0) out_nodes[qi * k] = n_cand; return; }      // (diagnostic: ZT_PRUNE_STOP)
@@ -286,18 +124,7 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
     wave_sync();
     int nd = n_cand;
     if (any_dup) {
-        // a leader's value is the left-to-right sum of its occurrences: later occurrences are added in index order,
-        // lane m doing model m (a lane's LDS accesses execute in program order)
-        for (int c0 = 0; c0 < n_cand; c0 += WAVE) {
-            const int c = c0 + lane;
-            u64 dm = __ballot(c < n_cand && L.perm[c] != c);
-            while (dm != 0ull) {
-                const int cc = c0 + __ffsll((long long)dm) - 1;
-                dm &= dm - 1ull;
-                const int lead = L.perm[cc];
-                if (lane < M) L.w[lane * wst + lead] = L.w[lane * wst + lead] + L.w[lane * wst + cc];
-            }
-        }
+        sum_duplicates(L, n_cand, M);
         wave_sync();
         // compact the leaders in order (dictionary insertion order)
         nd = 0;
@@ -324,43 +151,26 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
 
     if (dbg_stop == 2) { if (lane == 0) out_nodes[qi * k] = nd; return; }
     // ---- select and emit (:240-276), model by model ----
+    // (k <= ZT_MAX_K: one pass, lane j = entry j; wider k -- the reference puts no bound on --topk, train.py:46 -- strides)
     for (int m = 0; m < M; ++m) {
-        const long long ob = (long long)m * out_stride + qi * k;
+        if (nd <= k) { emit_all(grp, O, L, m, qi, k, nd, qt); continue; }
         const double *wm = L.w + m * wst;
-        // (k <= ZT_MAX_K: one pass, lane j = entry j; wider k -- the reference puts no bound on --topk, train.py:46 -- strides)
-        if (nd <= k) {
-            for (int j = lane; j < k; j += WAVE) {
-                const bool a = j < nd;
-                out_nodes[ob + j] = a ? (int)(unsigned)(L.key[j] & 0xffffffffull) : 0;
-                out_eidx[ob + j] = a ? (int)(unsigned)(L.key[j] >> 32) : 0;
-                out_w[ob + j] = a ? (float)wm[j] : 0.f;
-                const float tsf = a ? (float)L.ts[j] : 0.f;
-                out_dt[ob + j] = (float)(qt - (double)tsf);
-            }
-            continue;
-        }
-        if (dbg_stop == 4 || (dbg_stop == 3 && nd > WAVE)) { if (lane < k) L.sel[lane] = lane; wave_sync(); }   // (diagnostic)
-        else if (k <= ZT_MAX_K) topk_select_wave(wm, nd, k, L.sel, *L.sort, L.perm, L.stk);
-        else topk_select_any(wm, nd, k, L.sel, *L.sort, L.perm, L.stk);      // kept sets wider than a wavefront: correct first
-        for (int j = lane; j < k; j += WAVE) {
-            const int c = L.sel[j];
-            out_nodes[ob + j] = (int)(unsigned)(L.key[c] & 0xffffffffull);
-            out_eidx[ob + j] = (int)(unsigned)(L.key[c] >> 32);
-            out_w[ob + j] = (float)wm[c];
-            out_dt[ob + j] = (float)(qt - (double)(float)L.ts[c]);
-        }
+        if (dbg_stop == 4 || (dbg_stop == 3 && nd > WAVE)) { if (lane < k) sel[lane] = lane; wave_sync(); }   // (diagnostic)
+        else if (k <= ZT_MAX_K) topk_select_wave(wm, nd, k, sel, *sort, L.perm, stk);
+        else topk_select_any(wm, nd, k, sel, *sort, L.perm, stk);            // kept sets wider than a wavefront: correct first
+        emit_selected(grp, O, L, m, qi, k, sel, qt);
         wave_sync();
     }
 }
 
 // ---------------------------------------------------------------------------
-// The workspace form: the same query with its per-query arrays in a slab of device memory (zt_csr_reserve_pruning), for
-// walks that do not fit LDS (the reference bounds neither --n_degree nor --n_layer).  Persistent: worker = one WORKGROUP of
-// WS_THREADS threads, one slab each, queries worker, worker + grid, ...  A workgroup rather than a wavefront: a walk of
-// 10^4..10^5 states is latency-bound on global memory, and four waves keep four times the loads in flight per slab (slabs
-// are megabytes each, so slabs, not lanes, are what a budget runs out of); the barrier between stages and a 256-bin LDS
-// histogram for the selection come with it.  Stage by stage the semantics are k_pruned_topk's; what differs is how the
-// two quadratic steps are done:
+// The workspace form: the same query with its list in a slab of device memory (zt_csr_reserve_pruning), for walks that do
+// not fit LDS (the reference bounds neither --n_degree nor --n_layer).  Persistent: worker = one WORKGROUP of WS_THREADS
+// threads, one slab each, queries worker, worker + grid, ...  A workgroup rather than a wavefront: a walk of 10^4..10^5
+// states is latency-bound on global memory, and four waves keep four times the loads in flight per slab (slabs are megabytes
+// each, so slabs, not lanes, are what a budget runs out of); the barrier between stages and a 256-bin LDS histogram for the
+// selection come with it.  The walk, the duplicate sum and the row writers are prune_walk.hpp's, over the workgroup; what
+// differs from k_pruned_topk is how the two quadratic steps are done:
 //   merge   first occurrences through a hash table in the slab: a slot is claimed for a (edge, node) key by compare-and-swap
 //           and keeps the SMALLEST list index of its key (atomicMin), which does not depend on who inserts first;
 //   select  the cut (k-th largest value) by an 8-bit-per-pass radix select on the float64 patterns -- weights are positive
@@ -370,15 +180,13 @@ __global__ __launch_bounds__(WAVE * PR_WAVES) void k_pruned_topk(
 // A slab is reused from query to query: every array is written before it is read within a query (the hash table is
 // cleared over the slots this query uses).
 // ---------------------------------------------------------------------------
-constexpr int WS_THREADS = 256;
-constexpr int WS_WAVES = WS_THREADS / WAVE;
 struct WsLds {                                // k_pruned_topk_ws's LDS: the selection's scratch
     double cval[256];                         // the candidates at or above the cut: value,
     int cidx[256];                            // list index
     int sel[256];                             // the kept set, in output order
     int hist[256];                            // radix select: one pass's bins
     int stk[96];                              // numba_argsort_seq's stack
-    int wt[WS_WAVES];                         // block_scan_excl
+    int wt[WS_WAVES];                         // BlockGroup::scan_excl
     int bin, want, cnt;
 };
 constexpr int WS_STATIC_LDS = (int)sizeof(WsLds);
@@ -390,61 +198,12 @@ __host__ __device__ inline size_t ws_table_slots(long long n)           // power
     while (t < 2 * (size_t)n) t <<= 1;
     return t;
 }
+// a slab: the list, then the merge's hash table -- h_key [slots]: the key that owns the slot, h_first [slots]: the smallest
+// list index of that key
 __host__ __device__ inline size_t ws_slab_bytes(int cap_c, int cap_f, int M)
 {
-    const size_t b = (2 + (size_t)M) * align16((size_t)cap_c * 8) + align16((size_t)cap_c * 4) + 3 * align16((size_t)cap_f * 4) +
-                     (1 + (size_t)M) * align16((size_t)cap_f * 8) + align16(ws_table_slots(cap_c) * 8) + align16(ws_table_slots(cap_c) * 4);
+    const size_t b = prune_list_bytes(cap_c, cap_f, M) + align16(ws_table_slots(cap_c) * 8) + align16(ws_table_slots(cap_c) * 4);
     return (b + 255) & ~(size_t)255;
-}
-
-struct PruneSlab {
-    u64 *key;               // [cap_c] the LDS form's arrays ...
-    double *ts;             // [cap_c]
-    double *w;              // [M][cap_c]
-    int *perm;              // [cap_c] owner entry (walk) / hash slot, then first occurrence (merge) / the replay's permutation
-    int *f_cnt, *f_off, *f_ngh;   // [cap_f]
-    long long *f_lo;        // [cap_f]
-    double *f_base;         // [M][cap_f]
-    u64 *h_key;             // [slots] ... and the merge's hash table: the key that owns the slot
-    int *h_first;           // [slots] smallest list index of that key
-};
-
-__device__ inline PruneSlab carve_slab(char *base, int cap_c, int cap_f, int M)
-{
-    PruneSlab L;
-    char *p = base;
-    L.key = reinterpret_cast<u64 *>(p); p += align16((size_t)cap_c * 8);
-    L.ts = reinterpret_cast<double *>(p); p += align16((size_t)cap_c * 8);
-    L.w = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_c * 8);
-    L.perm = reinterpret_cast<int *>(p); p += align16((size_t)cap_c * 4);
-    L.f_cnt = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_off = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_ngh = reinterpret_cast<int *>(p); p += align16((size_t)cap_f * 4);
-    L.f_lo = reinterpret_cast<long long *>(p); p += align16((size_t)cap_f * 8);
-    L.f_base = reinterpret_cast<double *>(p); p += (size_t)M * align16((size_t)cap_f * 8);
-    L.h_key = reinterpret_cast<u64 *>(p); p += align16(ws_table_slots(cap_c) * 8);
-    L.h_first = reinterpret_cast<int *>(p);
-    return L;
-}
-
-// exclusive scan of v over the workgroup (thread order) and its total; wt: WS_WAVES ints of LDS.  Two barriers.
-__device__ inline int block_scan_excl(int v, int *wt, int *total)
-{
-    const int lane = lane_id(), wv = threadIdx.x / WAVE;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == WAVE - 1) wt[wv] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < WS_WAVES; ++q) { const int t = wt[q]; base += q < wv ? t : 0; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
 }
 
 __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
@@ -456,114 +215,26 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
 {
     __shared__ WsLds S;
     const int M = pm.M;
-    const PruneSlab L = carve_slab(slabs + (size_t)blockIdx.x * (size_t)slab_bytes, cap_c, cap_f, slab_models);
-    const size_t wst = align16((size_t)cap_c * 8) / 8, bst = align16((size_t)cap_f * 8) / 8;   // model strides (doubles)
-    const int tid = threadIdx.x, lane = lane_id();
+    char *slab = slabs + (size_t)blockIdx.x * (size_t)slab_bytes;
+    const PruneList L = carve_list(slab, cap_c, cap_f, slab_models);
+    u64 *h_key = reinterpret_cast<u64 *>(slab + prune_list_bytes(cap_c, cap_f, slab_models));
+    int *h_first = reinterpret_cast<int *>(h_key + ws_table_slots(cap_c));
+    const BlockGroup grp = {S.wt};
+    const PruneOut O = {out_nodes, out_eidx, out_dt, out_w, out_stride};
+    const size_t wst = L.wst;
+    const int tid = threadIdx.x;
     for (long long qi = blockIdx.x; qi < nq; qi += gridDim.x) {        // (every branch below is uniform over the workgroup)
         __syncthreads();                                               // the previous query's LDS and slab reads are done
         const int qn = q_nodes[qi];
         const double qt = q_ts[qi];
         if (qn < 0 || qn >= num_nodes) {
             if (tid == 0) atomicExch(status, ZT_ERR_RANGE);
-            if (zero_empty)
-                for (int m = 0; m < M; ++m) {
-                    const long long ob = (long long)m * out_stride + qi * k;
-                    for (int j = tid; j < k; j += WS_THREADS) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
-                }
+            if (zero_empty) zero_row(grp, O, M, qi, k);
             continue;
         }
-
-        // ---- the walk: k_pruned_topk's, level by level, over the workgroup ----
-        int n_cand = 0, fr_lo = 0, nf = 1;
-        for (int dep = 0; dep < depth; ++dep) {
-            // find_before of every frontier entry: a P-ary search by P lanes of one wave per entry
-            const int P = nf == 1 ? 64 : (nf == 2 ? 32 : (nf <= 4 ? 16 : 8));
-            const int epc = WS_THREADS / P;
-            const int g = tid / P, gl = lane / P, j = lane % P;
-            const u64 gmask = P == 64 ? ~0ull : ((1ull << P) - 1ull);
-            for (int f0 = 0; f0 < nf; f0 += epc) {
-                const int f = f0 + g;
-                const bool act = f < nf;
-                const int node = !act ? 0 : (dep == 0 ? qn : (int)(unsigned)(L.key[fr_lo + f] & 0xffffffffull));
-                const double t = !act ? 0.0 : (dep == 0 ? qt : L.ts[fr_lo + f]);
-                const long long lo0 = act ? indptr[node] : 0, hi0 = act ? indptr[node + 1] : 0;
-                long long lo = lo0, hi = hi0;                           // the answer (first index with ts >= t) is in [lo, hi]
-                while (__ballot(lo < hi) != 0ull) {
-                    const long long n = hi - lo;
-                    const bool open = lo < hi;
-                    const bool pred = open && ats[lo + (n * j) / P] < t;
-                    const int c = __popcll((__ballot(pred) >> (gl * P)) & gmask);
-                    if (open) {
-                        if (c == 0) hi = lo;
-                        else {
-                            const long long nlo = lo + (n * (c - 1)) / P + 1;
-                            hi = c < P ? lo + (n * c) / P : hi;
-                            lo = nlo;
-                        }
-                    }
-                }
-                if (act && j == 0) {
-                    const long long n_ngh = lo - lo0;
-                    L.f_ngh[f] = (int)n_ngh;
-                    L.f_lo[f] = lo0;
-                    L.f_cnt[f] = (int)(n_ngh < width ? n_ngh : width);
-                }
-            }
-            __syncthreads();
-            // exclusive scan of f_cnt
-            int n_new = 0;
-            for (int f0 = 0; f0 < nf; f0 += WS_THREADS) {
-                const int f = f0 + tid;
-                const int c = f < nf ? L.f_cnt[f] : 0;
-                int tot;
-                const int ex = block_scan_excl(c, S.wt, &tot);
-                if (f < nf) L.f_off[f] = n_new + ex;
-                n_new += tot;
-            }
-            if (n_new == 0) break;                                      // :234-235
-            if (n_cand + n_new > cap_c || nf > cap_f) break;            // (cannot happen: the plan's caps are sums of width^d)
-            __syncthreads();
-            // per entry and model: weight of its most recent neighbour (:208-209); who owns which new state
-            for (int f = tid; f < nf; f += WS_THREADS) {
-                const int c = L.f_cnt[f], o = n_cand + L.f_off[f];
-                if (c > 0) {
-                    const long long n_ngh = L.f_ngh[f];
-                    for (int m = 0; m < M; ++m) {
-                        const double alpha = pm.alpha[m], beta = pm.beta[m];
-                        const double qw = dep == 0 ? 1.0 : L.w[m * wst + fr_lo + f];
-                        const double norm = beta / (1.0 - beta) * (1.0 - numba_int_pow(beta, n_ngh));   // :208
-                        L.f_base[m * bst + f] = (alpha != 0.0 && dep == 0) ? qw * (1.0 - alpha) * beta / norm * alpha
-                                                                           : qw * (1.0 - alpha) * beta / norm;   // :209
-                    }
-                    for (int z = 0; z < c; ++z) L.perm[o + z] = f;
-                }
-            }
-            __syncthreads();
-            // the new states, most recent first (:211-232): one lane per (entry, z)
-            for (int i = tid; i < n_new; i += WS_THREADS) {
-                const int f = L.perm[n_cand + i];
-                const int z = i - L.f_off[f];
-                const long long p = L.f_lo[f] + L.f_ngh[f] - (z + 1);
-                L.key[n_cand + i] = ((u64)(unsigned)eid[p] << 32) | (u64)(unsigned)nbr[p];
-                L.ts[n_cand + i] = ats[p];
-                for (int m = 0; m < M; ++m) {
-                    const double beta = pm.beta[m];
-                    double weight = L.f_base[m * bst + f];
-                    for (int q = 0; q < z; ++q) weight = weight * beta;             // weight *= beta after every state
-                    L.w[m * wst + n_cand + i] = weight;
-                }
-            }
-            __syncthreads();
-            fr_lo = n_cand;
-            nf = n_new;
-            n_cand += n_new;
-        }
-        if (n_cand == 0) {                                              // :241-242, row untouched (zero_empty: written as zeros)
-            if (zero_empty)
-                for (int m = 0; m < M; ++m) {
-                    const long long ob = (long long)m * out_stride + qi * k;
-                    for (int j = tid; j < k; j += WS_THREADS) { out_nodes[ob + j] = 0; out_eidx[ob + j] = 0; out_w[ob + j] = 0.f; out_dt[ob + j] = 0.f; }
-                }
+        const int n_cand = prune_walk(grp, indptr, nbr, eid, ats, qn, qt, width, depth, pm, cap_c, cap_f, L);
+        if (n_cand == 0) {                                              // :241-242, row untouched
+            if (zero_empty) zero_row(grp, O, M, qi, k);
             continue;
         }
 
@@ -572,24 +243,24 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
         {
             const int tsz = (int)ws_table_slots(n_cand);
             const unsigned hmask = (unsigned)tsz - 1u;
-            for (int s = tid; s < tsz; s += WS_THREADS) { st_agent(&L.h_key[s], WS_EMPTY); st_agent(&L.h_first[s], 0x7fffffff); }
+            for (int s = tid; s < tsz; s += WS_THREADS) { st_agent(&h_key[s], WS_EMPTY); st_agent(&h_first[s], 0x7fffffff); }
             __syncthreads();
             for (int c = tid; c < n_cand; c += WS_THREADS) {
                 const u64 kc = L.key[c];
                 unsigned h = (unsigned)((kc * 0x9E3779B97F4A7C15ull) >> 40) & hmask;
                 for (;;) {
-                    const u64 prev = atomicCAS(&L.h_key[h], WS_EMPTY, kc);
+                    const u64 prev = atomicCAS(&h_key[h], WS_EMPTY, kc);
                     if (prev == WS_EMPTY || prev == kc) break;
                     h = (h + 1u) & hmask;
                 }
-                atomicMin(&L.h_first[h], c);
+                atomicMin(&h_first[h], c);
                 L.perm[c] = (int)h;
             }
             __syncthreads();
         }
         int dup = 0, mis = 0;
         for (int c = tid; c < n_cand; c += WS_THREADS) {
-            const int fi = ld_agent(&L.h_first[L.perm[c]]);
+            const int fi = ld_agent(&h_first[L.perm[c]]);
             mis |= (fi != c && L.ts[fi] != L.ts[c]) ? 1 : 0;
             dup |= fi != c ? 1 : 0;
             L.perm[c] = fi;
@@ -612,22 +283,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
         const bool any_dup = __syncthreads_or(dup) != 0;
         int nd = n_cand;
         if (any_dup) {
-            // a leader's value is the left-to-right sum of its occurrences: later occurrences are added in index order by
-            // ONE wave, lane m doing model m (a lane's accesses to one address execute in program order)
-            if (tid < WAVE) {
-                for (int c0 = 0; c0 < n_cand; c0 += WAVE) {
-                    const int c = c0 + lane;
-                    const int pc = c < n_cand ? L.perm[c] : c;
-                    u64 dm = __ballot(pc != c);
-                    while (dm != 0ull) {
-                        const int sl = __ffsll((long long)dm) - 1;
-                        dm &= dm - 1ull;
-                        const int cc = c0 + sl;
-                        const int lead = __shfl(pc, sl);
-                        if (lane < M) L.w[lane * wst + lead] = L.w[lane * wst + lead] + L.w[lane * wst + cc];
-                    }
-                }
-            }
+            if (tid < WAVE) sum_duplicates(L, n_cand, M);
             __syncthreads();
             // compact the leaders in order (dictionary insertion order): a chunk's reads come before the scan's barriers, its
             // writes after them, and land at or below the chunk (pos <= c)
@@ -641,7 +297,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
 #pragma unroll
                 for (int m = 0; m < PR_MAX_MODELS; ++m) wc[m] = (lead && m < M) ? L.w[m * wst + c] : 0.0;
                 int tot;
-                const int ex = block_scan_excl(lead ? 1 : 0, S.wt, &tot);
+                const int ex = grp.scan_excl(lead ? 1 : 0, &tot);
                 if (lead) {
                     const int pos = nd + ex;
                     L.key[pos] = kc; L.ts[pos] = tc;
@@ -655,19 +311,8 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
 
         // ---- select and emit (:240-276), model by model ----
         for (int m = 0; m < M; ++m) {
-            const long long ob = (long long)m * out_stride + qi * k;
+            if (nd <= k) { emit_all(grp, O, L, m, qi, k, nd, qt); continue; }
             const double *wm = L.w + m * wst;
-            if (nd <= k) {
-                for (int j = tid; j < k; j += WS_THREADS) {
-                    const bool a = j < nd;
-                    out_nodes[ob + j] = a ? (int)(unsigned)(L.key[j] & 0xffffffffull) : 0;
-                    out_eidx[ob + j] = a ? (int)(unsigned)(L.key[j] >> 32) : 0;
-                    out_w[ob + j] = a ? (float)wm[j] : 0.f;
-                    const float tsf = a ? (float)L.ts[j] : 0.f;
-                    out_dt[ob + j] = (float)(qt - (double)tsf);
-                }
-                continue;
-            }
             // np.argsort(values)[-k:] in numba's order (topk_select_any's contract, numba_sort.hpp)
             const int drop = nd - k;
             int odd = 0;                                                // a pattern whose order is not its value's: negative, NaN
@@ -734,13 +379,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_pruned_topk_ws(
                 for (int q = tid; q < k; q += WS_THREADS) S.sel[q] = L.perm[drop + q];
                 __syncthreads();
             }
-            for (int j = tid; j < k; j += WS_THREADS) {
-                const int c = S.sel[j];
-                out_nodes[ob + j] = (int)(unsigned)(L.key[c] & 0xffffffffull);
-                out_eidx[ob + j] = (int)(unsigned)(L.key[c] >> 32);
-                out_w[ob + j] = (float)wm[c];
-                out_dt[ob + j] = (float)(qt - (double)(float)L.ts[c]);
-            }
+            emit_selected(grp, O, L, m, qi, k, S.sel, qt);
             __syncthreads();
         }
     }
@@ -974,14 +613,15 @@ extern "C" int zt_csr_reserve_pruning(zt_csr *c, int32_t width, int32_t depth, i
     return ZT_OK;
 }
 
-// one launch for up to PR_MAX_MODELS models; out arrays are [M][nq][k]
+// out arrays are [M][nq][k]; one launch per group of models, in either form
 static int pruned_launch(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
                          int32_t depth, int M, const double *alpha, const double *beta, int32_t k, int32_t *on, int32_t *oe,
                          float *od, float *ow, int32_t *status_dev, hipStream_t s, bool zero_empty = false)
 {
-    const PrunePlan plan = prune_plan(width, depth, M, k, 0x7fffffffffffffffll);
+    PrunePlan plan = prune_plan(width, depth, M, k, 0x7fffffffffffffffll);
     if (plan.form == ZT_PRUNE_FORM_REFUSED) return ZT_ERR_UNSUPPORTED;
-    if (plan.form == ZT_PRUNE_FORM_WORKSPACE) {
+    const bool ws = plan.form == ZT_PRUNE_FORM_WORKSPACE;
+    if (ws) {
         if (!c->ws || plan.cap_c > c->ws_cap_c || plan.cap_f > c->ws_cap_f) {
             set_error("zt_pruned_topk: k=%d width=%d depth=%d exceeds the LDS-resident limits (k<=%d, sum width^d<=%d) and the "
                       "handle holds no workspace that covers it: use a narrower walk or reserve a workspace: "
@@ -990,50 +630,40 @@ static int pruned_launch(const zt_csr *c, const int32_t *q_nodes_dev, const doub
         }
         // the workspace serves one launch at a time: behind the previous one, on whatever stream that ran
         if (c->ws_used && c->ws_stream != s) ZT_HIP(hipStreamWaitEvent(s, c->ws_event, 0));
-        const int grid = (int)(nq < c->ws_slabs ? nq : c->ws_slabs);
-        for (int m0 = 0; m0 < M;) {
-            const int mm = M - m0 < c->ws_models ? M - m0 : c->ws_models;
-            PruneModels pm;
-            pm.M = mm;
-            for (int q = 0; q < mm; ++q) { pm.alpha[q] = alpha[m0 + q]; pm.beta[q] = beta[m0 + q]; }
-            const size_t o = (size_t)m0 * nq * k;
-            ZT_PROF_BEGIN(s, P_PRUNE);
-            k_pruned_topk_ws<<<grid, WS_THREADS, 0, s>>>(c->indptr, c->nbr, c->eid, c->ts, c->N, q_nodes_dev, q_ts_dev, nq, width,
-                                                         depth, pm, k, on + o, oe + o, od + o, ow + o, (long long)nq * k,
-                                                         status_dev, c->ws_cap_c, c->ws_cap_f, c->ws_models, (char *)c->ws,
-                                                         c->ws_slab_bytes, zero_empty ? 1 : 0);
-            ZT_PROF_END(s, P_PRUNE);
-            ZT_LAUNCH_CHECK();
-            m0 += mm;
-        }
-        ZT_HIP(hipEventRecord(c->ws_event, s));
-        c->ws_stream = s; c->ws_used = true;
-        return ZT_OK;
     }
-    const int cap_c = (int)plan.cap_c, cap_f = (int)plan.cap_f;
 #ifdef ZT_DIAG
     static const int dbg_stop = getenv("ZT_PRUNE_STOP") ? atoi(getenv("ZT_PRUNE_STOP")) : 0;   // diagnostic builds only (WRONG results): 1 walk only, 2 + merge
 #else
     constexpr int dbg_stop = 0;
 #endif
     for (int m0 = 0; m0 < M;) {
-        // as many models per launch as the workgroup's LDS allows (at least one)
-        int mm = M - m0 < PR_MAX_MODELS ? M - m0 : PR_MAX_MODELS;
-        while (mm > 1 && prune_lds_bytes(cap_c, cap_f, mm, k) * PR_WAVES > 64 * 1024) --mm;
+        // The models that remain are planned like a call of their own.  The form does not depend on M, and a launch's bytes
+        // are monotone in its models, so a group is min(remaining, the first plan's models) of them; a last group of fewer
+        // models asks for the LDS of that many.  A workspace carries the models it was reserved for.
+        if (m0 > 0) plan = prune_plan(width, depth, M - m0, k, 0x7fffffffffffffffll);
+        const int mm = ws && c->ws_models < plan.models ? c->ws_models : plan.models;
         PruneModels pm;
         pm.M = mm;
         for (int q = 0; q < mm; ++q) { pm.alpha[q] = alpha[m0 + q]; pm.beta[q] = beta[m0 + q]; }
-        const size_t lds = prune_lds_bytes(cap_c, cap_f, mm, k) * PR_WAVES;
-        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_pruned_topk), lds));
-        const int grid = (int)((nq + PR_WAVES - 1) / PR_WAVES);
         const size_t o = (size_t)m0 * nq * k;
+        if (!ws) ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_pruned_topk), (size_t)plan.lds));
         ZT_PROF_BEGIN(s, P_PRUNE);
-        k_pruned_topk<<<grid, WAVE * PR_WAVES, lds, s>>>(c->indptr, c->nbr, c->eid, c->ts, c->N, q_nodes_dev, q_ts_dev, nq,
-                                                         width, depth, pm, k, on + o, oe + o, od + o, ow + o,
-                                                         (long long)nq * k, status_dev, cap_c, cap_f, dbg_stop, zero_empty ? 1 : 0);
+        if (ws)
+            k_pruned_topk_ws<<<(int)(nq < c->ws_slabs ? nq : c->ws_slabs), plan.threads, 0, s>>>(
+                c->indptr, c->nbr, c->eid, c->ts, c->N, q_nodes_dev, q_ts_dev, nq, width, depth, pm, k, on + o, oe + o, od + o,
+                ow + o, (long long)nq * k, status_dev, c->ws_cap_c, c->ws_cap_f, c->ws_models, (char *)c->ws, c->ws_slab_bytes,
+                zero_empty ? 1 : 0);
+        else
+            k_pruned_topk<<<(int)((nq + PR_WAVES - 1) / PR_WAVES), plan.threads, (size_t)plan.lds, s>>>(
+                c->indptr, c->nbr, c->eid, c->ts, c->N, q_nodes_dev, q_ts_dev, nq, width, depth, pm, k, on + o, oe + o, od + o,
+                ow + o, (long long)nq * k, status_dev, (int)plan.cap_c, (int)plan.cap_f, dbg_stop, zero_empty ? 1 : 0);
         ZT_PROF_END(s, P_PRUNE);
         ZT_LAUNCH_CHECK();
         m0 += mm;
+    }
+    if (ws) {
+        ZT_HIP(hipEventRecord(c->ws_event, s));
+        c->ws_stream = s; c->ws_used = true;
     }
     return ZT_OK;
 }
@@ -1052,11 +682,11 @@ extern "C" int zt_pruned_topk(const zt_csr *c, const int32_t *q_nodes_dev, const
                          out_dt_dev, out_w_dev, status_dev, (hipStream_t)stream);
 }
 
-// zt_pruned_topk_multi into output arrays that were NOT cleared: rows with an empty dictionary are written as zeros by the kernel
-int zt::pruned_topk_multi_fill(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
-                               int32_t depth, int32_t n_models, const double *alpha_host, const double *beta_host, int32_t k,
-                               int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev,
-                               int32_t *status_dev, void *stream)
+// zero_empty: the output arrays were NOT cleared, rows with an empty dictionary are written as zeros by the kernel
+static int pruned_multi(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
+                        int32_t depth, int32_t n_models, const double *alpha_host, const double *beta_host, int32_t k,
+                        int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev, int32_t *status_dev,
+                        void *stream, bool zero_empty)
 {
     if (!c || nq < 0 || width <= 0 || depth <= 0 || k <= 0 || !status_dev || n_models <= 0 || !alpha_host || !beta_host) {
         set_error("zt_pruned_topk_multi: bad argument");
@@ -1064,7 +694,16 @@ int zt::pruned_topk_multi_fill(const zt_csr *c, const int32_t *q_nodes_dev, cons
     }
     if (nq == 0) return ZT_OK;
     return pruned_launch(c, q_nodes_dev, q_ts_dev, nq, width, depth, n_models, alpha_host, beta_host, k, out_nodes_dev,
-                         out_eidx_dev, out_dt_dev, out_w_dev, status_dev, (hipStream_t)stream, true);
+                         out_eidx_dev, out_dt_dev, out_w_dev, status_dev, (hipStream_t)stream, zero_empty);
+}
+
+int zt::pruned_topk_multi_fill(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
+                               int32_t depth, int32_t n_models, const double *alpha_host, const double *beta_host, int32_t k,
+                               int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev,
+                               int32_t *status_dev, void *stream)
+{
+    return pruned_multi(c, q_nodes_dev, q_ts_dev, nq, width, depth, n_models, alpha_host, beta_host, k, out_nodes_dev,
+                        out_eidx_dev, out_dt_dev, out_w_dev, status_dev, stream, true);
 }
 
 extern "C" int zt_pruned_topk_multi(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq,
@@ -1072,11 +711,6 @@ extern "C" int zt_pruned_topk_multi(const zt_csr *c, const int32_t *q_nodes_dev,
                                     const double *beta_host, int32_t k, int32_t *out_nodes_dev, int32_t *out_eidx_dev,
                                     float *out_dt_dev, float *out_w_dev, int32_t *status_dev, void *stream)
 {
-    if (!c || nq < 0 || width <= 0 || depth <= 0 || k <= 0 || !status_dev || n_models <= 0 || !alpha_host || !beta_host) {
-        set_error("zt_pruned_topk_multi: bad argument");
-        return ZT_ERR_ARG;
-    }
-    if (nq == 0) return ZT_OK;
-    return pruned_launch(c, q_nodes_dev, q_ts_dev, nq, width, depth, n_models, alpha_host, beta_host, k, out_nodes_dev,
-                         out_eidx_dev, out_dt_dev, out_w_dev, status_dev, (hipStream_t)stream);
+    return pruned_multi(c, q_nodes_dev, q_ts_dev, nq, width, depth, n_models, alpha_host, beta_host, k, out_nodes_dev,
+                        out_eidx_dev, out_dt_dev, out_w_dev, status_dev, stream, false);
 }
