@@ -101,6 +101,8 @@ int zt_stream_destroy(void *stream);
 #define ZT_RELEASE_MEMBER 1
 #define ZT_RELEASE_LAUNCH 2
 #define ZT_RELEASE_LAUNCH_FULL 3
+#define ZT_RELEASE_MEMBER_FRONT 4 /* by member, every batch's gate in front of its own step (the library's pick lets the GRU kernel of the
+                                  * step before carry it where that kernel is the step's last: pipeline.hip) */
 #define ZT_MSG_ONE 1
 #define ZT_MSG_TWO 2
 #define ZT_SCORE_LATENCY 1
@@ -638,6 +640,9 @@ int zt_pipeline_set_stats(zt_pipeline *p, float *avg_topk_dev);
  * non-zero the streaming T-PPR state is AHEAD of the last step: a caller must not query or update the state
  * through zt_tppr_stream (or leave the announced order) before those batches have been stepped. */
 int zt_pipeline_outstanding(const zt_pipeline *p);
+/* Steps since zt_pipeline_create whose GRU kernel carried the NEXT batch's gate of the release by member at its tail, so that
+ * the next step passed no gate of its own (pipeline.hip, "the gate at the tail of the GRU"); for tests and tools. */
+int zt_pipeline_tail_gates(const zt_pipeline *p);
 /* Returns ZT_ERR_TIMEOUT (once) when a kernel of an EARLIER step gave up a bounded in-kernel wait -- the gate between the
  * output layers and the GRU update in their shared launch waits at most 4 s for the source path's reads, then leaves the
  * memory rows of its tile untouched and reports to the status word of the descriptor and to a host-mapped latch that

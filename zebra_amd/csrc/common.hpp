@@ -143,6 +143,7 @@ struct embed_out_deferred {
     int gx;
     int *latch;            // host-mapped word a gate wait that gives up writes ZT_ERR_TIMEOUT to (or NULL); kept across embed_ex calls
 };
+struct member_gate;                                                         // (below: the wait for one batch's T-PPR rows)
 int embed_out_launch(const embed_out_deferred &d, void *stream);           // aggregate.hip: the output layers as a kernel of their own
 // zt_gru_update with the projected-table refresh folded into the GRU kernel (memory_update.hip); wm_p from embed_wm_ptr.
 // counter_zeroed: the row counter (first word of the workspace) is zero already; select_done: the row list and the counter
@@ -152,7 +153,10 @@ int gru_update_ex(float *memory_dev, float *last_update_dev, const float *messag
                   uint8_t *flags_dev, int64_t num_nodes, int32_t D, int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
                   const int32_t *n_ids_dev, const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready,
                   const float *wm_p, float *proj_table, void *stream, bool counter_zeroed = false, bool select_done = false,
-                  embed_out_deferred *fuse = nullptr, int cell = ZT_CELL_GRU);
+                  embed_out_deferred *fuse = nullptr, int cell = ZT_CELL_GRU, const member_gate *tail_gate = nullptr,
+                  bool *tail_carried = nullptr);
+// tail_gate (pipeline.hip, "the gate at the tail of the GRU"): the wait for the NEXT batch's T-PPR rows, carried by the first
+// workgroup of the plain k_gru once its rows are written; *tail_carried says whether the kernel that was launched took it along
 // zt_store_messages_range that also zeroes one int (the GRU update's row counter: first word of its workspace)
 int store_messages_ex(const float *memory_dev, const float *last_update_dev, const float *efeat_dev, const float *time_w_dev,
                       int64_t num_nodes, int64_t num_edges, int32_t D, int32_t F, int32_t T, const int32_t *src_dev,
@@ -168,6 +172,7 @@ struct member_gate {
     const int32_t *word;
     int32_t target;
     int *latch;            // host-mapped word a wait that gives up writes ZT_ERR_TIMEOUT to (or NULL)
+    int32_t *status;       // ... and the status word (gru_update_ex's tail gate: that call has no status argument of its own)
 };
 int member_gate_launch(const member_gate &g, int32_t *status_dev, void *stream);      // aggregate.hip
 // zt_embed with an event the stream waits for between the aggregation kernel and the output layer (pipeline.hip: the

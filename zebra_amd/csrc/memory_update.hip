@@ -274,6 +274,11 @@ struct GruArgs {
     const float *Wih_p, *Whh_p, *b_ih, *b_hh, *Wm_p;
     float *P;
     int cap;
+    // the wait for the NEXT batch's T-PPR rows (common.hpp: member_gate), carried by one thread of k_gru's first workgroup
+    // behind its own tile, or NULL: see pipeline.hip, "the gate at the tail of the GRU"
+    const int *next_word;
+    int next_target;
+    int *next_status, *next_latch;
 };
 
 // bid = the workgroup's 16-row tile.  gate != nullptr (k_out_gru): before a row of the memory table is written every
@@ -486,6 +491,11 @@ __global__ __launch_bounds__(64 * GRU_WAVES) void k_gru(GruArgs G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     gru_body<CELL, NW>(G, smem, blockIdx.x, nullptr);
+    // (one thread of ONE workgroup, once it has returned from its own tile -- other waves and workgroups may still be storing:
+    //  the gate only reads a counter, and the kernel boundary behind this kernel orders the rows.  One resident workgroup of a
+    //  kernel that is running out, not a persistent kernel on every compute unit: the wait keeps nobody's prepass out)
+    if (G.next_word != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+        (void)member_gate_wait<4>(G.next_word, G.next_target, G.next_status, G.next_latch);
 }
 
 // The output layers and the GRU update in ONE launch (round 5).  The two kernels are independent but for the memory rows the
@@ -976,8 +986,9 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
                       uint8_t *flags_dev, int64_t num_nodes, int32_t D, int32_t msg_dim, const int32_t *ids_dev, int64_t n_ids,
                       const int32_t *n_ids_dev, const zt_gru_weights *wt, void *workspace_dev, int32_t weights_ready,
                       const float *wm_p, float *proj_table, void *stream, bool counter_zeroed, bool select_done,
-                      zt::embed_out_deferred *fuse, int cell)
+                      zt::embed_out_deferred *fuse, int cell, const zt::member_gate *tail_gate, bool *tail_carried)
 {
+    if (tail_carried) *tail_carried = false;
     // (output layers held back by embed_ex run exactly once whatever happens: fused with the GRU kernel, else launched in
     //  front of it or on the way out)
     struct PendingOut {
@@ -1029,8 +1040,14 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
         ZT_HIP(hipMemsetAsync(cnt + GRU_SRC_WORD, 0, 2 * sizeof(int), s));   // the gate's two words (a fresh workspace; afterwards every launch leaves them at zero)
     }
     if (mp.out == OutLaunch::front) { const int rc = pending.launch(); if (rc != ZT_OK) return rc; }
-    const GruArgs G{memory_dev, last_update_dev, messages_dev, msg_ts_dev, rows, cnt, D, msg_dim, p.Xp, p.Hp, p.lda,
-                    wih, whh, wt->b_ih, wt->b_hh, wm_p, proj_table, (int)max_rows};
+    GruArgs G{memory_dev, last_update_dev, messages_dev, msg_ts_dev, rows, cnt, D, msg_dim, p.Xp, p.Hp, p.lda,
+              wih, whh, wt->b_ih, wt->b_hh, wm_p, proj_table, (int)max_rows, nullptr, 0, nullptr, nullptr};
+    // (the plain tiled kernel alone takes the tail gate along: the fused and the split forms are other steps' kernels)
+    if (mp.out != OutLaunch::fused_tile && mp.out != OutLaunch::fused_split && mp.gru == GruForm::tile && tail_gate != nullptr &&
+        tail_gate->word != nullptr && tail_gate->status != nullptr && tail_carried != nullptr) {
+        G.next_word = tail_gate->word; G.next_target = tail_gate->target; G.next_status = tail_gate->status; G.next_latch = tail_gate->latch;
+        *tail_carried = true;
+    }
     const GruSplitArgs GS{G, reinterpret_cast<int *>(ws + p.off_tiles), reinterpret_cast<float *>(ws + p.off_hnew)};
     const SrcGate gate{cnt + GRU_SRC_WORD, mp.target, mp.participants, held.present ? fuse->args.status : nullptr,
                        held.present ? fuse->latch : nullptr};

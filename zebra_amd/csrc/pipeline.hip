@@ -58,6 +58,7 @@ struct zt_pipeline {
         float *od, *ow;
         int32_t *mdone;        // [TPPR_MEMBER_WORDS] per member: the (edge, model) tasks whose output rows are written (k_stream)
         bool by_member;        // the launch counts there: the main stream passes a gate per member instead of waiting for `ready_ev`
+        unsigned tail_gated;   // bit j: member j's gate was carried by the GRU kernel of the step before it (no gate of its own)
         hipEvent_t ready;      // T-PPR outputs complete (side stream)
         hipEvent_t ready_ev;   // the event to wait on for that: `ready`, or the one the T-PPR update recorded itself
         hipEvent_t consumed;   // main stream is done with the slot
@@ -106,6 +107,7 @@ struct zt_pipeline {
     // (the gate of k_out_gru / k_out_gru2, memory_update.hip) writes ZT_ERR_TIMEOUT here at system scope, and the NEXT step
     // call fails with it -- no synchronisation, and a caller that never reads the status word still hears of it.
     int *latch_host, *latch_dev;
+    int tail_gates;            // steps whose GRU kernel carried the next batch's gate (zt_pipeline_tail_gates)
 };
 
 namespace {
@@ -253,6 +255,7 @@ int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int 
     for (int j = 0; j < g.n; ++j) { s.key[j] = g.eidx[j]; s.B[j] = g.B[j]; }
     s.n = g.n; s.n_done = 0; s.Btot = g.Btot; s.token = 0; s.launched = false; s.used = true; s.waited = false;
     s.by_member = by_member && g.n > 1;
+    s.tail_gated = 0u;
     s.q_lo = 0; s.q_hi = 0;
     *out = &s;
     return ZT_OK;
@@ -402,6 +405,8 @@ extern "C" int zt_pipeline_outstanding(const zt_pipeline *p)
         if (s.n > 0 && s.launched) n += s.n - s.n_done;
     return n;
 }
+
+extern "C" int zt_pipeline_tail_gates(const zt_pipeline *p) { return p ? p->tail_gates : 0; }
 
 extern "C" int zt_pipeline_set_stats(zt_pipeline *p, float *avg_topk_dev)
 {
@@ -564,8 +569,10 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
     // C5 (0.296 against 0.305 ms/step at 200 steps): while the main stream waits for the T-PPR update, a persistent aggregation
     // kernel that is already resident fills all of its compute units' registers, and the prepass kernels of the next launch
     // group -- on a stream without a CU mask -- are left with the T-PPR stream's compute units, beside the hub chains.
-    zt::member_gate gate = {nullptr, 0, p->latch_dev};
-    if (s->by_member) {
+    zt::member_gate gate = {nullptr, 0, p->latch_dev, d.status};
+    if (s->by_member && (s->tail_gated & (1u << j)) != 0u) {
+        // the GRU kernel of the previous step waited for this batch's rows at its tail (below): nothing to pass here
+    } else if (s->by_member) {
         // The counters are zeroed by the group's staging kernel, on another stream: the gate must not look at them before that
         // kernel has run -- what is left there from the slot's previous group IS a full count.  In practice the staging is two
         // launch groups ahead of this step; by construction it is this wait, once per group (`filled` is recorded behind the
@@ -675,10 +682,47 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
     // ---- P3: the GRU update over the messages built beside the aggregation; the refresh of the projected rows rides
     // inside the GRU kernel once the padded W_m is in the embed workspace ----
     if (!msgs_waited) ZT_HIP(hipStreamWaitEvent(p->main_s, p->msgs_done, 0));
+    // THE GATE AT THE TAIL OF THE GRU (round 8).  Large batches pass the gate of the release by member as a one-wave kernel in
+    // front of the aggregation (above): ~7 us of kernel + a kernel boundary of every step of a main stream that, on C5, is level
+    // with the T-PPR stream.  Where this step's GRU kernel is the LAST thing the step puts on the main stream and the next
+    // batch's slot is launched and released by member, the wait for the NEXT batch's rows rides at the tail of that kernel
+    // instead: one thread of its first workgroup, once that thread is through with its tile -- one resident workgroup of a
+    // kernel that is running out, so (unlike a persistent aggregation kernel waiting on every compute unit) it keeps the next
+    // group's prepass out of nothing.  The next step then finds its bit set.  The kernel boundary between this GRU and the next aggregation stays, so the rows are read by a
+    // kernel that starts after the count was seen, as behind k_member_gate.
+    // The counters of a NEW group are zeroed by its staging kernel on another stream, and what the slot's previous group left
+    // there is a full count (see the gate in front): the GRU kernel is ordered behind the group's `filled` event first, once per
+    // group -- the very wait the next step would otherwise put in front of its own gate; as a rule the event is complete
+    // (staged two launch groups ahead) and asking is enough.
+    // What it costs: the NEXT step's `entry` record on the main stream now lies behind this wait, and the message stream and
+    // the staging of later groups wait for `entry` (make_group: an `entry` behind the wait for the T-PPR update once cost a
+    // quarter of a millisecond at the start of a region).  So wherever the T-PPR stream is the slower one, the next step's
+    // message build and the staging two groups ahead start one gate-wait later: round 6 saw the 20-step region lose 0.8 % to
+    // it while the steady state gained; profiles/r8/experiments/launch_head_packets_gate_ab.log has both regions.
+    // ZT_RELEASE_MEMBER_FRONT keeps every gate in front of its own step (validation).
+    zt::member_gate tail = {nullptr, 0, p->latch_dev, d.status};
+    zt_pipeline::Slot *nxt = nullptr;
+    int jn = 0;
+    const bool tail_off = zt::kernel_choice(ZT_CHOICE_GROUP_RELEASE) == ZT_RELEASE_MEMBER_FRONT;
+    const bool gru_is_last = !tail_off && whole && n_rows > 0 && !p->aff_on && p->xchg == nullptr && (d.proj_table == nullptr || wm_p != nullptr);
+    if (gru_is_last && n_ahead > 0 && valid_batch(p, ahead)) {
+        nxt = find_slot(p, ahead, &jn);
+        // (a step of a small batch on CU-masked streams passes its gate inside its aggregation kernel: nothing to carry for it)
+        const bool next_in_kernel = p->masked && 3 * ahead->B <= 2048 && p->avg_topk == nullptr;
+        if (nxt != nullptr && nxt->by_member && nxt->launched && !next_in_kernel && (nxt->tail_gated & (1u << jn)) == 0u) {
+            if (!nxt->waited) {
+                if (hipEventQuery(nxt->filled) != hipSuccess) { (void)hipGetLastError(); ZT_HIP(hipStreamWaitEvent(p->main_s, nxt->filled, 0)); }
+                nxt->waited = true;
+            }
+            tail.word = nxt->mdone + jn; tail.target = (int32_t)(nxt->B[jn] * d.M);
+        }
+    }
+    bool carried = false;
     rc = zt::gru_update_ex(d.memory, d.last_update, d.messages, d.msg_ts, d.flags, d.num_nodes, d.D, msg_dim, nodes_cur, 2 * B,
                            nullptr, &d.gw, d.gru_ws, p->gru_ready ? 1 : 0, wm_p, wm_p ? d.proj_table : nullptr, p->main_s, true, true,
-                           n_rows > 0 ? &p->out_gru : nullptr, p->cell);
+                           n_rows > 0 ? &p->out_gru : nullptr, p->cell, tail.word ? &tail : nullptr, &carried);
     if (rc != ZT_OK) return rc;
+    if (carried && nxt != nullptr) { nxt->tail_gated |= 1u << jn; p->tail_gates++; }
     p->gru_ready = true;
     if (scored) {                                // compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written
         const int par = p->score_n & 1;

@@ -52,12 +52,16 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     MailSlot *in_slot = &mail->slot[(tpos - 1) % MAIL_R], *out_slot = &mail->slot[tpos % MAIL_R];
     PreScale pre_scale;
     pre_scale.valid = false;
-    // the norm the hub's row will arrive with and the scale factors that follow from it: worked out for every position when
-    // the workgroup started (zt_tppr::hubscale, k_stream) -- four doubles, on their way beside the partner's row; the lean
-    // section still holds the norm that ARRIVES against this one, bit for bit
+    // the norm the hub's row will arrive with and the scale factors that follow from it: worked out for every position by the
+    // workgroup's last wave, the first block before the first hop and the rest beside the hops (zt_tppr::hubscale, k_stream)
+    // -- four doubles, on their way beside the partner's row; the lean section still holds the norm that ARRIVES against
+    // this one, bit for bit.  mail->sc_ready says how far the table is written (a bounded wait, here off the chain; it is
+    // ahead of the hops as a rule); agent-scope loads: a 128-byte line holds four positions, and a plain load may find a
+    // line this compute unit fetched before its later positions were written.
     {
+        if (!wait_past(&mail->sc_ready, tpos, h.ctl + 2, i, -3)) wl_fail |= 128;
         const double *sc = hub_scale(h, m, chain_idx, tpos);
-        const double sn = sc[0], sn1 = sc[1], s1 = sc[2], s2 = sc[3];
+        const double sn = ld_agent(sc), sn1 = ld_agent(sc + 1), s1 = ld_agent(sc + 2), s2 = ld_agent(sc + 3);
         pre_scale.norm = sn; pre_scale.norm_next = sn1; pre_scale.scale_s1 = s1; pre_scale.scale_s2 = s2;
         pre_scale.valid = sn != 0.0;
     }

@@ -71,6 +71,7 @@ struct Mail {
 #endif
     MailSlot slot[MAIL_R];
     int head;          // next position of the chain's edge list
+    int sc_ready;      // positions of the chain whose scale factors (zt_tppr::hubscale) are written: [0, sc_ready) (k_stream)
 };
 
 struct StreamArgs {
@@ -111,6 +112,24 @@ __device__ inline bool wait_seq(const int *p, int want, int *status, int what, i
         }
     }
     asm volatile("" ::: "memory");      // LDS only, in program order behind the load that has just returned (see publish_seq)
+    return true;
+}
+
+// spin until *p > want (mail.sc_ready: a count that only grows); bounded in the same way
+__device__ inline bool wait_past(const int *p, int want, int *status, int what, int aux)
+{
+    unsigned spins = 0;
+    long long t0 = 0;
+    while (lds_load_seq(p) <= want) {
+        __builtin_amdgcn_s_sleep(1);
+        if ((++spins & 4095u) == 0) {
+            const long long now = (long long)wall_clock64();
+            if (t0 == 0) t0 = now;
+            else if (now - t0 > WAIT_TICKS) { note_timeout(status, 3, what, want, lds_load_seq(p), aux); return false; }
+            if (launch_failed(status)) return false;
+        }
+    }
+    asm volatile("" ::: "memory");
     return true;
 }
 

@@ -184,6 +184,39 @@ __global__ void k_hubacc(const int *__restrict__ nodes, long long role_stride, i
     d_hubacc(blockIdx.x * blockDim.x + threadIdx.x, nodes, role_stride, B, n_roles, slot, wo, chain_of, chain_len, hv);
 }
 
+// K2e: what every hop of a chain needs to know about its edge (zt_tppr::chain_rec), one packed record per (chain, position):
+// the chain workgroup fetches its records in ONE round trip when it starts instead of walking chain_edges -> nodes -> wo / hv.
+// (After K2d: hv is final.  Chains the launch does not run have length 0.)
+__device__ __forceinline__ void d_chainrec(int c, int q, int len, const int *__restrict__ nodes, long long role_stride, int B,
+                                           const int *wo, const int *hv, const int *chain_node, const int *chain_edges,
+                                           int4 *chain_rec)
+{
+    if (q >= len) return;
+    const int hub = pre_ld(chain_node + c), e = pre_ld(chain_edges + c * CH_MAX + q);
+    const int u = nodes[e], v = nodes[role_stride + e];
+    const int other = (u == hub ? 1 : 0) * B + e;                    // the partner's access: the role the hub does not have
+    int4 r;
+    r.x = e;
+    r.y = u == v ? -1 : (u == hub ? v : u);
+    r.z = pre_ld(wo + other);
+    r.w = u == v ? -1 : pre_ld(hv + other);
+    chain_rec[c * CH_MAX + q] = r;
+}
+
+// (one row of workgroups per possible chain: those beyond the chains the launch runs, ctl[4], leave at once)
+constexpr int REC_THREADS = 256;
+__global__ __launch_bounds__(REC_THREADS) void k_chainrec(const int *__restrict__ nodes, long long role_stride, int B, const int *wo,
+                                                          const int *hv, const int *chain_node, const int *chain_len,
+                                                          const int *chain_edges, int4 *chain_rec, const int *ctl)
+{
+    const int c = blockIdx.y;
+    if (c >= ctl[4]) return;
+    int len = chain_len[c];
+    len = len < CH_MAX ? len : CH_MAX;
+    for (int q = blockIdx.x * REC_THREADS + threadIdx.x; q < len; q += gridDim.x * REC_THREADS)
+        d_chainrec(c, q, len, nodes, role_stride, B, wo, hv, chain_node, chain_edges, chain_rec);
+}
+
 // K3: scatter accesses into their node's range, encoded (edge << 2) | role.
 __device__ __forceinline__ void d_fill(int a, const int *__restrict__ nodes, long long role_stride, int B, int n_roles,
                                        const int *off, const int *slot, int *list)
@@ -336,7 +369,7 @@ __global__ __launch_bounds__(PRE_THREADS) void k_prepass_fused(
     const int *__restrict__ nodes, const long long *__restrict__ eidx, long long role_stride, int B, int n_roles,
     long long N, int *cnt, int *slot, int *off, int *list, int *wo, int *pflag, int *nxt, int *ctl, int *latch,
     int *hot_node, int *hot_cnt, int *chain_of, int *chain_node, int *chain_len, int *chain_edges, int *owner_of,
-    int *hv, int max_chains, int big_min, int grid, int n_models)
+    int *hv, int4 *chain_rec, int max_chains, int big_min, int grid, int n_models)
 {
     __shared__ int sort_s[DEPS_SORT_MAX], sort_t[2 * PRE_THREADS];
     const int tid = threadIdx.x, A = B * n_roles;
@@ -361,6 +394,15 @@ __global__ __launch_bounds__(PRE_THREADS) void k_prepass_fused(
     __syncthreads();
     for (int a = tid; a < A; a += PRE_THREADS) d_hubacc(a, nodes, role_stride, B, n_roles, slot, wo, chain_of, chain_len, hv);
     __syncthreads();
+    {
+        const int n_ch = pre_ld(ctl + 4);                                        // (the chains d_hot_select kept)
+        for (int c = 0; c < n_ch && c < MAX_CHAINS; ++c) {
+            int len = pre_ld(chain_len + c);
+            len = len < CH_MAX ? len : CH_MAX;
+            for (int q = tid; q < len; q += PRE_THREADS)
+                d_chainrec(c, q, len, nodes, role_stride, B, wo, hv, chain_node, chain_edges, chain_rec);
+        }
+    }
     for (int a = tid; a < (A > MAX_HOT ? A : MAX_HOT); a += PRE_THREADS)
         d_cleanup(a, nodes, role_stride, B, n_roles, slot, cnt, ctl, hot_node, chain_of);
     __syncthreads();
@@ -442,7 +484,7 @@ int zt::tppr_plan_chunk(zt_tppr *h, int q, const int32_t *nodes, const long long
         k_prepass_fused<<<1, PRE_THREADS, 0, s>>>(nodes, eidx, role_stride, B, n_roles, h->N, h->cnt, h->slot, h->off, h->list,
                                                   h->wo, h->pflag, h->nxt, h->ctl, h->latch_dev, h->hot_node, h->hot_cnt,
                                                   h->chain_of, h->chain_node, h->chain_len, h->chain_edges, h->owner_of,
-                                                  h->hv, max_chains, big_min, budget_grid, n_models);
+                                                  h->hv, h->chain_rec, max_chains, big_min, budget_grid, n_models);
         ZT_PROF_END(s, P_PREPASS);
     } else {
         ZT_PROF_BEGIN(s, P_PREPASS);
@@ -457,6 +499,8 @@ int zt::tppr_plan_chunk(zt_tppr *h, int q, const int32_t *nodes, const long long
         k_own<<<(B + tb - 1) / tb, tb, 0, s>>>(nodes, role_stride, B, h->cnt, h->slot, h->wo, h->chain_of, h->chain_len,
                                                h->chain_edges, h->owner_of);
         k_hubacc<<<gb, tb, 0, s>>>(nodes, role_stride, B, n_roles, h->slot, h->wo, h->chain_of, h->chain_len, h->hv);
+        k_chainrec<<<dim3(CH_MAX / REC_THREADS / 2, MAX_CHAINS), REC_THREADS, 0, s>>>(nodes, role_stride, B, h->wo, h->hv, h->chain_node,
+                                                                                     h->chain_len, h->chain_edges, h->chain_rec, h->ctl);
         ZT_PROF_END(s, P_PREPASS);
         // per-node counters and the control words back to their rest state: the set is ready for k_stream
         ZT_PROF_BEGIN(s, P_CLEANUP);

@@ -78,6 +78,9 @@ struct zt_tppr {
     int *chain_len;    // [MAX_CHAINS]
     int *chain_edges;  // [MAX_CHAINS][CH_MAX] the hub's edges in order: position = the hub's writer ordinal (wo) at that edge.
                        // An edge between two hubs is in BOTH chains: each applies its own hub's update
+    int4 *chain_rec;   // [MAX_CHAINS][CH_MAX] per chain position {edge, partner (-1: self-loop), the partner's wo, the partner's
+                       // chain if this edge is a position there too, else -1}: HopRec (tppr_chain.hpp) as the prepass knows it,
+                       // so that a chain workgroup fetches its positions in one round trip (k_chainrec, behind k_hubacc)
     int *owner_of;     // [MAX_CHUNK] the chain whose partner task (general queue) emits the edge's rows, or -1
     int *hv;           // [3 * MAX_CHUNK] per access: the chain that holds the accessed node's row by version (the row to
                        // read is version wo of that chain), or -1: the row is read from / written to `rows`
@@ -99,6 +102,7 @@ struct zt_tppr {
     struct PlanSet {
         int *cnt, *off, *slot, *list, *wo, *pflag, *nxt, *chain_of, *hot_node, *hot_cnt, *chain_node, *chain_len,
             *chain_edges, *owner_of, *hv, *ctl;
+        int4 *chain_rec;
         hipEvent_t planned, consumed;      // prepass finished / k_stream finished with the set
         bool used;                         // `consumed` has been recorded at least once
         // what the set was planned for (valid == a zt_tppr_plan result not consumed yet)
@@ -123,7 +127,7 @@ inline void use_set(zt_tppr *h, int q)
     const zt_tppr::PlanSet &P = h->set[q];
     h->cnt = P.cnt; h->off = P.off; h->slot = P.slot; h->list = P.list; h->wo = P.wo; h->pflag = P.pflag; h->nxt = P.nxt;
     h->chain_of = P.chain_of; h->hot_node = P.hot_node; h->hot_cnt = P.hot_cnt; h->chain_node = P.chain_node;
-    h->chain_len = P.chain_len; h->chain_edges = P.chain_edges; h->owner_of = P.owner_of; h->hv = P.hv; h->ctl = P.ctl;
+    h->chain_len = P.chain_len; h->chain_edges = P.chain_edges; h->chain_rec = P.chain_rec; h->owner_of = P.owner_of; h->hv = P.hv; h->ctl = P.ctl;
 }
 
 // a failure latched by an earlier launch makes every later call fail until zt_tppr_status has reported it

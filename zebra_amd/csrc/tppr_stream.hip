@@ -49,6 +49,7 @@
 #include <cstdlib>
 #include <vector>
 
+static_assert(CH_MAX % (WAVE * WAVES_PER_WG) == 0, "k_stream: a chain workgroup fetches its records in whole trips");
 static_assert(WAVES_PER_WG == zt::TPPR_WAVES_PER_WG && REG_K_MAX == zt::TPPR_REG_K_MAX, "tppr_state.hpp");
 
 namespace {
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
     __shared__ WaveLds lds[WAVES_PER_WG];
     __shared__ Mail mail;
     __shared__ int ch_edge[CH_MAX], ch_partner[CH_MAX], ch_wop[CH_MAX], ch_pch[CH_MAX];   // chain workgroups: HopRec
+    __shared__ double sc_pn[WAVE];                     // ... and the norms of the block of positions whose scale factors are in the making
     WaveLds &L = lds[threadIdx.x / WAVE];
     const int lane = lane_id();
     if (ld_agent(h.ctl + 2) == ZT_ERR_RANGE) {         // rejected by k_count: the state is not touched,
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
     }
     __builtin_amdgcn_s_setprio(3);                     // chain hops must not queue behind throughput kernels
     if (threadIdx.x < MAIL_R) { mail.slot[threadIdx.x].seq_set = 0; mail.slot[threadIdx.x].seq_ord = 0; mail.slot[threadIdx.x].seq_free = 0; }
-    if (threadIdx.x == 0) mail.head = 0;
+    if (threadIdx.x == 0) { mail.head = 0; mail.sc_ready = 0; }
 #ifdef ZT_CRIT
     if (threadIdx.x == 0) mail.t_start = (long long)__builtin_readcyclecounter();
 #endif
@@ -99,50 +101,65 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
         const long long hub = h.chain_node[c];
         int len = h.chain_len[c];
         len = len < CH_MAX ? len : CH_MAX;
-        const int *edges = h.chain_edges + c * CH_MAX;
-        // what every hop needs to know about its edge (HopRec), once, into LDS
-        for (int q = threadIdx.x; q < len; q += blockDim.x) {
-            const int e = edges[q];
-            const long long u = A.nodes[e], v = A.nodes[A.role_stride + e];
-            const int role_h = u == hub ? 0 : 1;
-            ch_edge[q] = e;
-            ch_partner[q] = u == v ? -1 : (int)(u == hub ? v : u);
-            ch_wop[q] = h.wo[(1 - role_h) * A.B + e];
-            ch_pch[q] = u == v ? -1 : h.hv[(1 - role_h) * A.B + e];
+        // what every hop needs to know about its edge (HopRec), once, into LDS: the prepass left one packed record per position
+        // (zt_tppr::chain_rec), requested here before `len` is back -- every address is inside the buffer -- so the head of
+        // the launch pays one memory round trip for them
+        {
+            const int4 *rec = h.chain_rec + c * CH_MAX;
+            constexpr int PER = CH_MAX / (WAVE * WAVES_PER_WG);
+            int4 r[PER];
+#pragma unroll
+            for (int j = 0; j < PER; ++j) r[j] = rec[threadIdx.x + j * WAVE * WAVES_PER_WG];
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int q = threadIdx.x + j * WAVE * WAVES_PER_WG;
+                if (q < len) { ch_edge[q] = r[j].x; ch_partner[q] = r[j].y; ch_wop[q] = r[j].z; ch_pch[q] = r[j].w; }
+            }
         }
-        // version 0 of the hub's row = the row as the launch finds it in `rows` (nobody stores there before the chain's last
-        // hop): copied by the last wave right away, so that nothing that reads it -- the hub's readers ahead of its first
-        // edge, that edge's partner task, another hub's chain whose first edge is this hub's first too -- waits for a hop
-        if (len > 0 && (int)(threadIdx.x / WAVE) == WAVES_PER_WG - 1) {
-            const int m0 = A.m_lo + mo;
+        // The last wave.  (1) Version 0 of the hub's row = the row as the launch finds it in `rows` (nobody stores there before
+        // the chain's last hop): copied right away, so that nothing that reads it -- the hub's readers ahead of its first edge,
+        // that edge's partner task, another hub's chain whose first edge is this hub's first too -- waits for a hop.
+        // (2) The hub's norm at every position of the chain and the scale factors that follow from it (zt_tppr::hubscale):
+        // norm <- norm * beta + beta per edge (utils/util.py:567-572), a recurrence that does not look at the rows -- ONE lane
+        // runs it from the norm the launch finds, a block of 64 positions at a time, then every position's two float64
+        // divisions by a lane of its own: scale_s1 = norm / norm' * beta, scale_s2 = beta / norm' * (1 - alpha) with
+        // norm' = norm * beta + beta (:519-522).  The FIRST block is written before the first hop; the others while the
+        // other seven waves hop (the chain takes a position per ~1.1 us, a block of 64 is a few us), mail.sc_ready =
+        // positions written so far (chain_hop waits for its own there, off the chain), and the wave joins the hops after.
+        const bool scale_wave = len > 0 && (int)(threadIdx.x / WAVE) == WAVES_PER_WG - 1;
+        const int m0 = A.m_lo + mo;
+        const double sc_alpha = h.alpha[m0], sc_beta = h.beta[m0];
+        double sc_norm = 0.0;                              // (lane 0: the norm at the next position to write)
+        auto scale_block = [&](int b0) {
+            const int n = (len + 1 - b0) < WAVE ? (len + 1 - b0) : WAVE;
+            if (lane == 0) {
+                double pn = sc_norm;
+                for (int t = 0; t < n; ++t) { sc_pn[t] = pn; pn = pn * sc_beta + sc_beta; }
+                sc_norm = pn;
+            }
+            wave_sync();
+            if (lane < n) {
+                const double pn = sc_pn[lane], nn = pn * sc_beta + sc_beta;
+                double *e = hub_scale(h, m0, c, b0 + lane);
+                st_agent(e, pn);
+                st_agent(e + 1, nn);
+                st_agent(e + 2, pn / nn * sc_beta);
+                st_agent(e + 3, sc_beta / nn * (1.0 - sc_alpha));
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the stores are at the L2 before the count says so
+            wave_sync();                                             // (and sc_pn is free for the next block)
+            if (lane == 0) __hip_atomic_store(&mail.sc_ready, b0 + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        };
+        if (scale_wave) {
             Row r0;
             (void)load_row(h, m0, hub, lane, 0u, r0);
             store_row_at(hub_version(h, m0, c, 0), h.k, lane, r0.len, r0.key, r0.ts, r0.w, r0.norm, (A.epoch << ORD_BITS) | 1u);
-            // the hub's norm at every position of the chain: norm <- norm * beta + beta per edge (utils/util.py:567-572), a
-            // recurrence that does not look at the rows -- one lane runs it from the norm the launch finds (zt_tppr::hubscale)
-            if (lane == 0) {
-                const double beta = h.beta[m0];
-                double pn = r0.norm;
-                double *tab = hub_scale(h, m0, c, 0);
-                for (int t = 0; t <= len; ++t) { st_agent(tab + 4 * t, pn); pn = pn * beta + beta; }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
+            sc_norm = r0.norm;
+            scale_block(0);
         }
         __syncthreads();
-        if (len > 0) {
-            // ... and the scale factors that follow from it, two float64 divisions per position, every position by a thread of
-            // its own: scale_s1 = norm / norm' * beta, scale_s2 = beta / norm' * (1 - alpha) with norm' = norm * beta + beta (:519-522)
-            const int m0 = A.m_lo + mo;
-            const double alpha = h.alpha[m0], beta = h.beta[m0];
-            for (int t = threadIdx.x; t <= len; t += blockDim.x) {
-                double *e = hub_scale(h, m0, c, t);
-                const double pn = ld_agent(e), nn = pn * beta + beta;
-                e[1] = nn;
-                e[2] = pn / nn * beta;
-                e[3] = beta / nn * (1.0 - alpha);
-            }
-            __syncthreads();
-        }
+        if (scale_wave)
+            for (int b0 = WAVE; b0 <= len; b0 += WAVE) scale_block(b0);
         // chain_waves (ZT_CHAIN_WAVES, default all eight) waves take hops: what a hop needs besides the hub's update -- the
         // partner's update, the emission -- runs elsewhere (process_chain_partner), but a hop's preparation and its
         // off-chain half (replay, order, stores) still add up to ~5 hop periods of one wave's time.
@@ -252,6 +269,7 @@ extern "C" int zt_tppr_create(zt_tppr **out, int64_t num_nodes, int32_t k, int32
         ZT_HIP(hipMalloc(&P.chain_node, sizeof(int) * MAX_CHAINS));
         ZT_HIP(hipMalloc(&P.chain_len, sizeof(int) * MAX_CHAINS));
         ZT_HIP(hipMalloc(&P.chain_edges, sizeof(int) * MAX_CHAINS * CH_MAX));
+        ZT_HIP(hipMalloc(&P.chain_rec, sizeof(int4) * MAX_CHAINS * CH_MAX));
         ZT_HIP(hipMalloc(&P.owner_of, sizeof(int) * MAX_CHUNK));
         ZT_HIP(hipMalloc(&P.hv, sizeof(int) * 3 * MAX_CHUNK));
         ZT_HIP(hipMemset(P.chain_of, 0xff, (size_t)num_nodes * sizeof(int)));
@@ -303,7 +321,7 @@ extern "C" int zt_tppr_destroy(zt_tppr *h)
         (void)hipFree(P.cnt); (void)hipFree(P.off); (void)hipFree(P.ctl); (void)hipFree(P.slot); (void)hipFree(P.list);
         (void)hipFree(P.wo); (void)hipFree(P.pflag); (void)hipFree(P.nxt); (void)hipFree(P.chain_of);
         (void)hipFree(P.hot_node); (void)hipFree(P.hot_cnt); (void)hipFree(P.chain_node); (void)hipFree(P.chain_len);
-        (void)hipFree(P.chain_edges); (void)hipFree(P.owner_of); (void)hipFree(P.hv);
+        (void)hipFree(P.chain_edges); (void)hipFree(P.chain_rec); (void)hipFree(P.owner_of); (void)hipFree(P.hv);
         (void)hipEventDestroy(P.planned); (void)hipEventDestroy(P.consumed);
     }
     delete h;

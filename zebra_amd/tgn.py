@@ -496,6 +496,12 @@ class TGN(torch.nn.Module):
             return 0
         return int(lib().zt_pipeline_outstanding(self._pipe))
 
+    def pipeline_tail_gates(self):
+        """Steps whose GRU kernel carried the next batch's T-PPR gate at its tail (zt_pipeline_tail_gates; 0 without a pipeline)."""
+        if getattr(self, "_pipe", None) is None:
+            return 0
+        return int(lib().zt_pipeline_tail_gates(self._pipe))
+
     def _pipe_step_main(self, batch, ahead, rows, positions):
         self._pipe_refresh()
         if getattr(self, "_score_on", False):
