@@ -7,7 +7,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from zebra_amd import _capi
-_capi.LIB_PATH = os.path.join(ROOT, 'tools/out/libzebra_crit.so')
+_capi.LIB_PATH = os.path.join(ROOT, os.environ.get('ZT_CRIT_LIB', 'tools/out/libzebra_crit.so'))
 sys.argv = ['bench.py'] + sys.argv[1:]
 try:
     runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='__main__')
@@ -26,6 +26,14 @@ for mo in (0, 1):
     big = np.bincount(ch.astype(np.int64)).argmax()   # the hub's chain: the one with the most hops
     c = c[ch == big]
     c = c[np.argsort(c[:, 15])]
+    # positions chain_hop did not take (process_edge's: self-loops of the hub) leave no stamp here: a step of TWO positions
+    # between stamped neighbours is such a hop and the hop behind it, publication to publication
+    st2 = np.diff(c[:, 15]) == 2
+    d2 = np.diff(c[:, 3])[st2]; d2 = d2[d2 < 60000]
+    nx2 = c[1:][st2]
+    if len(d2):
+        print("model %d: %d positions taken by process_edge; that hop plus the next, publication to publication %s mean %.0f clocks; the next was lean in %d" % (
+            mo, int(st2.sum()), p(d2), d2.mean(), int((nx2[:, 7] == 1).sum())))
     c = c[np.concatenate([[True], np.diff(c[:, 15]) == 1])]
     d = np.diff(c[:, 3])
     d = d[d < 60000]                                  # (hops of other batches' edges in between are not stamped)
@@ -53,4 +61,4 @@ for mo in (0, 1):
     print("model %d: lean section left at (1 not sorted / norm, 2 no prune, 3 alternate may be in the row, 4 key match / NaN, 5 picked member kept): %s" % (
         mo, dict(zip(*np.unique(non[non[:, 10] < 100][:, 10], return_counts=True)))))
 r = c2[8199]
-print("model 0, all chains and launches since the library was loaded: lean %d; left at 1 not sorted / norm %d, 2 no prune %d, 3 alternate may be in the row %d, 4 key match / NaN %d, 5 picked member kept %d; lean not tried: prepared but left (sum of 1-5) %d, no norm prediction %d, slot functions clash %d, NaN / k %d" % tuple(int(x) for x in (r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9])))
+print("model 0, all chains and launches since the library was loaded: lean %d; left at 1 not sorted / norm %d, 2 no prune %d, 3 alternate may be in the row %d, 4 key match / NaN %d, 5 picked member kept %d; lean not tried: prepared but left (sum of 1-5) %d, no norm prediction %d, slot functions clash %d, NaN / k %d; lean self-loops %d, lean behind a self-loop %d, carried on after the order wait: alternate %d, picked member kept %d" % tuple(int(x) for x in (r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[11], r[12], r[13], r[14])))

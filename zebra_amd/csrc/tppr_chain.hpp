@@ -11,7 +11,12 @@ namespace {
 // process_chain_partner's), so this is process_edge's mailbox path with everything else taken out -- no row selection by
 // role, no third row, no emission: what is left between the arrival of the row and the publication of the new kept set
 // is the chain's critical path, and every scalar branch and register move on it is paid 200 times per batch.
-// Returns false when the hop is not of this kind (first hop, another writer in between, self-loop): process_edge takes it.
+// A self-loop of the hub (rec.partner < 0; utils/util.py:501-541 with s1 == s2) is a lean hop too: every key of the row meets
+// itself, so an entry's new weight is (w * scale_s1) + (w * scale_s2) -- two rounded products and one add --, the only new
+// candidate is (edge_idx, hub, ts), and the map from w to the new weight is monotone: the arriving arrangement stays ascending.
+// The prepared side is prepare_b's on an empty partner row (one candidate, no hash table); nothing else differs.
+// Returns false when the hop is not of this kind (first hop, another writer in between, a self-loop that leaves the lean
+// section -- nothing has been written then): process_edge takes it.
 // What a hop needs to know about its edge besides the rows, gathered ONCE per launch by the whole chain workgroup into
 // LDS (k_stream): from memory these are three levels of dependent loads (edge -> endpoints -> writer ordinals / reader
 // flags) at the start of every hop's preparation.
@@ -20,6 +25,9 @@ struct HopRec {
     int wo_p;          // ordinal of the last earlier writer of the partner (the tag to expect; the hub's own is the position)
     int pchain;        // the partner is a hub itself and this edge a position of ITS chain too: that chain's index -- its
                        // row is version wo_p there and that chain applies its update --, else -1
+#ifdef ZT_CRIT
+    int prev_self;     // (diagnostic) the chain's previous position is a self-loop
+#endif
 };
 
 __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h, const StreamArgs &A, WaveLds &L, int lane, int i, int mo, Mail *mail,
@@ -29,8 +37,8 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     if (prev_edge < 0 || h.k > REG_K_MAX) return false;
     const int k = h.k;
     const int m = A.m_lo + mo;
-    if (rec.partner < 0) return false;
-    const long long pnode = rec.partner;
+    const bool self = rec.partner < 0;                                       // (scalar: the record was read to scalar registers)
+    const long long pnode = self ? hub : rec.partner;
     const int wo_h = tpos, wo_p = rec.wo_p;                                  // (chain position = the hub's writer ordinal)
     const double alpha = h.alpha[m], beta = h.beta[m];
     const unsigned epoch = A.epoch, tag_base = epoch << ORD_BITS, vtag = tag_base | 1u;
@@ -43,9 +51,11 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     // ---- the partner's row: from `rows` (poll where a writer of this launch precedes us), or -- the partner is a hub and
     // ---- its chain holds this edge too -- the version of its row at that chain's position ----
     Row rp;
+    // (a self-loop has no partner row: psrc is worked out -- a valid address, the hub's own row -- but never read or polled)
     const RowSrc psrc = row_src(h, m, pnode, wo_p, rec.pchain, tag_base, vtag);
     RawRow praw;
-    load_row_issue(psrc.base, k, lane, praw);                               // on its way while the rest is looked up
+    if (!self) load_row_issue(psrc.base, k, lane, praw);                    // on its way while the rest is looked up
+    else praw.g0 = praw.g1 = praw.g2 = praw.g3 = praw.g4 = praw.g5 = praw.gh = 0;   // (a self-loop has no partner row: empty)
     const double tnow = A.tsv[i];
     const long long e = A.eidx[i];
     const bool hub_to_memory = next_edge < 0;                               // see process_edge: the chain's last hop only
@@ -65,7 +75,8 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
         pre_scale.norm = sn; pre_scale.norm_next = sn1; pre_scale.scale_s1 = s1; pre_scale.scale_s2 = s2;
         pre_scale.valid = sn != 0.0;
     }
-    if (row_from_raw(praw, k, lane, psrc.expect, rp) != psrc.expect && psrc.polled)
+    if (self) { rp.key = 0ull; rp.ts = 0.0; rp.w = 0.0; rp.len = 0; rp.norm = 0.0; }
+    else if (row_from_raw(praw, k, lane, psrc.expect, rp) != psrc.expect && psrc.polled)
         if (!load_row_wait_at(psrc.base, k, lane, psrc.expect, rp, h.ctl + 2, (int)pnode, psrc.aux(m), psrc.version)) wl_fail |= 2;
     // ---- while the hub's row is on its way: everything that depends on the partner only ----
     int pre_hash = 0;                           // 1 / 3: partner entered into this wave's hash table (slot function 1 / 2),
@@ -98,6 +109,8 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     if (pre_hash != 2) prepare_b(lane, k, alpha, rp, nkey, tnow, pre_scale, pre_b, h2slot);
     // the partner's row has arrived (its tags were looked at): the partner task may store the partner's new row.  (No
     // s_waitcnt vmcnt(0) here: it would also wait for the write-through stores of this wave's previous hop.)
+    // (A self-loop's partner task stores no row and never waits for this flag; process_edge writes the same word again when a
+    //  self-loop is handed back to it: harmless both ways.)
     st_agent(h.cdone + (long long)m * MAX_CHUNK + i, epoch);
     CRIT(5);
     HSTAMP(1);
@@ -167,8 +180,10 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
     // code below, which starts from the mailbox again.
 #ifdef ZT_CRIT
 #define LEANC(c) do { crit_t[10] = (c); if (lane == 0 && mo == 0) atomicAdd((unsigned long long *)&g_crit[8199 * 16 + (c)], 1ull); } while (0)
+#define LEANN(c) do { if (lane == 0 && mo == 0) atomicAdd((unsigned long long *)&g_crit[8199 * 16 + (c)], 1ull); } while (0)   // (count only)
 #else
 #define LEANC(c) do { } while (0)
+#define LEANN(c) do { } while (0)
 #endif
     bool lean_done = false;
     if (pre_b.ok) {
@@ -181,8 +196,20 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             if (low) { ckey = in_slot->key[lane]; cts = in_slot->ts[lane]; hw = in_slot->w[lane]; }
             const int fs = lds_load_seq(&out_slot->seq_free);
             const unsigned hz = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.z);
-            const unsigned hunc = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.w);
-            const int n1 = (int)(hz & 0xffu), munc = (int)((hz >> 8) & 0xffu), nalt = (int)((hz >> 16) & 0xffu);
+            unsigned hunc = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.w);
+            const int n1 = (int)(hz & 0xffu);
+            int munc = (int)((hz >> 8) & 0xffu), nalt = (int)((hz >> 16) & 0xffu);
+            // Where only the IDENTITY of some entries of equal weight is missing (an alternate of a straddling run may be in
+            // the row; a picked member is kept): off the chain's priority, wait for the predecessor's replay and take the keys
+            // in dictionary order.  The weights by position are the same in both arrangements (hub_to_dict), so the merge
+            // network's result stands; the row is final from here on and the key tests are made on the final keys.
+            auto settle = [&]() {
+                __builtin_amdgcn_s_setprio(1);
+                if (!wait_seq(&in_slot->seq_ord, tpos, h.ctl + 2, i, -prev_edge - 2)) wl_fail |= 32;
+                if (low) { ckey = in_slot->key2[lane]; cts = in_slot->ts2[lane]; }
+                hunc = 0u; munc = 0; nalt = 0;
+                __builtin_amdgcn_s_setprio(3);
+            };
             // sorted arrangement, predicted norm (bit patterns on the scalar unit: both are finite and positive)
             const unsigned h0 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.x), h1 = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.y);
             if ((hz >> 24) == 0u || h0 != pn0 || h1 != pn1 || (h0 | h1) == 0u) { LEANC(1); return false; }
@@ -196,7 +223,7 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
                 const u64 alt = in_slot->alt_key[lane & 31];
                 bool t = lane < nalt && alt == nkey;
                 if (table) t = t || (lane < nalt && L.htab[key_hash_m(alt, hm0, hm1)] >= 0);
-                if (__ballot(t) != 0ull) { LEANC(3); return false; }
+                if (__ballot(t) != 0ull) { LEANC(13); settle(); }
             }
             // is a key of the hub's row in the partner's row?  Read now, looked at after the network
             const bool in1 = lane < n1;
@@ -204,7 +231,15 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             const double inf = __longlong_as_double(0x7ff0000000000000ll);
             double sw = pre_b.sw;
             int sid = pre_b.sid;
-            if (low) { cw = hw * pre_scale.scale_s1; sw = in1 ? cw : inf; sid = lane; }
+            double hw1 = hw * pre_scale.scale_s1;                // t_s1_PPR[key] = value * scale_s1
+            if (self) {                                          // ... += value * scale_s2: the row meets itself
+                // Two rounded products and one add: that rests on -ffp-contract=off, which zebra_amd/build.py sets for this
+                // file.  The empty asm only keeps the compiler from turning this uniform branch into selects on the vector
+                // unit, which would put both instructions into every hop.
+                asm volatile("" : "+v"(hw1));
+                hw1 = hw1 + hw * pre_scale.scale_s2;
+            }
+            if (low) { cw = hw1; sw = in1 ? cw : inf; sid = lane; }
             merge_stage<32>(sw, sid);
             merge_stage<16>(sw, sid);
             merge_stage<8>(sw, sid);
@@ -240,7 +275,20 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
                 // a picked member of the previous hop's straddling run that is kept here (or ties with the cut) needs the
                 // previous hop's replay first: the general code waits for it
                 const int thr = full ? drop : rsG;
-                if (__ballot(lane < munc && lt >= thr) != 0ull) { LEANC(5); return false; }
+                if (__ballot(lane < munc && lt >= thr) != 0ull) {
+                    LEANC(14);
+                    settle();
+                    // the key tests again, on the final keys
+                    bool bad2 = in1 && ckey == nkey && cts == tnow;
+                    const int cand2 = (table && in1) ? L.htab[key_hash_m(ckey, hm0, hm1)] : -1;
+                    if (__ballot(cand2 >= 0) != 0ull) {
+                        const int src = cand2 >= 0 ? cand2 : 0;
+                        const u64 kj = __shfl(rp.key, src);
+                        const double tj = __shfl(rp.ts, src);
+                        bad2 = bad2 || (in1 && cand2 >= 0 && kj == ckey && tj == cts);
+                    }
+                    if (__ballot(bad2) != 0ull) { LEANC(4); return false; }
+                }
             }
             // ---- provisional slots: the candidate at sorted position p >= drop takes slot p - drop ----
             const u64 nmask = ((u64)2 << (n - 1)) - 1ull;       // positions 0 .. n-1 (n <= 63)
@@ -270,6 +318,10 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             CRIT(3);
             HSTAMP(4);
             __builtin_amdgcn_s_setprio(0);                       // the rest of this hop is off the chain
+            if (self) LEANC(11);
+#ifdef ZT_CRIT
+            if (rec.prev_self) LEANN(12);
+#endif
             // ---- what the tail needs ----
             if (table && lane < lenp) L.htab[pre_b.h2] = -1;     // the table is clean again
             hub_unc = hunc; hub_munc = munc; hub_nalt = nalt;
@@ -292,6 +344,7 @@ __device__ __attribute__((always_inline)) inline bool chain_hop(const zt_tppr &h
             return true;
         }();
     }
+    if (self && !lean_done) return false;                        // (nothing written: process_edge starts from the mailbox again)
     if (!lean_done) {
     // ---- the hub's row: one batch of LDS reads ----
     mail_hdr_read(in_slot, rh.norm, rh.len, hub_unc, hub_munc, hub_nalt, hub_sorted);

@@ -448,9 +448,9 @@ __device__ __attribute__((always_inline)) inline void process_edge(const zt_tppr
         // one full pair update, rows in dictionary order; the hub's new row also goes to the mailbox (both stages)
         auto update = [&](const Row &a, const Row &b, long long xa, long long xb, int oa, int pre, int stamp) {
             const u64 nkey = ((u64)(unsigned)e << 32) | (u64)(unsigned)xb;
-            int n;
+            int n, mode = FR_NOPRUNE;
             if (reg_path) {
-                n = merge_pair_reg(L, lane, k, alpha, beta, a, b, nkey, tnow, c, pre, stamp);
+                n = merge_pair_reg(L, lane, k, alpha, beta, a, b, nkey, tnow, c, pre, stamp, &mode);
             } else {
                 n = merge_pair(L, lane, k, alpha, beta, a, b, nkey, tnow, c.key, c.ts, c.w, pre, stamp);
                 c.slot = lane < n ? lane : -1;
@@ -459,7 +459,12 @@ __device__ __attribute__((always_inline)) inline void process_edge(const zt_tppr
             if (mail != nullptr && xa == hub) {
                 if (hint != nullptr) { hint->norm_out = new_norm; hint->tpos = tpos; }
                 ring_free();
-                publish_set(c.slot, n, new_norm);
+                // A merge that pruned leaves the row in ascending order of weight: its dictionary order is the reference's argsort
+                // (:553-559; prepare_b relies on the same for rows from memory).  Saying so (sorted = 1; the set is final: no
+                // provisional slot, pos the identity) lets the NEXT position -- the one behind a self-loop, position 1 of every
+                // chain -- take chain_hop's lean section.  A row that was not pruned (never full) or holds a NaN is not sorted.
+                const int sorted = (mode == FR_RANKS || mode == FR_TIES || mode == FR_STRADDLE) ? 1 : 0;
+                publish_set(c.slot, n, new_norm, 0u, 0, 0, sorted);
                 if (c.slot >= 0) out_slot->pos[c.slot] = c.slot;
                 publish_seq(true, true);
                 HSTAMP(4);

@@ -802,13 +802,15 @@ __device__ inline int merge_order(WaveLds &L, int lane, int k, Front &F, int pos
     return slot;
 }
 
-// both halves (s1's row is in dictionary order: position = lane)
+// both halves (s1's row is in dictionary order: position = lane).  mode_out: the Front's mode (FR_*) -- a merge that
+// pruned without NaNs leaves the new row in ascending order of weight (the reference's dictionary order IS its argsort)
 __device__ inline int merge_pair_reg(WaveLds &L, int lane, int k, double alpha, double beta, const Row &r1,
                                      const Row &r2, u64 newkey, double newts, Cand &out, int pre = 0,
-                                     int g_stamp_i = -1)
+                                     int g_stamp_i = -1, int *mode_out = nullptr)
 {
     Front F;
     merge_front(L, lane, k, alpha, beta, r1, r2, newkey, newts, F, pre, g_stamp_i);
+    if (mode_out != nullptr) *mode_out = F.mode;
     int n_new;
     out.slot = merge_order(L, lane, k, F, lane, &n_new, g_stamp_i);
     out.key = F.key; out.ts = F.ts; out.w = F.w;

@@ -178,6 +178,9 @@ __global__ __launch_bounds__(ZT_STREAM_BOUNDS) void k_stream(zt_tppr h, StreamAr
             const int pe = t > 0 ? ZT_U(ch_edge[t - 1]) : -1, ne = t + 1 < len ? ZT_U(ch_edge[t + 1]) : -1, ce = ZT_U(ch_edge[t]);
             HopRec rec;
             rec.partner = ZT_U(ch_partner[t]); rec.wo_p = ZT_U(ch_wop[t]); rec.pchain = ZT_U(ch_pch[t]);
+#ifdef ZT_CRIT
+            rec.prev_self = t > 0 && ZT_U(ch_partner[t - 1]) < 0;
+#endif
 #undef ZT_U
             if (!chain_hop(h, A, L, lane, ce, mo, &mail, hub, pe, ne, t, &hint, c, rec))
                 process_edge(h, A, L, lane, ce, mo, &mail, hub, pe, ne, t, &hint, c);
