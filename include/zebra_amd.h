@@ -802,6 +802,46 @@ int zt_pipeline_last_scores(zt_pipeline *p, void *stream, float **prob_out, int6
 int zt_pipeline_set_metrics(zt_pipeline *p, double *sum_dev, double *per_batch_dev, int64_t cap);
 int zt_pipeline_metrics(zt_pipeline *p, void *stream, int64_t *n_out);
 
+/* The tail of a TRAINING step (csrc/train_tail.hip): the loss of train.py:212-213 and the optimizer step of train.py:215.
+ *
+ * Pair loss.  prob_dev [2B] holds B positive probabilities, then B negative ones (what zt_affinity_train_forward writes):
+ *   loss_dev[0] = mean_i -max(log p_i, -100) + mean_j -max(log(1 - n_j), -100)
+ * -- torch.nn.BCELoss with labels 1 and 0, added up -- and dprob_dev [2B] = (x - y) / max((1 - x) x, 1e-12) / B, the gradient
+ * at grad_output = 1.  One launch for any B >= 1; logarithms, quotients and sums in float64 with a fixed association, rounded
+ * to float32 once: two runs give the same bits, no atomics.  The backward is one launch, d_prob_dev = grad_loss_dev[0] *
+ * dprob_dev: the scalar is read on the device, nothing synchronises.  B < 1 or a NULL pointer: ZT_ERR_ARG before any device
+ * call. */
+int zt_link_bce_forward(const float *prob_dev, int64_t B, float *loss_dev, float *dprob_dev, void *stream);
+int zt_link_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int64_t B, float *d_prob_dev, void *stream);
+/* Adam for a whole list of float32 tensors in one launch per ZT_ADAM_MAX_TENSORS non-empty tensors: torch.optim.Adam's
+ * single-tensor update without weight decay, amsgrad or maximize, in torch's order,
+ *   m = m + (g - m) (1 - beta1);  v = v beta2 + (1 - beta2) g g;  p = p - step_size (m / (sqrt(v) / bias2_sqrt + eps))
+ * with the multiply-add of each statement fused (one rounding), as torch's device kernels compile.
+ * step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t) are the caller's, computed in double, per tensor: the
+ * tensors of a call may be at different steps.  1 - beta is formed in double from the shortest decimal that rounds to the
+ * float given (0.999f stands for 0.999), which is the factor torch, holding the betas as Python floats, multiplies by.
+ * The table is host memory and travels in the kernels' arguments: no copy, no synchronisation, nothing to keep alive after
+ * the call returns.  The device pointers need no alignment (16-byte accesses where all four of a tensor have it).
+ * n = 0: ZT_OK, no launch; an entry with numel = 0 is skipped.  ZT_ERR_ARG before any device call: n < 0, a NULL pointer in
+ * an entry, numel < 0 or numel >= 2^31. */
+typedef struct zt_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t numel;
+    float step_size;
+    float bias2_sqrt;
+} zt_adam_tensor;
+#define ZT_ADAM_CHUNK 4096      /* elements per workgroup */
+#define ZT_ADAM_MAX_TENSORS 64  /* non-empty tensors per launch */
+int zt_adam_step(const zt_adam_tensor *tensors_host, int32_t n, float beta1, float beta2, float eps, void *stream);
+/* The launches a zt_adam_step over tensors of these sizes makes (host code only, no GPU call; the step goes through the same
+ * walk): out[0] = launches, out[1 + i] = workgroups of launch i -- the sum of ceil(numel / ZT_ADAM_CHUNK) over its tensors,
+ * which are the next ZT_ADAM_MAX_TENSORS non-empty ones in the order given.  out holds 1 + ceil(n / ZT_ADAM_MAX_TENSORS)
+ * values at most.  ZT_ERR_ARG for n < 0, NULL out, or a size outside [0, 2^31). */
+int zt_adam_plan(const int64_t *numel_host, int32_t n, int64_t *out);
+
 /* ------------------------------------------------------------------------ */
 /* One-node multi-GPU exchange of touched rows.  The reference  */
 /* has no distributed code; this is the data-path step around the one RCCL     */

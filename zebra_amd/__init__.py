@@ -5,3 +5,14 @@ The compute lives in zebra_amd/lib/libzebra_amd.so (hand-written HIP, C-ABI in
 include/zebra_amd.h).  The Python classes mirror the reference's surface.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # (resolved on first use: `python -m zebra_amd.build` imports the package and needs no torch)
+    if name == "Adam":
+        from .optim import Adam
+        return Adam
+    if name == "link_bce_loss":
+        from .losses import link_bce_loss
+        return link_bce_loss
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -33,6 +33,7 @@ SYMBOLS = [
     "zt_rnn_update", "zt_rnn_train_forward", "zt_rnn_train_backward", "zt_pipeline_set_cell",
     "zt_affinity_train_workspace_bytes", "zt_affinity_train_forward", "zt_affinity_train_backward",
     "zt_link_metrics_plan", "zt_pipeline_set_metrics", "zt_pipeline_metrics",
+    "zt_link_bce_forward", "zt_link_bce_backward", "zt_adam_step", "zt_adam_plan",
 ]
 
 
@@ -51,6 +52,7 @@ CELL_GRU, CELL_RNN = 0, 1                                       # zt_pipeline_se
 METRICS_FORM_REFUSED, METRICS_FORM_SINGLE, METRICS_FORM_SPLIT = 0, 1, 2   # zt_link_metrics_plan
 METRICS_MAX_B = 16384
 MSG_ONE, MSG_TWO = 1, 2
+ADAM_CHUNK, ADAM_MAX_TENSORS = 4096, 64                         # zt_adam_plan / zt_adam_step
 
 
 def set_kernel_choice(which, value):
@@ -109,6 +111,11 @@ class ExchangeDesc(C.Structure):
                 ("unique_id", C.c_void_p), ("shm_name", C.c_char_p), ("cap_rows", C.c_int64),
                 ("memory", C.c_void_p), ("last_update", C.c_void_p), ("messages", C.c_void_p), ("msg_ts", C.c_void_p),
                 ("D", C.c_int32), ("msg_dim", C.c_int32)]
+
+
+class AdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("step_size", C.c_float), ("bias2_sqrt", C.c_float)]
 
 
 class Batch(C.Structure):
@@ -176,6 +183,15 @@ def link_metrics_plan(B):
     out = (C.c_int64 * 4)()
     check(lib().zt_link_metrics_plan(C.c_int64(B), out), "zt_link_metrics_plan")
     return dict(form=int(out[0]), threads=int(out[1]), n2=int(out[2]), lds_bytes=int(out[3]))
+
+
+def adam_plan(numel):
+    """zt_adam_plan: the grids of the launches one zt_adam_step makes for tensors of these sizes (host code only)."""
+    n = len(numel)
+    sizes = (C.c_int64 * max(n, 1))(*[int(x) for x in numel])
+    out = (C.c_int64 * (2 + n // ADAM_MAX_TENSORS))()
+    check(lib().zt_adam_plan(sizes, C.c_int32(n), out), "zt_adam_plan")
+    return [int(out[1 + i]) for i in range(int(out[0]))]
 
 
 def ptr(t):

@@ -33,6 +33,7 @@ SOURCES = {
     "attention.hip": [],
     "scoring.hip": [],
     "scoring_train.hip": [],
+    "train_tail.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],
 }

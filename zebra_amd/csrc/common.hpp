@@ -18,7 +18,7 @@ void set_error(const char *fmt, ...);
 // an event pair is recorded on the launch stream around the kernel; elapsed
 // times are summed per kernel name when the profile is read.
 enum ProfId { P_PREPASS = 0, P_STREAM, P_CLEANUP, P_PRUNE, P_EMBED_PREP, P_FC1_AGG, P_EMBED_OUT, P_STORE_MSG, P_GRU,
-              P_SCORE, P_EXCHANGE, P_COUNT };
+              P_SCORE, P_EXCHANGE, P_LINK_BCE, P_ADAM, P_COUNT };
 extern bool g_prof_on;
 void prof_begin(hipStream_t s, int id);
 void prof_end(hipStream_t s, int id);

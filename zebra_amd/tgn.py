@@ -15,6 +15,7 @@ import torch
 
 from . import _capi
 from ._capi import check, lib, ptr, stream_ptr
+from .losses import _HipLinkBCE, link_bce_loss
 from .modules import Memory, MergeLayer, TimeEncode, _HipLinkScore, get_embedding_module, get_memory_updater
 
 
@@ -694,6 +695,27 @@ class TGN(torch.nn.Module):
                 full = torch.cat([s, dd, n])
             return self.score_train(full)
         return self._score_pairs(s, dd, n)
+
+    def compute_edge_loss(self, source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs, n_neighbors):
+        """(loss, pos_prob, neg_prob) of a training batch: train.py:212-213 in one call -- compute_edge_probabilities(train=True)
+        and BCELoss of the positive pairs against ones plus BCELoss of the negative pairs against zeros.  Where link_score_plan
+        says "hip" the [2B] vector of _HipLinkScore goes straight into _HipLinkBCE (csrc/train_tail.hip): no slice, squeeze or
+        cat node enters the graph; otherwise the probabilities' composition with losses.link_bce_loss.  pos_prob and neg_prob
+        are detached [B, 1] views for the caller's metrics."""
+        n_samples = len(source_nodes)
+        s, dd, n = self.compute_temporal_embeddings(source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs,
+                                                    n_neighbors, True)
+        if n_samples and link_score_plan(s.device.type, s.dtype, s.shape[1], getattr(self, "fused_scoring", True)) == "hip":
+            full = getattr(self, "_last_node_block", None)               # (as compute_edge_probabilities)
+            if full is None or full.data_ptr() != s.data_ptr() or full.shape[0] != 3 * n_samples or not full.is_contiguous():
+                full = torch.cat([s, dd, n])
+            a = self.affinity_score
+            prob = _HipLinkScore.apply(full, a.fc1.weight, a.fc1.bias, a.fc2.weight, a.fc2.bias)
+            loss = _HipLinkBCE.apply(prob)
+            prob = prob.detach()
+            return loss, prob[:n_samples].unsqueeze(1), prob[n_samples:].unsqueeze(1)
+        pos, neg = self._score_pairs(s, dd, n)
+        return link_bce_loss(pos, neg), pos.detach(), neg.detach()
 
     def update_memory(self, memory, positives):
         with torch.no_grad():
