@@ -68,6 +68,9 @@ STREAM_CASES = {
     "gen_k40": ("general", 200, 2000, 13, 200, 40, [0.0, 0.3], [0.9, 0.7], False),
     "bs1_single": ("general", 50, 300, 14, 1, 5, [0.1], [0.9], True),
     "hub_ties": ("hub", 120, 1500, 15, 50, 20, [0.1], [0.5], False),
+    # three and four models: betas 0.5 and 0.25 scale exactly (ties decide the top k), one alpha is 0
+    "hub_m4": ("hub", 120, 1500, 16, 50, 20, [0.1, 0.1, 0.2, 0.0], [0.5, 0.95, 0.25, 0.8], False),
+    "gen_m3": ("general", 50, 600, 17, 7, 5, [0.1, 0.2, 0.1], [0.5, 0.8, 0.95], True),
 }
 
 # name -> (stream kind, n_nodes, n_edges, seed, n_queries, width, depth, k, alpha, beta)
@@ -147,6 +150,14 @@ EMBED_CASES = {
     "d100_f172": (120, 400, 100, 172, 100, 20, [0.1, 0.1], [0.5, 0.95], 31, 20, 4),
     "d100_f1": (120, 400, 100, 1, 100, 20, [0.1, 0.1], [0.5, 0.95], 32, 20, 4),
     "d20_f7": (60, 300, 20, 7, 20, 5, [0.2], [0.8], 33, 16, 4),
+    "d100_f4_m3": (120, 400, 100, 4, 100, 20, [0.1, 0.1, 0.2], [0.5, 0.95, 0.8], 34, 20, 4),
+    "d20_f7_m4": (60, 300, 20, 7, 20, 5, [0.2, 0.1, 0.1, 0.0], [0.8, 0.5, 0.95, 0.25], 35, 16, 4),
+}
+
+# embedding case -> training-gradient fixture (the reference's own loss and every parameter gradient)
+TRAIN_GRAD_CASES = {
+    "d20_f7": "g8_train_grads",
+    "d20_f7_m4": "g8_train_grads_m4",
 }
 
 

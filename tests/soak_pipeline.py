@@ -2,7 +2,7 @@
 CU-masked streams, the message build beside the aggregation, the projected table, the GRU) against the CPU oracle's
 protocol -- test infrastructure, run on a GPU box:   python tests/soak_pipeline.py [seconds] [first seed]
 Random node counts, batch sizes (a ragged last batch now and then), k, widths (the reference's 100/100 and others: every
-aggregation kernel), feature widths, one or two models, launch groups 1..4, CU masks, views ahead of different lengths,
+aggregation kernel), feature widths, one or two models (three or four now and then from seed 100000 on), launch groups 1..4, CU masks, views ahead of different lengths,
 shuffled node ids.  Per batch: embeddings <= 1e-4; at the end: T-PPR state bit-exact, memory / messages <= 1e-4,
 last_update / flags exact."""
 import os
@@ -21,6 +21,7 @@ TOL = 1e-4
 def one(seed, torch, pyoracle):
     import inputs as I
     from helpers import build_tgn
+    from soak_tppr import many_models
     from zebra_amd import synth
     rng = np.random.RandomState(seed)
     N = int(rng.choice([60, 2000, 100000]))
@@ -32,6 +33,9 @@ def one(seed, torch, pyoracle):
     M = int(rng.choice([1, 2, 2]))
     al = [float(rng.choice([0.1, 0.2])) for _ in range(M)]
     be = [float(rng.choice([0.5, 0.8, 0.95])) for _ in range(M)]
+    many = many_models(seed, [0.1, 0.2], [0.5, 0.8, 0.95])       # (seeds from soak_tppr.MANY_MODELS_SEED on: three or four models)
+    if many is not None:
+        M, al, be = many
     group = int(rng.choice([1, 2, 3, 4]))
     cus = int(rng.choice([0, 32, 64, 96]))
     look = int(rng.randint(0, 3 * group + 2))

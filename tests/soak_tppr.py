@@ -2,7 +2,8 @@
 pytest: run on a GPU box with   python tests/soak_tppr.py [seconds] [first seed]).
 Every configuration draws its own graph shape (hub-dominated, dense, bipartite-like, power law), k, batch size (up to
 launches that exercise several chains per model), alpha / beta (0.5 and 0.25 scale exactly: ties), self-loops, negatives
-equal to endpoints or hubs, repeated timestamps; every batch's four output arrays and the final state must be bit-identical."""
+equal to endpoints or hubs, repeated timestamps; every batch's four output arrays and the final state must be bit-identical.
+One or two models; seeds from MANY_MODELS_SEED on: three or four in about half of the configurations."""
 import os
 import sys
 import time
@@ -14,6 +15,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 
+MANY_MODELS_SEED = 100000      # seeds from here on draw three or four models now and then; every seed below keeps its configuration
+
+
+def many_models(seed, alphas, betas):
+    """(M, alpha, beta) with M in {3, 4} for about half of the seeds at or above MANY_MODELS_SEED, else None.  Drawn from a
+    generator of its own, so that nothing else of a seed's configuration moves (soak_pipeline.py and soak_train.py use it too)."""
+    if seed < MANY_MODELS_SEED:
+        return None
+    rng2 = np.random.RandomState(seed + 4242)
+    if rng2.random_sample() >= 0.5:
+        return None
+    M = int(rng2.choice([3, 4]))
+    return M, [float(rng2.choice(alphas)) for _ in range(M)], [float(rng2.choice(betas)) for _ in range(M)]
+
+
 def one(seed, tppr, pyoracle):
     rng = np.random.RandomState(seed)
     N = int(rng.choice([12, 41, 300, 5000, 100000]))
@@ -23,6 +39,9 @@ def one(seed, tppr, pyoracle):
     M = int(rng.choice([1, 2, 2]))
     al = [float(rng.choice([0.0, 0.1, 0.2])) for _ in range(M)]
     be = [float(rng.choice([0.5, 0.5, 0.25, 0.8, 0.95])) for _ in range(M)]
+    many = many_models(seed, [0.0, 0.1, 0.2], [0.5, 0.5, 0.25, 0.8, 0.95])
+    if many is not None:
+        M, al, be = many
     expo = float(rng.choice([0.0, 0.7, 1.0, 1.3]))
     E = bs * nb
     p = 1.0 / np.arange(1, N) ** expo

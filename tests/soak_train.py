@@ -4,7 +4,8 @@ g8_train_grads pins to the reference's gradients -- on random shapes.  Test infr
     python tests/soak_train.py [seconds] [first seed]
 The cotangent of the embeddings is a fixed random matrix (a linear loss: nothing downstream amplifies rounding); embeddings
 to 1e-5, every parameter gradient to 1e-4 of its scale in all but 1 % of the elements and to 2e-3 in norm (a ReLU whose
-pre-activation is within rounding of zero may flip)."""
+pre-activation is within rounding of zero may flip).  One or two models; three or four now and then from seed 100000 on
+(soak_tppr.many_models)."""
 import os
 import sys
 import time
@@ -20,6 +21,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.pa
 def one(seed, torch):
     import inputs as I
     from helpers import build_tgn
+    from soak_tppr import many_models
     rng = np.random.RandomState(seed)
     D, T = [(100, 100), (100, 100), (32, 16), (64, 100)][rng.randint(4)]
     F = int(rng.choice([1, 4, 16, 172]))
@@ -31,6 +33,9 @@ def one(seed, torch):
     kind = ["bipartite", "general", "hub"][rng.randint(3)]
     al = [float(rng.choice([0.1, 0.2])) for _ in range(M)]
     be = [float(rng.choice([0.5, 0.8, 0.95])) for _ in range(M)]
+    many = many_models(seed, [0.1, 0.2], [0.5, 0.8, 0.95])       # (seeds from soak_tppr.MANY_MODELS_SEED on: three or four models)
+    if many is not None:
+        M, al, be = many
     E = bs * nb
     tag = "seed %d: N=%d bs=%d nb=%d k=%d D=%d T=%d F=%d M=%d %s" % (seed, N, bs, nb, k, D, T, F, M, kind)
     if os.environ.get("ZT_SOAK_VERBOSE"):

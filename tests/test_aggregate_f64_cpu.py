@@ -12,6 +12,7 @@ import torch
 
 from conftest import ROOT
 import test_aggregate_f64_gpu as G
+import test_many_models_gpu as MM
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import aggregate_f64
@@ -75,10 +76,14 @@ def test_generator_covers_what_it_says():
 def test_undecided_units_stay_under_their_cap(D, F, T, k, p):
     """Every training case of the GPU file: the units within TAU of zero are at most 1e-4 of the live ones, and no row of
     a gradient has more of them than the GPU test tries in and out (so no element is left to the allowance alone)."""
-    x, ref = G.train_reference(D, F, T, k, p)
-    assert ref["n_live"] > 0.3 * G.M * G.TRAIN_N * k * D * (1 - p)
-    print("D=%d F=%d T=%d k=%d p=%g: %d of %d live units undecided (%.2e)"
-          % (D, F, T, k, p, ref["n_undecided"], ref["n_live"], ref["n_undecided"] / ref["n_live"]))
+    _undecided_under_cap(D, F, T, k, p, G.M)
+
+
+def _undecided_under_cap(D, F, T, k, p, M):
+    x, ref = G.train_reference(D, F, T, k, p, M=M)
+    assert ref["n_live"] > 0.3 * M * G.TRAIN_N * k * D * (1 - p)
+    print("M=%d D=%d F=%d T=%d k=%d p=%g: %d of %d live units undecided (%.2e)"
+          % (M, D, F, T, k, p, ref["n_undecided"], ref["n_live"], ref["n_undecided"] / ref["n_live"]))
     assert ref["n_undecided"] <= G.UNDECIDED_CAP * ref["n_live"]
     for name, an in (("d_overlay", "allow_overlay"), ("dW1", "allow_W1"), ("db1", "allow_b1")):
         groups = G.flip_groups(ref, name)
@@ -90,6 +95,12 @@ def test_undecided_units_stay_under_their_cap(D, F, T, k, p):
             else sum(len(t) for t in groups.values()) == ref["n_undecided"]
     for kk in ("H", "z", "dW1", "db1", "d_overlay"):
         assert ref[kk].dtype == np.float64 and np.isfinite(ref[kk]).all()
+
+
+@pytest.mark.parametrize("M,D,F,T,k,p", MM.TRAIN_MANY, ids=["M%d-%d-%d-%d-%d-p%g" % c for c in MM.TRAIN_MANY])
+def test_undecided_units_stay_under_their_cap_many_models(M, D, F, T, k, p):
+    """The same for the three- and four-model training cases of tests/test_many_models_gpu.py."""
+    _undecided_under_cap(D, F, T, k, p, M)
 
 
 def _broken(x, mask):

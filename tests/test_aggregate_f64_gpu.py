@@ -91,11 +91,13 @@ def _oracle():
     return aggregate_f64
 
 
-def make_inputs(D, F, T, k, n, overlay=False):
+def make_inputs(D, F, T, k, n, overlay=False, M=M):
     """The one seeded generator of this file and of test_aggregate_f64_cpu.py (CPU tensors).  The special rows sit at
     fixed positions from row 0 on, so the first rows of a draw are a smaller case of the same kind: the eval cases draw
-    257 rows once and run their first 1, 37 and 257."""
-    g = torch.Generator().manual_seed(7000 + 131 * D + 17 * F + 5 * T + k + (1 if overlay else 0))
+    257 rows once and run their first 1, 37 and 257.  M models (tests/test_many_models_gpu.py runs 3, 4 and 16): the
+    model count enters the seed only where it is not 2, so the cases of this file draw what they always drew."""
+    g = torch.Generator().manual_seed(7000 + 131 * D + 17 * F + 5 * T + k + (1 if overlay else 0)
+                                      + (100003 * M if M != 2 else 0))
     x = {"w": I.model_weights(D, F, T, M, 61), "tw": I.time_encode_weights(T)}
     x["memory"] = torch.randn((NN, D), generator=g)
     x["efeat"] = torch.randn((E1, F), generator=g)                      # non-zero at every F, row 0 included
@@ -122,7 +124,7 @@ def make_inputs(D, F, T, k, n, overlay=False):
     return x
 
 
-def train_mask(D, k, p):
+def train_mask(D, k, p, M=M):
     """The kernels' keep-mask for a training case (its definition: zebra_amd.modules.dropout_mask), or None."""
     if p == 0:
         return None
@@ -130,17 +132,17 @@ def train_mask(D, k, p):
     return dropout_mask(DROP_SEED, p, (M, TRAIN_N, k), D)
 
 
-def train_reference(D, F, T, k, p, overlay=True):
-    x = make_inputs(D, F, T, k, TRAIN_N, overlay=overlay)
+def train_reference(D, F, T, k, p, overlay=True, M=M):
+    x = make_inputs(D, F, T, k, TRAIN_N, overlay=overlay, M=M)
     ref = _oracle().aggregate_f64(x["w"]["fc1_w"], x["w"]["fc1_b"], x["memory"], x["efeat"], x["tw"], x["on"], x["oe"],
                                   x["od"], x["ow"], x["G"], overlay=x.get("overlay"), row_map=x.get("row_map"),
-                                  mask=train_mask(D, k, p), tau=TAU)
+                                  mask=train_mask(D, k, p, M), tau=TAU)
     return x, ref
 
 
 @functools.lru_cache(maxsize=None)
-def _eval_reference(D, F, T, k):
-    x = make_inputs(D, F, T, k, max(EVAL_N))
+def _eval_reference(D, F, T, k, M=M):
+    x = make_inputs(D, F, T, k, max(EVAL_N), M=M)
     nodes = torch.randint(0, NN, (max(EVAL_N),), generator=torch.Generator().manual_seed(D + F + k), dtype=torch.int32)
     nodes[1] = 0
     out, H, S = _oracle().embed_f64(x["w"], x["memory"].numpy(), x["efeat"].numpy(), x["tw"], nodes.numpy(),
@@ -148,9 +150,10 @@ def _eval_reference(D, F, T, k):
     return x, nodes, out, S
 
 
-def _tgn(x, D, F, T, k):
+def _tgn(x, D, F, T, k, M=M):
     from helpers import build_tgn
-    tgn = build_tgn(NN, E1, D, F, T, k, [0.1, 0.1], [0.5, 0.95], x["w"], x["efeat"].numpy())
+    al, be = ([0.1, 0.1, 0.2, 0.0] * 4)[:M], ([0.5, 0.95, 0.8, 0.25] * 4)[:M]     # (the aggregation reads neither)
+    tgn = build_tgn(NN, E1, D, F, T, k, al, be, x["w"], x["efeat"].numpy())
     tgn.memory.memory.copy_(x["memory"].to(tgn.device))
     return tgn
 
@@ -173,11 +176,11 @@ def _torch_embed(em, memory, nodes, on, oe, od, ow):
         return torch.cat(outs, dim=1)
 
 
-def _check_eval(form, D, F, T, k, table, out_choice=0, Ns=EVAL_N):
+def _check_eval(form, D, F, T, k, table, out_choice=0, Ns=EVAL_N, M=M):
     from zebra_amd import _capi
-    x, nodes, want, S = _eval_reference(D, F, T, k)
+    x, nodes, want, S = _eval_reference(D, F, T, k, M)
     hooks = _capi.hooks_lib()
-    tgn = _tgn(x, D, F, T, k).eval()
+    tgn = _tgn(x, D, F, T, k, M).eval()
     em, dev = tgn.embedding_module, tgn.device
     tol = 2e-5 * max(1.0, np.abs(want).max())
     assert (S == 0).any() and (S == 1).any()
@@ -193,8 +196,8 @@ def _check_eval(form, D, F, T, k, table, out_choice=0, Ns=EVAL_N):
         d_hip = np.abs(got.cpu().numpy().astype(np.float64) - want[:n])
         d_torch = np.abs(ref32.cpu().numpy().astype(np.float64) - want[:n])
         e_hip, e_torch = float(d_hip.max()), float(d_torch.max())
-        print("eval %-15s D=%d F=%d T=%d k=%d table=%d out=%d/%d N=%d: models' columns hip %.2e torch %.2e, source columns "
-              "hip %.2e torch %.2e (tol %.2e)" % (form, D, F, T, k, table, out_choice, o, n, d_hip[:, D:].max(),
+        print("eval %-15s M=%d D=%d F=%d T=%d k=%d table=%d out=%d/%d N=%d: models' columns hip %.2e torch %.2e, source columns "
+              "hip %.2e torch %.2e (tol %.2e)" % (form, M, D, F, T, k, table, out_choice, o, n, d_hip[:, D:].max(),
                                                   d_torch[:, D:].max(), d_hip[:, :D].max(), d_torch[:, :D].max(), tol))
         assert got.shape == (n, D * (M + 1))
         assert e_torch <= 0.5 * tol, "torch float32 itself is %.3g from float64 at N = %d" % (e_torch, n)
@@ -271,13 +274,13 @@ def allowance_only_share(ref, name):
     return sum(1 for t in flip_groups(ref, name).values() if len(t) > MAX_FLIPS) / n
 
 
-def _check_train(D, F, T, k, p, overlay=True):
+def _check_train(D, F, T, k, p, overlay=True, M=M):
     from zebra_amd import _capi
     from zebra_amd.modules import _NeighbourAggregate
-    x, ref = train_reference(D, F, T, k, p, overlay)
+    x, ref = train_reference(D, F, T, k, p, overlay, M)
     form = LP.plan(_capi.hooks_lib(), TRAIN_N, D, F, T, M, k, False, training=True)[0]
     assert form == LP.AGG["tiled_full" if k <= 80 else "split"]      # one tile up to k = 80, the row split beyond
-    tgn = _tgn(x, D, F, T, k)
+    tgn = _tgn(x, D, F, T, k, M)
     em, dev = tgn.embedding_module, tgn.device
     mem = tgn.memory.memory.detach()
     on, oe, od, ow, G = [x[kk].to(dev) for kk in ("on", "oe", "od", "ow", "G")]
@@ -315,7 +318,7 @@ def _check_train(D, F, T, k, p, overlay=True):
         xx = torch.cat([rows, em.edge_features[oe.long()], torch.cos(od.unsqueeze(-1) * tw)], dim=-1)
         h = torch.relu(torch.nn.functional.linear(xx, fc1_w, fc1_b))
         if p > 0:
-            h = h * torch.from_numpy(train_mask(D, k, p)).to(dev)
+            h = h * torch.from_numpy(train_mask(D, k, p, M)).to(dev)
         wn, nz = _wn(ow)
         H = (h * wn.unsqueeze(-1)).sum(dim=2)
         (H * G).sum().backward()
@@ -323,7 +326,7 @@ def _check_train(D, F, T, k, p, overlay=True):
 
     Hf, Sf, gf = fused()
     Hc, Sc, gc = composed()
-    what = "D=%d F=%d T=%d k=%d p=%g%s" % (D, F, T, k, p, "" if overlay else " no overlay")
+    what = "%sD=%d F=%d T=%d k=%d p=%g%s" % ("" if M == 2 else "M=%d " % M, D, F, T, k, p, "" if overlay else " no overlay")
     share = ref["n_undecided"] / ref["n_live"]
     print("train %s: undecided %d of %d live units (%.2e)" % (what, ref["n_undecided"], ref["n_live"], share))
     assert share <= UNDECIDED_CAP

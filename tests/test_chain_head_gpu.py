@@ -68,11 +68,13 @@ def star_launch(rng, B, hubs, first_eidx, t0, loops=(), joins=0, hub_negs=0):
     return src, dst, neg, ts, eidx
 
 
-def run_case(zt, oracle, k, seed, launches):
-    """launches: list of dicts for star_launch (B, hubs, ..).  A fresh finder; every launch compared."""
+def run_case(zt, oracle, k, seed, launches, al=None, be=None):
+    """launches: list of dicts for star_launch (B, hubs, ..).  A fresh finder; every launch compared.  al, be: the models'
+    alpha / beta lists (AL, BE where not given)."""
+    al, be = AL if al is None else al, BE if be is None else be
     rng = np.random.default_rng(seed)
-    f = zt.tppr_finder(N, k, len(AL), AL, BE)
-    o = oracle.TpprOracle(N, k, len(AL), AL, BE)
+    f = zt.tppr_finder(N, k, len(al), al, be)
+    o = oracle.TpprOracle(N, k, len(al), al, be)
     e0, t0 = 1, 0.0
     for n, spec in enumerate(launches):
         src, dst, neg, ts, eidx = star_launch(rng, first_eidx=e0, t0=t0, **spec)
@@ -85,7 +87,7 @@ def run_case(zt, oracle, k, seed, launches):
         for x, y, nm in zip(a, b, ("nodes", "eidx", "dt", "w")):
             assert np.array_equal(np.stack(x), np.stack(y)), "emitted %s differs: %s" % (nm, what)
         ids = np.unique(nodes).astype(np.int64)
-        for m in range(len(AL)):
+        for m in range(len(al)):
             sa, sb = f.export_rows(m, ids), o.export_rows(m, ids)
             for kk in ("len", "norm", "eidx", "node", "ts", "w"):
                 assert np.array_equal(sa[kk], sb[kk]), "state %s of model %d differs: %s" % (kk, m, what)

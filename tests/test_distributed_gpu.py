@@ -114,6 +114,9 @@ CFGS = {
     "pruning_native": (900, 2890, 100, 1, 100, 40, [0.1, 0.1], [0.5, 0.95], 306, 250, "pruning", 1, "msg"),
     # ... and the payload of a real run: [id | memory row | last_update] only
     "streaming_native_nomsg": (600, 2400, 100, 172, 100, 20, [0.1, 0.1], [0.5, 0.95], 307, 200, "streaming", 2, "nomsg"),
+    # three models through the pipeline (the shard's rows of every model brought together: a 2-D copy M rows high); run from
+    # tests/test_many_models_gpu.py
+    "streaming_pipe_m3": (600, 1200, 100, 4, 100, 20, [0.1, 0.1, 0.2], [0.5, 0.95, 0.25], 308, 200, "streaming", 2),
 }
 
 

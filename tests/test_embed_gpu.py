@@ -185,12 +185,13 @@ def test_pipelined_step_matches_sequential(tppr_cus, strategy):
 
 
 @pytest.mark.parametrize("F,bs", [(1, 400), (172, 400), (1, 150)])
-def test_fused_output_and_gru_launch_matches_separate_kernels(F, bs):
+def test_fused_output_and_gru_launch_matches_separate_kernels(F, bs, al=(0.1, 0.1), be=(0.5, 0.95)):
     """k_out_gru / k_out_gru2 (the output layers beside the GRU update in ONE launch, csrc/memory_update.hip): a pipelined
     step against the sequential path -- which launches k_embed_out / k_embed_out2 and k_gru / k_gru_split one after the
     other -- bit for bit: embeddings of every batch, the memory table, last_update.  bs = 400: 1 200 rows, the tiled output
-    kernel + k_gru<1> (partial-sum groups with F = 172: k_out_gru<5>); bs = 150: 450 rows, the latency-organised forms."""
-    N, D, T, k, al, be, seed = 3000, 100, 100, 20, [0.1, 0.1], [0.5, 0.95], 91
+    kernel + k_gru<1> (partial-sum groups with F = 172: k_out_gru<5>); bs = 150: 450 rows, the latency-organised forms.
+    al, be: the models (tests/test_many_models_gpu.py runs four)."""
+    N, D, T, k, al, be, seed = 3000, 100, 100, 20, list(al), list(be), 91
     nbt = 5
     E = nbt * bs
     src, dst, neg, ts, eidx = I.make_stream("general", N, E, seed)

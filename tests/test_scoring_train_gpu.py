@@ -16,7 +16,8 @@ from helpers import build_tgn, load_weights, make_args
 pytestmark = pytest.mark.gpu
 
 # hidden width H = D (n_tppr + 1) -> (D, n_tppr)
-WIDTHS = {40: (20, 1), 60: (20, 2), 200: (100, 1), 300: (100, 2), 344: (172, 1), 516: (172, 2), 768: (256, 2)}
+WIDTHS = {40: (20, 1), 60: (20, 2), 200: (100, 1), 300: (100, 2), 344: (172, 1), 516: (172, 2), 768: (256, 2),
+          400: (100, 3)}                                   # (three models: run from tests/test_many_models_gpu.py)
 # every H with a ragged B and with B = 4096; the other batch sizes of the issue's list spread over the widths
 SHAPES = [(1, 40), (17, 40), (4096, 40), (15, 60), (17, 60), (4096, 60), (16, 200), (17, 200), (4096, 200),
           (17, 300), (200, 300), (600, 300), (4096, 300), (17, 344), (600, 344), (4096, 344),
