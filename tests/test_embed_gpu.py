@@ -184,14 +184,17 @@ def test_pipelined_step_matches_sequential(tppr_cus, strategy):
             assert np.array_equal(outs["seq"][2][kk], outs[mode][2][kk])
 
 
-@pytest.mark.parametrize("F,bs", [(1, 400), (172, 400), (1, 150)])
-def test_fused_output_and_gru_launch_matches_separate_kernels(F, bs, al=(0.1, 0.1), be=(0.5, 0.95)):
+@pytest.mark.parametrize("F,bs,D", [(1, 400, 100), (172, 400, 100), (1, 150, 100), (16, 150, 128), (16, 400, 128)],
+                         ids=["1-400", "172-400", "1-150", "16-150-d128", "16-400-d128"])
+def test_fused_output_and_gru_launch_matches_separate_kernels(F, bs, D, al=(0.1, 0.1), be=(0.5, 0.95)):
     """k_out_gru / k_out_gru2 (the output layers beside the GRU update in ONE launch, csrc/memory_update.hip): a pipelined
     step against the sequential path -- which launches k_embed_out / k_embed_out2 and k_gru / k_gru_split one after the
     other -- bit for bit: embeddings of every batch, the memory table, last_update.  bs = 400: 1 200 rows, the tiled output
     kernel + k_gru<1> (partial-sum groups with F = 172: k_out_gru<5>); bs = 150: 450 rows, the latency-organised forms.
-    al, be: the models (tests/test_many_models_gpu.py runs four)."""
-    N, D, T, k, al, be, seed = 3000, 100, 100, 20, list(al), list(be), 91
+    al, be: the models (tests/test_many_models_gpu.py runs four).  D = 128 (Hp = 128, eight N-tiles, no padded column):
+    bs = 400 is k_out_gru again; at bs = 150 the split does not take Hp = 128, so the latency-organised output layers run
+    in front of k_gru -- what each shape reaches is pinned in tests/test_memory_f64_cpu.py (test_one_launch_forms_at_d128)."""
+    N, T, k, al, be, seed = 3000, 100, 20, list(al), list(be), 91
     nbt = 5
     E = nbt * bs
     src, dst, neg, ts, eidx = I.make_stream("general", N, E, seed)

@@ -410,7 +410,7 @@ def test_fused_output_and_gru_launch_four_models(bs):
     """test_fused_output_and_gru_launch_matches_separate_kernels with four models: the grid of k_out_gru counts out_tiles (M + 1)
     workgroups in front of the GRU's, k_out_gru2 per_path M neighbour-path units."""
     import test_embed_gpu as TE
-    TE.test_fused_output_and_gru_launch_matches_separate_kernels(1, bs, al=AL4, be=BE4)
+    TE.test_fused_output_and_gru_launch_matches_separate_kernels(1, bs, 100, al=AL4, be=BE4)
 
 
 @pytest.mark.parametrize("M", [3, 4])
