@@ -82,24 +82,46 @@ def test_removed_tppr_alternatives_are_refused(capi):
         assert lib.zt_set_kernel_choice(C.c_int32(capi.CHOICE_TPPR_PREPASS), C.c_int32(0)) == capi.ZT_OK
 
 
+def _code_object_notes(capi, tmp_path, name):
+    """The gfx950 code object's metadata notes of the built object lib/<name>.o, as text: the object's fat binary, its gfx950
+    member, that member's notes.  Skips where the object or the LLVM tools are missing."""
+    import subprocess
+    obj = os.path.join(os.path.dirname(capi.LIB_PATH), name + ".o")
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
+        pytest.skip("no built object / no LLVM tools here (the GPU box runs the prebuilt library)")
+    fat, co = str(tmp_path / (name + ".fat.bin")), str(tmp_path / (name + ".co"))
+    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, obj, str(tmp_path / "unused.o")], check=True)
+    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o",
+                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co], check=True)
+    return subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+
+
 def test_k_stream_register_count_leaves_room_for_the_message_kernels(capi, tmp_path):
     """k_stream's workgroups sit two waves to a SIMD on the T-PPR stream's compute units and the message kernels of the
     step (k_last_pos, k_build_messages2: <= 64 registers) run BESIDE them: that needs 2 x (k_stream's registers, in
     granules of 8) + 64 <= 512, i.e. k_stream <= 224 vector registers.  At 225 (round 6, a replay-server experiment) the message
     kernels waited for every k_stream to end and the step DOUBLED; at 256 (round 5, the paired hop inlined) likewise.  The
     count is read from the built object's code-object metadata (no GPU needed)."""
-    import re
-    import subprocess
-    obj = os.path.join(os.path.dirname(capi.LIB_PATH), "tppr_stream.o")
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
-        pytest.skip("no built object / no LLVM tools here (the GPU box runs the prebuilt library)")
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "ts.co")
-    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, obj, str(tmp_path / "unused.o")], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co], check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    notes = _code_object_notes(capi, tmp_path, "tppr_stream")
     m = re.search(r"\.name:\s+\S*8k_streamE\S*.*?\.vgpr_count:\s+(\d+)", notes, re.S)
     assert m, "k_stream not found in the code object's metadata"
     vgprs = int(m.group(1))
     assert vgprs <= 224, "k_stream needs %d vector registers: the message kernels no longer fit beside it" % vgprs
+
+
+def test_fc1_agg_kernels_use_no_scratch(capi, tmp_path):
+    """Every instantiation of the neighbour aggregation's kernels (k_fc1_agg*: tiled, row-split, backward, and the specialised
+    ones beside them) keeps its accumulators in registers: a private segment of 0 bytes.  The backward sits at the 256-register
+    limit with the shared fc1 product's look-ahead inside; one more live value there would go to scratch memory, in the
+    innermost loop.  Read from the built objects' code-object metadata (no GPU needed)."""
+    seen = {}
+    for name in ("aggregate", "aggregate_split", "aggregate_bwd"):
+        notes = _code_object_notes(capi, tmp_path, name)
+        kernels = re.findall(r"\.name:\s+(\S*k_fc1_agg\S*)\s.*?\.private_segment_fixed_size:\s+(\d+)", notes, re.S)
+        assert kernels, "no k_fc1_agg kernel in %s.o's metadata" % name
+        seen.update({k: int(v) for k, v in kernels})
+    for stem in ("9k_fc1_aggI", "15k_fc1_agg_splitI", "13k_fc1_agg_bwdI"):        # the three general kernels were among them
+        assert any(stem in k for k in seen), (stem, sorted(seen))
+    spilled = {k: v for k, v in seen.items() if v != 0}
+    assert not spilled, "scratch bytes per lane: %r" % spilled

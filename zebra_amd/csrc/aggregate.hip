@@ -19,18 +19,17 @@
 //               (three D x D layers, also f32 MFMA) and the concat into out[N, D*(M+1)].
 // Arithmetic is float32 throughout (parity tolerance for embeddings: 1e-4).
 #include "common.hpp"
-#include "embed_out_body.hpp"     // f32x4, AGG_THREADS / AGG_WAVES / NTW, small_gemm, the output layers' body (shared with memory_update.hip)
+#include "embed_out_body.hpp"     // small_gemm, the output layers' body (shared with memory_update.hip)
+#include "fc1_tile.hpp"           // the fc1 tile steps shared with aggregate_split.hip and aggregate_bwd.hip; k_pad_matrix
 
 using namespace zt;
+using namespace zt::dense;        // f32x4, round_up, AGG_LDS_BUDGET, AGG_THREADS / AGG_WAVES / NTW / NTW_WIDE
 
 namespace {
 
 constexpr int MAX_MT = 5;          // M-tiles (16 gathered rows each) per workgroup
 constexpr int MAX_MT_BIG = 16;     // ... of the instantiation for 80 < k <= 255 (k_fc1_agg<TAB, MAX_MT_BIG>)
 constexpr int MAX_MT_BIG_WIDE = 8; // ... of the one for 128 < D (k_fc1_agg<TAB, MAX_MT_BIG_WIDE, NTW_WIDE>: 80 < k <= 128)
-constexpr int LDS_BUDGET = 150 * 1024;
-
-__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 #ifdef ZT_AGG_STAMP
 // diagnostic build only: shader-clock time per phase of k_fc1_agg, summed over workgroups
@@ -39,16 +38,6 @@ __device__ unsigned long long g_agg[8];
 #else
 #define AGG_STAMP(i) do { } while (0)
 #endif
-
-// Zero-padded copy of the block W[0..rows)[c0..c0+cols) of a matrix with leading dimension ld -> Wp[rows_p][cols_p].
-__global__ void k_pad_matrix(const float *__restrict__ W, int ld, int c0, int rows, int cols, float *__restrict__ Wp,
-                             int rows_p, int cols_p)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_p * cols_p) return;
-    const int r = i / cols_p, c = i % cols_p;
-    Wp[i] = (r < rows && c < cols) ? W[(size_t)r * ld + c0 + c] : 0.f;
-}
 
 // ---------------------------------------------------------------------------
 // fc1 + ReLU + weighted k-reduction.
@@ -69,16 +58,13 @@ __global__ void k_pad_matrix(const float *__restrict__ W, int ld, int c0, int ro
 // NW: N-tiles of the hidden layer per wave.  NTW (Dp <= 128); NTW_WIDE for 128 < D <= 256, D % 4 == 0 (MMT <= MAX_MT_BIG_WIDE:
 // the accumulators of MMT x NW tiles stay at the MAX_MT_BIG instantiation's 128 registers).
 template <bool TAB, int MMT = MAX_MT, int NW = NTW>
-__global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
-    const float *__restrict__ memory, const float *__restrict__ efeat, const float *__restrict__ time_w,
-    long long num_nodes, long long num_edges, int D, int F, int T, long long N, int k, int rq, int mt_count, int lda,
-    const int *__restrict__ nbr, const int *__restrict__ eix, const float *__restrict__ dt,
-    const float *__restrict__ w, const float *__restrict__ W1p, int K1p, const float *__restrict__ b1,
-    float *__restrict__ H, float *__restrict__ S, int *status, int Dout, const int *__restrict__ row_map,
-    const float *__restrict__ overlay, unsigned drop_lo = 0u, unsigned drop_hi = 0u, unsigned drop_thr = 0u,
-    float drop_inv = 1.f)
+__global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(FcAggArgs a, int rq, int mt_count, int lda)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // (a struct member carries no __restrict__: the hot pointers as locals)
+    const float *__restrict__ memory = a.memory, *__restrict__ efeat = a.efeat, *__restrict__ overlay = a.overlay;
+    const int D = a.ldm, F = a.F, T = a.T, k = a.k, Dout = a.D;       // D: the row stride of `memory` (TAB: Dp)
+    const long long N = a.N;
     float *A = reinterpret_cast<float *>(smem);                       // [mt*16][lda]
     float *wn = A + (size_t)mt_count * 16 * lda;                      // [mt*16] normalised weights
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -89,18 +75,9 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     const int CM = TAB ? 0 : D;                                       // memory columns held in the tile
     const int K1 = CM + F + T;
     const size_t mb = ((size_t)m * N + q0) * k;                       // first entry of this tile in [M][N][k]
-    // ---- this wave's N-tiles {wave, wave+4, ..}; weight fragments stream from L2 one chunk ahead of their MFMAs
-    // ---- (keeping all of them in registers was measured: no gain, and it halves the occupancy)
     const int NT = (Dout + 15) / 16;
     const int r16 = lane & 15, g4 = lane >> 4;
-    const float *bp[NW];
-    bool live[NW];
-#pragma unroll
-    for (int b = 0; b < NW; ++b) {
-        const int nt = wave + b * AGG_WAVES;
-        live[b] = nt < NT;
-        bp[b] = W1p + (size_t)((live[b] ? nt : 0) * 16 + r16) * K1p + 4 * g4;
-    }
+    const fc1_weight_cursor<NW> wc(a.W1p, a.K1p, NT);
 #ifdef ZT_AGG_STAMP
     long long t_prev__ = clock64();
 #endif
@@ -116,17 +93,17 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
         int nb = 0, ei = 0;
         float d = 0.f, wv = 0.f;
         if (g < rows) {
-            nb = nbr[mb + g]; ei = eix[mb + g]; d = dt[mb + g]; wv = w[mb + g];
-            if (nb < 0 || nb >= num_nodes || ei < 0 || ei >= num_edges) {
-                atomicExch(status, ZT_ERR_RANGE);
+            nb = a.nbr[mb + g]; ei = a.eix[mb + g]; d = a.dt[mb + g]; wv = a.w[mb + g];
+            if (nb < 0 || nb >= a.num_nodes || ei < 0 || ei >= a.num_edges) {
+                atomicExch(a.status, ZT_ERR_RANGE);
                 nb = 0; ei = 0;
             }
             // training: rows of the lazily updated memory live in a compact overlay (aggregate_bwd.hip)
-            if (!TAB && row_map != nullptr) { const int ov = row_map[nb]; if (ov >= 0) nb = -ov - 1; }
+            if (!TAB && a.row_map != nullptr) { const int ov = a.row_map[nb]; if (ov >= 0) nb = -ov - 1; }
         }
         g_nb[g] = nb; g_ei[g] = ei; g_dt[g] = d; wn[g] = wv;
     }
-    for (int c = tid; c < T; c += AGG_THREADS) tw[c] = time_w[c];
+    for (int c = tid; c < T; c += AGG_THREADS) tw[c] = a.time_w[c];
     __syncthreads();
     // w / sum(w), 0 where the sum is 0 (:267-270); sum in entry order like torch.sum(dim=1)
     float my_sum = 0.f;
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     __syncthreads();
     if (tid < rows) {
         wn[tid] = (my_sum == 0.f) ? 0.f : wn[tid] / my_sum;
-        if (tid % k == 0) S[(size_t)m * N + q0 + tid / k] = (my_sum == 0.f) ? 0.f : 1.f;
+        if (tid % k == 0) a.S[(size_t)m * N + q0 + tid / k] = (my_sum == 0.f) ? 0.f : 1.f;
     }
 
     auto mem_row = [&](int s) { return s >= 0 ? memory + (size_t)s * D : overlay + (size_t)(-s - 1) * D; };
@@ -146,24 +123,26 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     // memory round trip is hidden behind it; the MFMAs then accumulate on top of them
     f32x4 acc[MMT][NW];
 #pragma unroll
-    for (int a = 0; a < MMT; ++a)
+    for (int x = 0; x < MMT; ++x)
 #pragma unroll
         for (int b = 0; b < NW; ++b) {
-            acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (TAB && a < mt_count && live[b]) {
+            acc[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (TAB && x < mt_count && wc.live[b]) {
                 const int col = (wave + b * AGG_WAVES) * 16 + r16;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[a][b][j] = memory[(size_t)g_nb[a * 16 + g4 * 4 + j] * D + col];
+                for (int j = 0; j < 4; ++j) acc[x][b][j] = memory[(size_t)g_nb[x * 16 + g4 * 4 + j] * D + col];
             }
         }
-    // ---- gather: flat (row, column) loops, GU loads in flight per thread before any LDS store
-    // ---- (a row-at-a-time loop serialises on HBM latency: 20 rows x ~3 us per wave)
+    // ---- gather: flat (row, column) loops, GU loads in flight per thread before any LDS store (fc1_tile.hpp: batched_copy)
     constexpr int GU = 8;
-    const unsigned mD = fastdiv_magic((unsigned)D), mF = fastdiv_magic((unsigned)(F > 0 ? F : 1)),
-                   mT = fastdiv_magic((unsigned)(T > 0 ? T : 1));
+    const unsigned mT = fastdiv_magic((unsigned)(T > 0 ? T : 1));
     // rows are whole float4s, 16-byte aligned in HBM and in the tile
     const bool vecD = TAB || ((D & 3) == 0 && ((size_t)memory & 15) == 0);
     const bool vecF = vecD && F > 0 && (F & 3) == 0 && ((size_t)efeat & 15) == 0;
+    auto mem1 = [&](int g, int c) { return mem_row(g_nb[g])[c]; };
+    auto mem4 = [&](int g, int c) { return *reinterpret_cast<const f32x4 *>(mem_row(g_nb[g]) + 4 * c); };
+    auto ef1 = [&](int g, int c) { return efeat[(size_t)g_ei[g] * F + c]; };
+    auto ef4 = [&](int g, int c) { return *reinterpret_cast<const f32x4 *>(efeat + (size_t)g_ei[g] * F + 4 * c); };
     // cos(dt * w_c) for every (row, frequency); reads only LDS.  A thread keeps ONE frequency in a register and
     // walks down a block of rows, four dt values per (broadcast) LDS read: no dependent LDS read and no index
     // arithmetic per element, and the four cosines of a step are independent instructions.
@@ -179,165 +158,44 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
         const int RG = AGG_THREADS / TC, per = rows_p / RG;             // rows_p is a multiple of 16
         const int c = tid & (TC - 1), g0 = (tid / TC) * per;
         if (c >= T) return;
-        const float wc = tw[c];
+        const float freq = tw[c];
         float *dst = A + (size_t)g0 * lda + CM + F + c;
         for (int i = 0; i < per; i += 4) {
             const f32x4 d4 = *reinterpret_cast<const f32x4 *>(g_dt + g0 + i);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                dst[(size_t)(i + u) * lda] = (g0 + i + u) < rows ? time_cosf(d4[u] * wc) : 0.f;     // cos(t*w + 0)
+                dst[(size_t)(i + u) * lda] = (g0 + i + u) < rows ? time_cosf(d4[u] * freq) : 0.f;     // cos(t*w + 0)
         }
     };
+    const batched_copy<float, GU> ef_s(F, rows_p, rows);
     if (vecD) {
         // One memory round trip for the whole gather, with the time encoding computed underneath it: the
         // first GU 16-byte loads of every thread (all of them for D = 100, k = 20) and the first batch
         // of edge-feature loads are issued, then the cosines are evaluated, then the loaded values are
         // stored to the tile.  (Memory latency under the gather load is ~3-4 us per dependent access.)
-        const int D4 = D >> 2, F4 = F >> 2;
-        const unsigned mD4 = fastdiv_magic((unsigned)D4), mF4 = fastdiv_magic((unsigned)(F4 > 0 ? F4 : 1));
+        const batched_copy<f32x4, GU> mem_v(D >> 2, rows_p, rows), ef_v(F >> 2, rows_p, rows);
         f32x4 vm[GU], vf[GU];
         float sf[GU];
-        if (!TAB) {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mD4), c = f - g * D4;
-                vm[u] = (f < rows_p * D4 && g < rows) ? *reinterpret_cast<const f32x4 *>(mem_row(g_nb[g]) + 4 * c)
-                                                      : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-        if (vecF) {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mF4), c = f - g * F4;
-                vf[u] = (f < rows_p * F4 && g < rows)
-                            ? *reinterpret_cast<const f32x4 *>(efeat + (size_t)g_ei[g] * F + 4 * c)
-                            : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mF), c = f - g * F;
-                sf[u] = (f < rows_p * F && g < rows) ? efeat[(size_t)g_ei[g] * F + c] : 0.f;
-            }
-        }
+        if (!TAB) mem_v.load(vm, tid, mem4);                            // 1. first batch of memory loads
+        if (vecF) ef_v.load(vf, tid, ef4);                              // 2. first batch of edge-feature loads
+        else ef_s.load(sf, tid, ef1);
         AGG_STAMP(1);
-        time_encode();
+        time_encode();                                                  // 3. the cosines underneath them
         AGG_STAMP(2);
-        if (!TAB) {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mD4), c = f - g * D4;
-                if (f < rows_p * D4) *reinterpret_cast<f32x4 *>(A + (size_t)g * lda + 4 * c) = vm[u];
-            }
-        }
-        if (vecF) {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mF4), c = f - g * F4;
-                if (f < rows_p * F4) *reinterpret_cast<f32x4 *>(A + (size_t)g * lda + CM + 4 * c) = vf[u];
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = tid + u * AGG_THREADS;
-                const int g = fastdiv(f, mF), c = f - g * F;
-                if (f < rows_p * F) A[(size_t)g * lda + CM + c] = sf[u];
-            }
-        }
-        // whatever does not fit the first batch
-        for (int f0 = tid + AGG_THREADS * GU; !TAB && f0 < rows_p * D4; f0 += AGG_THREADS * GU) {
-            f32x4 v[GU];
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mD4), c = f - g * D4;
-                v[u] = (f < rows_p * D4 && g < rows)
-                           ? *reinterpret_cast<const f32x4 *>(mem_row(g_nb[g]) + 4 * c)
-                           : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mD4), c = f - g * D4;
-                if (f < rows_p * D4) *reinterpret_cast<f32x4 *>(A + (size_t)g * lda + 4 * c) = v[u];
-            }
-        }
-        if (vecF) {
-            for (int f0 = tid + AGG_THREADS * GU; f0 < rows_p * F4; f0 += AGG_THREADS * GU) {
-                f32x4 v[GU];
-#pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    const int f = f0 + u * AGG_THREADS;
-                    const int g = fastdiv(f, mF4), c = f - g * F4;
-                    v[u] = (f < rows_p * F4 && g < rows)
-                               ? *reinterpret_cast<const f32x4 *>(efeat + (size_t)g_ei[g] * F + 4 * c)
-                               : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    const int f = f0 + u * AGG_THREADS;
-                    const int g = fastdiv(f, mF4), c = f - g * F4;
-                    if (f < rows_p * F4) *reinterpret_cast<f32x4 *>(A + (size_t)g * lda + CM + 4 * c) = v[u];
-                }
-            }
-        } else {
-            for (int f0 = tid + AGG_THREADS * GU; f0 < rows_p * F; f0 += AGG_THREADS * GU) {
-                float v[GU];
-#pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    const int f = f0 + u * AGG_THREADS;
-                    const int g = fastdiv(f, mF), c = f - g * F;
-                    v[u] = (f < rows_p * F && g < rows) ? efeat[(size_t)g_ei[g] * F + c] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < GU; ++u) {
-                    const int f = f0 + u * AGG_THREADS;
-                    const int g = fastdiv(f, mF), c = f - g * F;
-                    if (f < rows_p * F) A[(size_t)g * lda + CM + c] = v[u];
-                }
-            }
-        }
+        if (!TAB) mem_v.store(vm, tid, A, lda, 0);                      // 4. the stores
+        if (vecF) ef_v.store(vf, tid, A, lda, CM);
+        else ef_s.store(sf, tid, A, lda, CM);
+        if (!TAB) mem_v.run(tid + AGG_THREADS * GU, mem4, A, lda, 0);   // 5. whatever does not fit the first batch
+        if (vecF) ef_v.run(tid + AGG_THREADS * GU, ef4, A, lda, CM);
+        else ef_s.run(tid + AGG_THREADS * GU, ef1, A, lda, CM);
     } else {
-        for (int f0 = tid; f0 < rows_p * D; f0 += AGG_THREADS * GU) {
-            float v[GU];
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mD), c = f - g * D;
-                v[u] = (f < rows_p * D && g < rows) ? mem_row(g_nb[g])[c] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mD), c = f - g * D;
-                if (f < rows_p * D) A[(size_t)g * lda + c] = v[u];
-            }
-        }
+        batched_copy<float, GU>(D, rows_p, rows).run(tid, mem1, A, lda, 0);
         AGG_STAMP(1);
-        for (int f0 = tid; f0 < rows_p * F; f0 += AGG_THREADS * GU) {
-            float v[GU];
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mF), c = f - g * F;
-                v[u] = (f < rows_p * F && g < rows) ? efeat[(size_t)g_ei[g] * F + c] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int f = f0 + u * AGG_THREADS;
-                const int g = fastdiv(f, mF), c = f - g * F;
-                if (f < rows_p * F) A[(size_t)g * lda + CM + c] = v[u];
-            }
-        }
+        ef_s.run(tid, ef1, A, lda, CM);
         AGG_STAMP(2);
         time_encode();
     }
-    const int padw = K1p - K1;
+    const int padw = a.K1p - K1;
     const unsigned mP = fastdiv_magic((unsigned)(padw > 0 ? padw : 1));
     for (int f = tid; f < rows_p * padw; f += AGG_THREADS) {
         const int g = fastdiv(f, mP), c = f - g * padw;
@@ -348,58 +206,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
     AGG_STAMP(4);
 
     // ---- fc1 on f32 MFMA: wave handles N-tiles {wave, wave+4, ..}, all M-tiles ----
-    {
-        const int nchunk = K1p / 16;
-        f32x4 bcur[NW], bnext[NW];
-#pragma unroll
-        for (int b = 0; b < NW; ++b) bcur[b] = *reinterpret_cast<const f32x4 *>(bp[b]);
-        for (int kc = 0; kc < nchunk; ++kc) {
-            if (kc + 1 < nchunk) {
-#pragma unroll
-                for (int b = 0; b < NW; ++b) bnext[b] = *reinterpret_cast<const f32x4 *>(bp[b] + 16 * (kc + 1));
-            }
-            f32x4 av[MMT];
-#pragma unroll
-            for (int a = 0; a < MMT; ++a)
-                av[a] = a < mt_count
-                            ? *reinterpret_cast<const f32x4 *>(A + (size_t)(a * 16 + r16) * lda + 16 * kc + 4 * g4)
-                            : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int a = 0; a < MMT; ++a)
-#pragma unroll
-                    for (int b = 0; b < NW; ++b)
-                        if (a < mt_count && live[b])
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bcur[b][j], acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int b = 0; b < NW; ++b) bcur[b] = bnext[b];
-        }
-    }
+    fc1_mfma<MMT, NW>(A, lda, mt_count, wc, a.K1p, acc);
     AGG_STAMP(5);
     __syncthreads();   // every wave is done reading the A tile: reuse it for the hidden rows
 
-    // ---- bias + ReLU + weight, staged as Hs[g][col] in the A region ----
+    // ---- bias + ReLU + dropout + weight, staged as Hs[g][col] in the A region ----
     float *Hs = A;                               // [rows_p][ldh]
     const int ldh = NT * 16 + 1;
-#pragma unroll
-    for (int b = 0; b < NW; ++b) {
-        if (!live[b]) continue;
-        const int col = (wave + b * AGG_WAVES) * 16 + r16;
-        const float bias = col < Dout ? b1[col] : 0.f;
-#pragma unroll
-        for (int a = 0; a < MMT; ++a) {
-            if (a >= mt_count) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int g = a * 16 + g4 * 4 + j;
-                float v = acc[a][b][j] + bias;
-                v = v > 0.f ? v : 0.f;
-                if (drop_thr != 0u) v *= drop_scale(drop_lo, drop_hi, drop_thr, drop_inv, (unsigned long long)(mb + g) * Dout + col);
-                Hs[(size_t)g * ldh + col] = v * wn[g];
-            }
-        }
-    }
+    fc1_hidden_rows<MMT, NW>(acc, wc.live, mt_count, a, wn, mb, Hs, ldh);      // (wn = 0 past the last entry: staged above)
     __syncthreads();
     AGG_STAMP(6);
     // ---- reduce over the k neighbours of each query row ----
@@ -408,7 +222,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg(
         const int q = fastdiv(idx, mDo), c = idx - q * Dout;
         float s = 0.f;
         for (int j = 0; j < k; ++j) s += Hs[(size_t)(q * k + j) * ldh + c];
-        H[((size_t)m * N + q0 + q) * Dout + c] = s;
+        a.H[((size_t)m * N + q0 + q) * Dout + c] = s;
     }
     AGG_STAMP(7);
 }
@@ -1265,13 +1079,13 @@ bool tile_shape(int Kp, int Dp, int k, int T, int *lda_out, int *mt_out, int *rq
 {
     const int lda = Kp + 4;
     int mt = max_mt;
-    while (mt > 1 && ((size_t)mt * 16 * lda * 4 + (size_t)mt * 16 * 16) > (size_t)LDS_BUDGET) --mt;
+    while (mt > 1 && ((size_t)mt * 16 * lda * 4 + (size_t)mt * 16 * 16) > (size_t)AGG_LDS_BUDGET) --mt;
     int rq = (mt * 16) / k;
     if (rq < 1) {
         // one query row must fit: grow to ceil(k/16) tiles if the budget allows
         mt = (k + 15) / 16;
         rq = 1;
-        if (mt > max_mt || ((size_t)mt * 16 * lda * 4 + (size_t)mt * 16 * 16) > (size_t)LDS_BUDGET) return false;
+        if (mt > max_mt || ((size_t)mt * 16 * lda * 4 + (size_t)mt * 16 * 16) > (size_t)AGG_LDS_BUDGET) return false;
     }
     mt = (rq * k + 15) / 16;
     // the hidden staging [rows_p][Dp+1] reuses the A region: it must fit
@@ -1493,7 +1307,7 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
                                        kernel_choice(ZT_CHOICE_EMBED_OUT), p);
     if (kp.refusal == Refusal::shape) {
         set_error("zt_embed: D=%d F=%d T=%d k=%d outside the supported shapes (D <= 128, or a multiple of 4 up to %d; one query "
-                  "row of k neighbours must fit the %d KB LDS tile)", D, F, T, k, MAX_D, LDS_BUDGET / 1024);
+                  "row of k neighbours must fit the %d KB LDS tile)", D, F, T, k, MAX_D, AGG_LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1507,7 +1321,7 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
     }
     if (kp.refusal == Refusal::no_split) {
         set_error("zt_embed: k=%d needs the projected table (a query row's [memory | ef | time] tile does not fit %d KB of LDS, "
-                  "nor does a chunk of it)", k, LDS_BUDGET / 1024);
+                  "nor does a chunk of it)", k, AGG_LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     if (kp.refusal == Refusal::groups) { set_error("zt_embed: %d partial-sum groups per row", kp.hg); return ZT_ERR_UNSUPPORTED; }
@@ -1519,12 +1333,21 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
     }
     const dim3 tile_grid((unsigned)(kp.rq > 0 ? (N + kp.rq - 1) / kp.rq : 0), (unsigned)M);
     const bool wide = p.Dp > 16 * NTW * AGG_WAVES;     // the NTW_WIDE instantiations (128 < D <= 256)
-    // k_fc1_agg over the plan's tile: `rows` is memory (row stride D) or the projected table (stride Dp)
-    auto tiled = [&](decltype(&k_fc1_agg<false>) fn, const float *rows, int ld, size_t w_off, int Kp) {
+    // the general kernels' arguments: the full [memory | ef | time] tile of the stored memory, no overlay, no dropout
+    FcAggArgs fa{};
+    fa.memory = memory_dev; fa.efeat = efeat_dev; fa.time_w = wt->time_w;
+    fa.num_nodes = num_nodes; fa.num_edges = num_edges; fa.N = N;
+    fa.D = D; fa.F = F; fa.T = T; fa.M = M; fa.k = k; fa.ldm = D;
+    fa.nbr = nbr_dev; fa.eix = eix_dev; fa.dt = dt_dev; fa.w = w_dev;
+    fa.W1p = reinterpret_cast<const float *>(ws + p.off_w1p); fa.K1p = p.K1p; fa.b1 = wt->fc1_b;
+    fa.H = H; fa.S = S; fa.status = status_dev;
+    fa.set_dropout(0.f, 0ull);
+    // k_fc1_agg over the plan's tile, of memory rows or (table) of the projected table's: row stride Dp, the [ef | time] weights
+    auto tiled = [&](decltype(&k_fc1_agg<false>) fn, bool table) {
+        FcAggArgs ta = fa;
+        if (table) { ta.memory = proj_table_dev; ta.ldm = p.Dp; ta.W1p = reinterpret_cast<const float *>(ws + p.off_w1t); ta.K1p = p.K2p; }
         ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), kp.lds));
-        fn<<<tile_grid, AGG_THREADS, kp.lds, s>>>(rows, efeat_dev, wt->time_w, num_nodes, num_edges, ld, F, T, N, k, kp.rq, kp.mt,
-                                                  kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + w_off),
-                                                  Kp, wt->fc1_b, H, S, status_dev, D, nullptr, nullptr, 0u, 0u, 0u, 1.f);
+        fn<<<tile_grid, AGG_THREADS, kp.lds, s>>>(ta, kp.rq, kp.mt, kp.lda);
         return ZT_OK;
     };
     // k_fc1_agg_reg: persistent, one workgroup (4 waves) per CU
@@ -1567,22 +1390,11 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
             return ZT_OK;
         });
         break;
-    case AggKernel::tiled_table:
-        rc = tiled(wide ? k_fc1_agg<true, MAX_MT, NTW_WIDE> : k_fc1_agg<true>, proj_table_dev, p.Dp, p.off_w1t, p.K2p);
-        break;
-    case AggKernel::tiled_table_big:
-        rc = tiled(wide ? k_fc1_agg<true, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<true, MAX_MT_BIG>, proj_table_dev, p.Dp, p.off_w1t,
-                   p.K2p);
-        break;
-    case AggKernel::tiled_full: rc = tiled(wide ? k_fc1_agg<false, MAX_MT, NTW_WIDE> : k_fc1_agg<false>, memory_dev, D, p.off_w1p, p.K1p); break;
-    case AggKernel::tiled_full_big:
-        rc = tiled(wide ? k_fc1_agg<false, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<false, MAX_MT_BIG>, memory_dev, D, p.off_w1p, p.K1p);
-        break;
-    case AggKernel::split:
-        rc = fc1_agg_split_launch(memory_dev, nullptr, nullptr, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, M, k,
-                                  nbr_dev, eix_dev, dt_dev, w_dev, reinterpret_cast<const float *>(ws + p.off_w1p), p.K1p,
-                                  wt->fc1_b, H, S, status_dev, 0.f, 0ull, s);
-        break;
+    case AggKernel::tiled_table: rc = tiled(wide ? k_fc1_agg<true, MAX_MT, NTW_WIDE> : k_fc1_agg<true>, true); break;
+    case AggKernel::tiled_table_big: rc = tiled(wide ? k_fc1_agg<true, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<true, MAX_MT_BIG>, true); break;
+    case AggKernel::tiled_full: rc = tiled(wide ? k_fc1_agg<false, MAX_MT, NTW_WIDE> : k_fc1_agg<false>, false); break;
+    case AggKernel::tiled_full_big: rc = tiled(wide ? k_fc1_agg<false, MAX_MT_BIG_WIDE, NTW_WIDE> : k_fc1_agg<false, MAX_MT_BIG>, false); break;
+    case AggKernel::split: rc = fc1_agg_split_launch(fa, s); break;
     case AggKernel::unsupported: break;               // (refused above)
     }
     if (rc != ZT_OK) return rc;
@@ -1728,24 +1540,27 @@ extern "C" int zt_agg_train_forward(const float *memory_dev, const float *overla
         return ZT_ERR_UNSUPPORTED;
     }
     if (kp.refusal == Refusal::no_split) {
-        set_error("zt_agg_train_forward: D=%d F=%d T=%d k=%d: no 16-row chunk fits %d KB of LDS", D, F, T, k, LDS_BUDGET / 1024);
+        set_error("zt_agg_train_forward: D=%d F=%d T=%d k=%d: no 16-row chunk fits %d KB of LDS", D, F, T, k, AGG_LDS_BUDGET / 1024);
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace_dev);
-    const float *W1p = reinterpret_cast<const float *>(ws + p.off_w1p);
     embed_prepare(wt, D, F, T, p, ws, s);          // the weights change every optimizer step
+    FcAggArgs fa{};
+    fa.memory = memory_dev; fa.efeat = efeat_dev; fa.time_w = wt->time_w;
+    fa.num_nodes = num_nodes; fa.num_edges = num_edges; fa.N = N;
+    fa.D = D; fa.F = F; fa.T = T; fa.M = M; fa.k = k; fa.ldm = D;
+    fa.nbr = nbr_dev; fa.eix = eix_dev; fa.dt = dt_dev; fa.w = w_dev;
+    fa.W1p = reinterpret_cast<const float *>(ws + p.off_w1p); fa.K1p = p.K1p; fa.b1 = wt->fc1_b;
+    fa.H = H_dev; fa.S = S_dev; fa.status = status_dev;
+    fa.overlay = overlay_dev; fa.row_map = row_map_dev;
+    fa.set_dropout(drop_p, drop_seed);
     if (kp.agg == AggKernel::split)                // a query row wider than the 80-row tile: chunks of that tile
-        return fc1_agg_split_launch(memory_dev, overlay_dev, row_map_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N,
-                                    M, k, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b, H_dev, S_dev, status_dev, drop_p,
-                                    drop_seed, s);
+        return fc1_agg_split_launch(fa, s);
     const auto fwd = p.Dp > 16 * NTW * AGG_WAVES ? k_fc1_agg<false, MAX_MT, NTW_WIDE> : k_fc1_agg<false>;
     ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fwd), kp.lds));
     dim3 grid((unsigned)((N + kp.rq - 1) / kp.rq), (unsigned)M);
-    fwd<<<grid, AGG_THREADS, kp.lds, s>>>(memory_dev, efeat_dev, wt->time_w, num_nodes, num_edges, D, F, T, N, k,
-                                          kp.rq, kp.mt, kp.lda, nbr_dev, eix_dev, dt_dev, w_dev, W1p, p.K1p, wt->fc1_b,
-                                          H_dev, S_dev, status_dev, D, row_map_dev, overlay_dev, (unsigned)drop_seed,
-                                          (unsigned)(drop_seed >> 32), zt::drop_threshold(drop_p), 1.f / (1.f - drop_p));
+    fwd<<<grid, AGG_THREADS, kp.lds, s>>>(fa, kp.rq, kp.mt, kp.lda);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

@@ -15,34 +15,21 @@
 //   A query row wider than one tile (k > 80, or F = 172 past k = 64) is split: a tile is then one chunk of one row's
 //   neighbours, (m, n, chunk), and re-reads the row's k weights for the normaliser (forward: aggregate_split.hip).
 #include "common.hpp"
+#include "fc1_tile.hpp"            // the gather and the fc1 product shared with the forward kernels; k_pad_matrix
 
 using namespace zt;
+using namespace zt::dense;         // f32x4, round_up, AGG_LDS_BUDGET, AGG_THREADS / AGG_WAVES / NTW / NTW_WIDE
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BW_THREADS = 256;
-constexpr int BW_WAVES = 4;
 constexpr int BW_MT = 5;           // 16-row tiles of gathered rows per step (80 rows)
-constexpr int BW_NTW = 2;          // forward N-tiles per wave (D <= 128)
-constexpr int BW_NTW_WIDE = 4;     // ... of the instantiation for 128 < D <= 256 (D % 4 == 0)
 constexpr int BW_MAX_OT = 24;      // dW1 output tiles per wave and launch (96 accumulator registers)
-constexpr int BW_MT_WIDE = 3;      // ... the BW_NTW_WIDE instantiation: 48 rows per step, 12 dW1 tiles per wave (the accumulators of
+constexpr int BW_MT_WIDE = 3;      // ... the NTW_WIDE instantiation: 48 rows per step, 12 dW1 tiles per wave (the accumulators of
 constexpr int BW_MAX_OT_WIDE = 12; // its forward recompute are four N-tiles wide: within the register file without scratch)
 
-__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 struct BwdArgs {
-    const float *memory, *overlay;     // [num_nodes][D], [U][D]
-    const int *row_map;                // [num_nodes]: overlay row or -1
-    const float *efeat, *time_w;
-    long long num_nodes, num_edges, N;
-    int D, F, T, k, M, rq, lda, ldp, K1p, Dp;
-    const int *nbr, *eix;
-    const float *dt, *w;
-    const float *W1p;                  // [Dp][K1p] zero padded fc1 weight
-    const float *b1;
+    FcAggArgs f;                       // the forward's arguments (H, S, status unused; ldm = D)
+    int rq, lda, ldp, Dp;
     const float *dH;                   // [M][N][D]
     float *dW1, *db1, *d_overlay;      // [D][K1], [D], [U][D]  (accumulated with atomics)
     long long n_tiles;                 // tiles of rq query rows per model (row split: N * nch)
@@ -50,15 +37,16 @@ struct BwdArgs {
     int nch;                           // row split: chunks of mt * 16 gathered rows per query row (rq = 1); 0: whole rows
     int kt_lo, kt_hi;                  // this launch accumulates dW1 column tiles [kt_lo, kt_hi)
     int first;                         // 1: this launch also accumulates db1 and d_overlay
-    unsigned drop_lo, drop_hi, drop_thr;   // training dropout of the hidden layer (common.hpp: drop_scale); thr = 0: none
-    float drop_inv;
 };
 
-template <int NW, int OT, int MT>  // forward N-tiles per wave, dW1 tiles per wave, 16-row tiles per step: BW_* or BW_*_WIDE
-__global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
+template <int NW, int OT, int MT>  // forward N-tiles per wave, dW1 tiles per wave, 16-row tiles per step: NTW / BW_* or NTW_WIDE / BW_*_WIDE
+__global__ __launch_bounds__(AGG_THREADS) void k_fc1_agg_bwd(BwdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int D = a.D, F = a.F, T = a.T, k = a.k, lda = a.lda, ldp = a.ldp, K1p = a.K1p, Dp = a.Dp;
+    const FcAggArgs &f = a.f;
+    // (a struct member carries no __restrict__: the hot pointers as locals)
+    const float *__restrict__ memory = f.memory, *__restrict__ overlay = f.overlay, *__restrict__ efeat = f.efeat;
+    const int D = f.D, F = f.F, T = f.T, k = f.k, lda = a.lda, ldp = a.ldp, K1p = f.K1p, Dp = a.Dp;
     const int K1 = D + F + T;
     const int mt = a.mt, rows_p = mt * 16;
     float *A = reinterpret_cast<float *>(smem);                 // [rows_p][lda]   gathered rows
@@ -76,9 +64,12 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
 #pragma unroll
     for (int q = 0; q < OT; ++q) gw[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     float gb = 0.f;                                             // db1[tid] (tid < Dp)
-    for (int c = tid; c < T; c += BW_THREADS) tw[c] = a.time_w[c];
+    for (int c = tid; c < T; c += AGG_THREADS) tw[c] = f.time_w[c];
+    const fc1_weight_cursor<NW> wc(f.W1p, K1p, NT);
+    const fc1_row_source from(memory, overlay, efeat, tw, D, F, T);
+    const unsigned mK4 = fastdiv_magic((unsigned)(K1p >> 2));
 
-    const long long total = a.n_tiles * a.M;
+    const long long total = a.n_tiles * f.M;
     for (long long tile = blockIdx.x; tile < total; tile += gridDim.x) {
         const int m = (int)(tile / a.n_tiles);
         long long q0 = (tile % a.n_tiles) * a.rq;
@@ -88,18 +79,18 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
             q0 = r / a.nch;
             j0 = (int)(r - q0 * a.nch) * rows_p;
         }
-        const int nq = (int)((a.N - q0) < a.rq ? (a.N - q0) : a.rq);
+        const int nq = (int)((f.N - q0) < a.rq ? (f.N - q0) : a.rq);
         const int rows = a.nch > 0 ? (k - j0 < rows_p ? k - j0 : rows_p) : nq * k;
-        const size_t mb = ((size_t)m * a.N + q0) * k + j0;     // first gathered row of this tile in [M][N][k]
+        const size_t mb = ((size_t)m * f.N + q0) * k + j0;     // first gathered row of this tile in [M][N][k]
         __syncthreads();                                        // previous tile fully consumed
-        for (int g = tid; g < rows_p; g += BW_THREADS) {
+        for (int g = tid; g < rows_p; g += AGG_THREADS) {
             int src = 0, ei = 0;
             float d = 0.f, wv = 0.f;
             if (g < rows) {
-                int nb = a.nbr[mb + g];
-                ei = a.eix[mb + g]; d = a.dt[mb + g]; wv = a.w[mb + g];
-                if (nb < 0 || nb >= a.num_nodes || ei < 0 || ei >= a.num_edges) { nb = 0; ei = 0; wv = 0.f; }
-                const int ov = a.row_map ? a.row_map[nb] : -1;
+                int nb = f.nbr[mb + g];
+                ei = f.eix[mb + g]; d = f.dt[mb + g]; wv = f.w[mb + g];
+                if (nb < 0 || nb >= f.num_nodes || ei < 0 || ei >= f.num_edges) { nb = 0; ei = 0; wv = 0.f; }
+                const int ov = f.row_map ? f.row_map[nb] : -1;
                 src = ov >= 0 ? -ov - 1 : nb;
             }
             g_src[g] = src; g_ei[g] = ei; g_dt[g] = d; wn[g] = wv;
@@ -108,8 +99,8 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         float *wrow = P;
         if (a.nch > 0 && tid < k) {
             const size_t e = mb - j0 + tid;
-            const int nb = a.nbr[e], ei = a.eix[e];
-            wrow[tid] = (nb < 0 || nb >= a.num_nodes || ei < 0 || ei >= a.num_edges) ? 0.f : a.w[e];
+            const int nb = f.nbr[e], ei = f.eix[e];
+            wrow[tid] = (nb < 0 || nb >= f.num_nodes || ei < 0 || ei >= f.num_edges) ? 0.f : f.w[e];
         }
         __syncthreads();
         float my_sum = 0.f;
@@ -123,22 +114,8 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         }
         __syncthreads();
         if (tid < rows) wn[tid] = (my_sum == 0.f) ? 0.f : wn[tid] / my_sum;
-        // ---- gather x = [memory' | ef | cos] into the tile ----
-        for (int f = tid; f < rows_p * K1p; f += BW_THREADS) {
-            const int g = f / K1p, c = f - g * K1p;
-            float v = 0.f;
-            if (g < rows && c < K1) {
-                if (c < D) {
-                    const int s = g_src[g];
-                    v = s >= 0 ? a.memory[(size_t)s * D + c] : a.overlay[(size_t)(-s - 1) * D + c];
-                } else if (c < D + F) {
-                    v = a.efeat[(size_t)g_ei[g] * F + (c - D)];
-                } else {
-                    v = time_cosf(g_dt[g] * tw[c - D - F]);
-                }
-            }
-            A[(size_t)g * lda + c] = v;
-        }
+        // ---- gather x = [memory' | ef | cos | 0] into the tile ----
+        gather_rows_v4(A, lda, rows, rows_p, K1p, mK4, from, g_src, g_ei, g_dt);
         __syncthreads();
         // ---- recompute pre = x W1^T (f32 MFMA; wave owns N-tiles {wave, wave+4, ..}) ----
         f32x4 acc[MT][NW];
@@ -146,33 +123,14 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         for (int x = 0; x < MT; ++x)
 #pragma unroll
             for (int b = 0; b < NW; ++b) acc[x][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int kc = 0; kc < K1p / 16; ++kc) {
-            f32x4 av[MT], bv[NW];
-#pragma unroll
-            for (int x = 0; x < MT; ++x)
-                av[x] = x < mt ? *reinterpret_cast<const f32x4 *>(A + (size_t)(x * 16 + r16) * lda + 16 * kc + 4 * g4)
-                               : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int b = 0; b < NW; ++b) {
-                const int nt = wave + b * BW_WAVES;
-                bv[b] = nt < NT ? *reinterpret_cast<const f32x4 *>(a.W1p + (size_t)(nt * 16 + r16) * K1p + 16 * kc + 4 * g4)
-                                : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int x = 0; x < MT; ++x)
-#pragma unroll
-                    for (int b = 0; b < NW; ++b)
-                        if (x < mt) acc[x][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[x][j], bv[b][j], acc[x][b], 0, 0, 0);
-        }
+        fc1_mfma<MT, NW>(A, lda, mt, wc, K1p, acc);
         // ---- dpre = w_k dH 1[pre > 0] into P ----
 #pragma unroll
         for (int b = 0; b < NW; ++b) {
-            const int nt = wave + b * BW_WAVES;
+            const int nt = wave + b * AGG_WAVES;
             if (nt >= NT) continue;
             const int col = nt * 16 + r16;
-            const float bias = col < D ? a.b1[col] : 0.f;
+            const float bias = col < D ? f.b1[col] : 0.f;
 #pragma unroll
             for (int x = 0; x < MT; ++x)
 #pragma unroll
@@ -181,9 +139,9 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
                     const int g = x * 16 + g4 * 4 + j;
                     float dp = 0.f;
                     if (g < rows && col < D && acc[x][b][j] + bias > 0.f) {
-                        dp = wn[g] * a.dH[((size_t)m * a.N + q0 + g / k) * D + col];
-                        if (a.drop_thr != 0u)
-                            dp *= drop_scale(a.drop_lo, a.drop_hi, a.drop_thr, a.drop_inv, (unsigned long long)(mb + g) * D + col);
+                        dp = wn[g] * a.dH[((size_t)m * f.N + q0 + g / k) * D + col];
+                        if (f.drop_thr != 0u)
+                            dp *= drop_scale(f.drop_lo, f.drop_hi, f.drop_thr, f.drop_inv, (unsigned long long)(mb + g) * D + col);
                     }
                     P[(size_t)g * ldp + col] = dp;
                 }
@@ -198,7 +156,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
         // ---- dW1[i][c] += sum_g P[g][i] x[g][c]: tiles t = wave, wave+4, ...; tile t = (dt, kt) ----
 #pragma unroll
         for (int q = 0; q < OT; ++q) {
-            const int t = wave + q * BW_WAVES;
+            const int t = wave + q * AGG_WAVES;
             if (t >= n_ot) break;
             const int dtile = t / KT, ktile = a.kt_lo + t - dtile * KT;
             f32x4 c4 = gw[q];
@@ -211,7 +169,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
             gw[q] = c4;
         }
         // ---- d_overlay[row][c] += sum_col P[g][col] W1[col][c]  (memory columns c < D only) ----
-        if (a.first && a.row_map != nullptr) {
+        if (a.first && f.row_map != nullptr) {
             f32x4 dx[MT][NW];
 #pragma unroll
             for (int x = 0; x < MT; ++x)
@@ -224,8 +182,8 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
                 for (int x = 0; x < MT; ++x) pa[x] = x < mt ? P[(size_t)(x * 16 + r16) * ldp + col] : 0.f;   // [m = row g][k = col]
 #pragma unroll
                 for (int b = 0; b < NW; ++b) {
-                    const int c = (wave + b * BW_WAVES) * 16 + r16;
-                    wb[b] = c < D ? a.W1p[(size_t)col * K1p + c] : 0.f;                           // [k = col][n = c]
+                    const int c = (wave + b * AGG_WAVES) * 16 + r16;
+                    wb[b] = c < D ? f.W1p[(size_t)col * K1p + c] : 0.f;                           // [k = col][n = c]
                 }
 #pragma unroll
                 for (int x = 0; x < MT; ++x)
@@ -235,7 +193,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
             }
 #pragma unroll
             for (int b = 0; b < NW; ++b) {
-                const int c = (wave + b * BW_WAVES) * 16 + r16;
+                const int c = (wave + b * AGG_WAVES) * 16 + r16;
                 if (c >= D) continue;
 #pragma unroll
                 for (int x = 0; x < MT; ++x)
@@ -252,7 +210,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
     // ---- flush the accumulated weight gradient ----
 #pragma unroll
     for (int q = 0; q < OT; ++q) {
-        const int t = wave + q * BW_WAVES;
+        const int t = wave + q * AGG_WAVES;
         if (t >= n_ot) break;
         const int dtile = t / KT, ktile = a.kt_lo + t - dtile * KT;
         const int c = ktile * 16 + r16;
@@ -265,15 +223,6 @@ __global__ __launch_bounds__(BW_THREADS) void k_fc1_agg_bwd(BwdArgs a)
     if (a.first && tid < D && gb != 0.f) atomicAdd(a.db1 + tid, gb);
 }
 
-// Zero-padded copy W[rows][cols] -> Wp[rows_p][cols_p]
-__global__ void k_pad(const float *__restrict__ W, int rows, int cols, float *__restrict__ Wp, int rows_p, int cols_p)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_p * cols_p) return;
-    const int r = i / cols_p, c = i % cols_p;
-    Wp[i] = (r < rows && c < cols) ? W[(size_t)r * cols + c] : 0.f;
-}
-
 // the backward's tile: as many whole query rows as fit max_mt 16-row tiles and 150 KB of LDS, else (a query row does not fit)
 // the row split: tiles of one chunk of max_mt (or as many as fit) 16-row tiles, nch chunks per row.  false: refused
 size_t bwd_lds(int mt, int K1p, int Dp, int T) { return ((size_t)mt * 16 * (K1p + 4 + Dp + 4) + (size_t)mt * 16 * 4 + T) * 4; }
@@ -282,19 +231,19 @@ bool bwd_tile(int D, int F, int T, int k, int &mt, int &rq, int &nch)
 {
     if (!zt::width_supported(D) || F < 0 || T < 0 || k <= 0) return false;
     const int Dp = round_up(D, 16), K1p = round_up(D + F + T, 16);
-    const int max_mt = Dp > 16 * BW_NTW * BW_WAVES ? BW_MT_WIDE : BW_MT;
+    const int max_mt = Dp > 16 * NTW * AGG_WAVES ? BW_MT_WIDE : BW_MT;
     mt = max_mt;
-    while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > 150 * 1024) --mt;
+    while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > AGG_LDS_BUDGET) --mt;
     rq = (mt * 16) / k;
     if (rq < 1) { mt = (k + 15) / 16; rq = 1; }
     nch = 0;
-    if ((mt > max_mt || bwd_lds(mt, K1p, Dp, T) > 150 * 1024) && k <= ZT_MAX_K_WIDE) {
+    if ((mt > max_mt || bwd_lds(mt, K1p, Dp, T) > AGG_LDS_BUDGET) && k <= ZT_MAX_K_WIDE) {
         mt = max_mt;
-        while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > 150 * 1024) --mt;
+        while (mt > 1 && bwd_lds(mt, K1p, Dp, T) > AGG_LDS_BUDGET) --mt;
         rq = 1;
         nch = (k + mt * 16 - 1) / (mt * 16);
     }
-    if (mt > max_mt || bwd_lds(mt, K1p, Dp, T) > 150 * 1024) return false;
+    if (mt > max_mt || bwd_lds(mt, K1p, Dp, T) > AGG_LDS_BUDGET) return false;
     if (nch == 0) mt = (rq * k + 15) / 16;
     return true;
 }
@@ -329,7 +278,7 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     }
     if (N == 0) return ZT_OK;
     const int K1 = D + F + T, Dp = round_up(D, 16), K1p = round_up(K1, 16);
-    const bool wide = Dp > 16 * BW_NTW * BW_WAVES;
+    const bool wide = Dp > 16 * NTW * AGG_WAVES;
     int mt, rq, nch;
     if (!bwd_tile(D, F, T, k, mt, rq, nch)) {
         set_error("zt_agg_train_backward: D=%d F=%d T=%d k=%d outside the supported shapes (D <= 128, or a multiple of 4 up to %d)",
@@ -338,21 +287,21 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     }
     hipStream_t s = (hipStream_t)stream;
     float *W1p = reinterpret_cast<float *>(workspace_dev);
-    k_pad<<<(Dp * K1p + 255) / 256, 256, 0, s>>>(fc1_w_dev, D, K1, W1p, Dp, K1p);
-    BwdArgs a;
-    a.memory = memory_dev; a.overlay = overlay_dev; a.row_map = row_map_dev; a.efeat = efeat_dev; a.time_w = time_w_dev;
-    a.drop_lo = (unsigned)drop_seed; a.drop_hi = (unsigned)(drop_seed >> 32);
-    a.drop_thr = (drop_p > 0.f && drop_p < 1.f) ? zt::drop_threshold(drop_p) : 0u;
-    a.drop_inv = a.drop_thr ? 1.f / (1.f - drop_p) : 1.f;
-    a.num_nodes = num_nodes; a.num_edges = num_edges; a.N = N;
-    a.D = D; a.F = F; a.T = T; a.k = k; a.M = M; a.rq = rq; a.lda = K1p + 4; a.ldp = Dp + 4; a.K1p = K1p; a.Dp = Dp;
-    a.nbr = nbr_dev; a.eix = eix_dev; a.dt = dt_dev; a.w = w_dev; a.W1p = W1p; a.b1 = fc1_b_dev; a.dH = dH_dev;
-    a.dW1 = dW1_dev; a.db1 = db1_dev; a.d_overlay = d_overlay_dev;
+    k_pad_matrix<<<(Dp * K1p + 255) / 256, 256, 0, s>>>(fc1_w_dev, K1, 0, D, K1, W1p, Dp, K1p);
+    BwdArgs a{};
+    FcAggArgs &f = a.f;
+    f.memory = memory_dev; f.overlay = overlay_dev; f.row_map = row_map_dev; f.efeat = efeat_dev; f.time_w = time_w_dev;
+    f.set_dropout((drop_p > 0.f && drop_p < 1.f) ? drop_p : 0.f, drop_seed);
+    f.num_nodes = num_nodes; f.num_edges = num_edges; f.N = N;
+    f.D = D; f.F = F; f.T = T; f.k = k; f.M = M; f.ldm = D; f.K1p = K1p;
+    f.nbr = nbr_dev; f.eix = eix_dev; f.dt = dt_dev; f.w = w_dev; f.W1p = W1p; f.b1 = fc1_b_dev;
+    a.rq = rq; a.lda = K1p + 4; a.ldp = Dp + 4; a.Dp = Dp;
+    a.dH = dH_dev; a.dW1 = dW1_dev; a.db1 = db1_dev; a.d_overlay = d_overlay_dev;
     a.n_tiles = nch > 0 ? N * nch : (N + rq - 1) / rq;
     a.mt = mt;
     a.nch = nch;
     const size_t lds = bwd_lds(mt, K1p, Dp, T);
-    const auto fn = wide ? k_fc1_agg_bwd<BW_NTW_WIDE, BW_MAX_OT_WIDE, BW_MT_WIDE> : k_fc1_agg_bwd<BW_NTW, BW_MAX_OT, BW_MT>;
+    const auto fn = wide ? k_fc1_agg_bwd<NTW_WIDE, BW_MAX_OT_WIDE, BW_MT_WIDE> : k_fc1_agg_bwd<NTW, BW_MAX_OT, BW_MT>;
     ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(fn), lds));
     hipDeviceProp_t prop;
     int dev = 0;
@@ -364,10 +313,10 @@ extern "C" int zt_agg_train_backward(const float *memory_dev, const float *overl
     // (F = 172; D > 128: at D = 256, windows of 3 column tiles) take several launches over windows of input columns (the
     // recompute is repeated, db1 / d_overlay are not).
     const int NT = Dp / 16, KT = K1p / 16;
-    const int win = ((wide ? BW_MAX_OT_WIDE : BW_MAX_OT) * BW_WAVES) / NT;
+    const int win = ((wide ? BW_MAX_OT_WIDE : BW_MAX_OT) * AGG_WAVES) / NT;
     for (int lo = 0; lo < KT; lo += win) {
         a.kt_lo = lo; a.kt_hi = lo + win < KT ? lo + win : KT; a.first = lo == 0 ? 1 : 0;
-        fn<<<(unsigned)grid, BW_THREADS, lds, s>>>(a);
+        fn<<<(unsigned)grid, AGG_THREADS, lds, s>>>(a);
     }
     ZT_LAUNCH_CHECK();
     return ZT_OK;

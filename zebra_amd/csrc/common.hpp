@@ -14,6 +14,25 @@ namespace zt {
 
 void set_error(const char *fmt, ...);
 
+// Shared by the dense f32-MFMA kernels of the embedding path (aggregate.hip, aggregate_split.hip, aggregate_bwd.hip,
+// embed_out_body.hpp, fc1_tile.hpp).  In a namespace of their own: other translation units keep helpers of these names.
+namespace dense {
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+constexpr int AGG_LDS_BUDGET = 150 * 1024;     // dynamic LDS one workgroup of the aggregation kernels may ask for
+constexpr int AGG_THREADS = 256;
+constexpr int AGG_WAVES = 4;
+constexpr int NTW = 2;             // N-tiles per wave -> D <= 128
+constexpr int NTW_WIDE = 4;        // ... of the instantiations for 128 < D <= 256 (D % 4 == 0)
+}  // namespace dense
+// p -> threshold of drop_scale (0 = no dropout); host side
+inline unsigned drop_threshold(float p)
+{
+    if (!(p > 0.f)) return 0u;
+    const double t = (double)p * 4294967296.0;
+    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+}
+
 // Optional HIP-event timing of individual kernels (zt_profile_* in the ABI):
 // an event pair is recorded on the launch stream around the kernel; elapsed
 // times are summed per kernel name when the profile is read.
@@ -199,11 +218,34 @@ int fc1_agg_split_rows(int D, int F, int T);
 // zt_agg_train_backward takes (D, F, T, k) (aggregate_bwd.hip)
 bool agg_backward_supported(int D, int F, int T, int k);
 size_t fc1_agg_split_lds(int D, int F, int T);
-int fc1_agg_split_launch(const float *memory, const float *overlay, const int *row_map, const float *efeat,
-                         const float *time_w, long long num_nodes, long long num_edges, int D, int F, int T, long long N,
-                         int M, int k, const int *nbr, const int *eix, const float *dt, const float *w, const float *W1p,
-                         int K1p, const float *b1, float *H, float *S, int *status, float drop_p,
-                         unsigned long long drop_seed, hipStream_t s);
+// The arguments of the neighbour aggregation's general kernels (k_fc1_agg, k_fc1_agg_split take it by value beside their tile
+// parameters; k_fc1_agg_bwd inside its BwdArgs): H[m][n][:] = sum_k w_k/sum(w) drop(relu(fc1([memory'[nbr] | ef | cos(dt w)])))
+struct FcAggArgs {
+    const float *memory;               // [num_nodes][ldm]: the memory table -- or (k_fc1_agg<true>) the projected table
+    const float *efeat, *time_w;       // [num_edges][F], [T]
+    long long num_nodes, num_edges, N;
+    int D, F, T, M, k;
+    int ldm;                           // row stride of `memory`: D (the projected table: Dp)
+    const int *nbr, *eix;              // [M][N][k]
+    const float *dt, *w;               // [M][N][k]
+    const float *W1p;                  // [Dp][K1p] zero padded fc1 weight (the table path: its [ef | time] columns)
+    int K1p;
+    const float *b1;
+    float *H, *S;                      // [M][N][D], [M][N]
+    int *status;
+    const float *overlay;              // training: [U][D] rows of the lazily updated memory, or NULL
+    const int *row_map;                // [num_nodes]: overlay row or -1; NULL: no overlay
+    unsigned drop_lo, drop_hi, drop_thr;   // training dropout of the hidden layer (drop_scale below); thr = 0: none
+    float drop_inv;
+
+    void set_dropout(float p, unsigned long long seed)
+    {
+        drop_lo = (unsigned)seed; drop_hi = (unsigned)(seed >> 32);
+        drop_thr = drop_threshold(p);
+        drop_inv = drop_thr ? 1.f / (1.f - p) : 1.f;
+    }
+};
+int fc1_agg_split_launch(const FcAggArgs &a, hipStream_t s);
 int pruned_topk_multi_fill(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t nq, int32_t width,
                            int32_t depth, int32_t n_models, const double *alpha_host, const double *beta_host, int32_t k,
                            int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev,
@@ -483,15 +525,6 @@ __device__ __forceinline__ float drop_scale(unsigned seed_lo, unsigned seed_hi, 
     return h >= thr ? inv_keep : 0.f;
 }
 
-#endif  // __HIPCC__
-// p -> threshold of drop_scale (0 = no dropout); host side
-inline unsigned drop_threshold(float p)
-{
-    if (!(p > 0.f)) return 0u;
-    const double t = (double)p * 4294967296.0;
-    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-}
-#if defined(__HIPCC__)
 // floor(f / d) for small f via a precomputed multiplier m = fastdiv_magic(d); exact for f*d < 2^32.
 __device__ __forceinline__ unsigned fastdiv_magic(unsigned d) { return d <= 1u ? 0u : 0xFFFFFFFFu / d + 1u; }   // 0 = divide by 1
 __device__ __forceinline__ int fastdiv(int f, unsigned m) { return m == 0u ? f : (int)__umulhi((unsigned)f, m); }

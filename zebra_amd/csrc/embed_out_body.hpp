@@ -12,15 +12,11 @@ using zt::fastdiv;
 using zt::fastdiv_magic;
 using zt::wave_sync;
 
-#ifndef ZT_F32X4_DEFINED
-#define ZT_F32X4_DEFINED
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#endif
-
-constexpr int AGG_THREADS = 256;
-constexpr int AGG_WAVES = 4;
-constexpr int NTW = 2;             // N-tiles per wave -> D <= 128
-constexpr int NTW_WIDE = 4;        // ... of the instantiations for 128 < D <= 256 (D % 4 == 0)
+using zt::dense::f32x4;
+using zt::dense::AGG_THREADS;
+using zt::dense::AGG_WAVES;
+using zt::dense::NTW;
+using zt::dense::NTW_WIDE;
 
 // ---------------------------------------------------------------------------
 // out[n] = [ fc2s(relu(fc1s(memory[nodes[n]]))) | fc2(H_0[n]) + b2*S_0[n] | ... ]
