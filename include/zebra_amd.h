@@ -196,6 +196,22 @@ int zt_tppr_plan(zt_tppr *h, const int32_t *nodes_dev, const int64_t *eidx_dev,
                  int64_t B, int32_t n_roles, int32_t model, uint64_t *token_out,
                  void *stream);
 
+/* Rows of ARBITRARY nodes from the live state, read-only: out_* [n_emitted_models][N][k] -- model as in zt_tppr_stream:
+ * -1 every model, else that one (ZT_ERR_ARG outside [-1, n_tppr)).  Row i is what extract_streaming_tppr
+ * (utils/util.py:447-469) gives for the dictionary of nodes_dev[i] at current_timestamp = ts_dev[i] (N timestamps, one per
+ * row): entries in dictionary order, dt = f32(f64(t) - f64(f32(entry ts))); entries j >= len of a non-empty row read
+ * 0, 0, f32(t), 0; an empty row is all zeros -- the bits zt_tppr_stream emits for a negative sample's row.
+ * An id outside [0, num_nodes) gives an all-zero row and ZT_ERR_RANGE in *status_dev (may be NULL), as in zt_embed.
+ * N = 0: ZT_OK, nothing enqueued; a NULL pointer (status_dev apart) or N < 0: ZT_ERR_ARG before any device call.
+ * The call reads the state's rows and NOTHING else of the handle -- no control word, plan, epoch, hub version or status
+ * latch is read or written on the device, the handle is not modified on the host; a latched failure of an earlier launch
+ * neither fails it nor is cleared by it.
+ * CONTRACT: the call is enqueued on a stream ordered after every writer of the state (zt_tppr_stream, zt_tppr_import*,
+ * zt_tppr_copy / reset, a pipeline's T-PPR stream), and where a pipeline owns the handle zt_pipeline_outstanding is 0 --
+ * batches queried ahead have their updates applied already, the rows would be those of a later time. */
+int zt_tppr_query(const zt_tppr *h, const int32_t *nodes_dev, const double *ts_dev, int64_t N, int32_t model,
+                  int32_t *out_nodes_dev, int32_t *out_eidx_dev, float *out_dt_dev, float *out_w_dev,
+                  int32_t *status_dev, void *stream);
 /* Synchronises `stream` and returns the latched status (ZT_OK, ZT_ERR_RANGE
  * or ZT_ERR_TIMEOUT) of the launches so far, clearing it. */
 int zt_tppr_status(zt_tppr *h, void *stream);
@@ -767,6 +783,35 @@ int zt_affinity_train_backward(const float *emb_dev, int64_t B, int32_t H,
  * ZT_ERR_UNSUPPORTED before any device call.  zt_link_metrics_plan is where the form is decided (host code only). */
 int zt_link_metrics(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev,
                     int32_t accumulate, void *stream);
+/* One source against many candidates (csrc/rank.hip): prob_dev [Q][C],
+ *   prob[q][c] = sigmoid(fc2(relu(fc1([emb_q[q] | emb_c[cand_idx[q][c]]])))),
+ * MergeLayer as compute_edge_probabilities applies it (model/tgn_model.py:185-188, utils/util.py:14-26).  emb_q_dev [Q][H],
+ * emb_c_dev [Nc][H]; cand_idx_dev [Q][C] names rows of emb_c, -1 = absent (probability 0 is written); NULL: every query takes
+ * all Nc candidates in order, and C must equal Nc (ZT_ERR_ARG otherwise).  The weights are read as they lie in the module
+ * (UNPACKED, as zt_affinity_train_forward; fc1_b and fc2_w 16-byte aligned).  Two launches of the f32 MFMA GEMM project both
+ * sides into the workspace (P_q = emb_q W_a^T, P_c = emb_c W_b^T), one pair kernel does the rest: H runs in chunks, so no
+ * LDS-resident-row bound applies: any H % 4 == 0 with 4 <= H <= 4352 (ZT_ERR_UNSUPPORTED otherwise -- this bound is
+ * zt_affinity_rank's own, zt_affinity and zt_affinity_train_* keep theirs).  Every pair's sum has one fixed association, no
+ * float atomics: two calls give the same bits.  Q = 0 or C = 0: ZT_OK, nothing touched; argument checks come before any
+ * device call.
+ * workspace_dev: zt_affinity_rank_workspace_bytes(Q, Nc, H) bytes (-1: H unsupported, or a negative size), 16-byte aligned,
+ * sized for THIS call's Q and Nc or more.  Its first int32 is the call's status word: the call sets it to 0, and to
+ * ZT_ERR_RANGE when an index is >= Nc or below -1 (that pair reads probability 0); read it once the stream has passed the
+ * call. */
+int64_t zt_affinity_rank_workspace_bytes(int64_t Q, int64_t Nc, int32_t H);
+int zt_affinity_rank(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                     const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w,
+                     float *prob_dev, void *workspace_dev, void *stream);
+/* Ranks, MRR and Hits@k of prob_dev [Q][C] (cand_idx_dev as above, may be NULL: every entry present).  Column 0 is the
+ * positive:  rank = 1 + #{c >= 1 present : p_c > p_0} + 0.5 #{c >= 1 present : p_c == p_0}, the mean of the optimistic and
+ * the pessimistic rank.  A query whose column 0 is absent is skipped and not counted.  rank_dev [Q] (or NULL) receives the
+ * ranks, 0 for a skipped query.  acc_dev [5] (float64) is ADDED to: sum of 1 / rank, Hits@1, Hits@3, Hits@10 (rank <= n),
+ * queries counted -- so a pass accumulates over its batches without a host read; the caller zeroes it.  One workgroup; the
+ * per-query ranks are written, then one lane adds them to the sums first to last: a fixed order, the same bits on every
+ * run.  Q = 0 or C = 0: ZT_OK, nothing touched; NULL prob_dev / acc_dev or a negative size: ZT_ERR_ARG before any device
+ * call. */
+int zt_rank_metrics(const float *prob_dev, const int32_t *cand_idx_dev, int64_t Q, int64_t C, float *rank_dev,
+                    double *acc_dev, void *stream);
 #define ZT_METRICS_FORM_REFUSED 0
 #define ZT_METRICS_FORM_SINGLE 1 /* one bitonic sort of 2B 64-bit (key | label) words */
 #define ZT_METRICS_FORM_SPLIT 2  /* positives and negatives sorted as two runs of 32-bit keys */

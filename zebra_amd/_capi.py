@@ -34,6 +34,7 @@ SYMBOLS = [
     "zt_affinity_train_workspace_bytes", "zt_affinity_train_forward", "zt_affinity_train_backward",
     "zt_link_metrics_plan", "zt_pipeline_set_metrics", "zt_pipeline_metrics",
     "zt_link_bce_forward", "zt_link_bce_backward", "zt_adam_step", "zt_adam_plan",
+    "zt_tppr_query", "zt_affinity_rank_workspace_bytes", "zt_affinity_rank", "zt_rank_metrics",
 ]
 
 
@@ -53,6 +54,7 @@ METRICS_FORM_REFUSED, METRICS_FORM_SINGLE, METRICS_FORM_SPLIT = 0, 1, 2   # zt_l
 METRICS_MAX_B = 16384
 MSG_ONE, MSG_TWO = 1, 2
 ADAM_CHUNK, ADAM_MAX_TENSORS = 4096, 64                         # zt_adam_plan / zt_adam_step
+RANK_MIN_H, RANK_MAX_H = 4, 4352                                # zt_affinity_rank's hidden widths (H % 4 == 0)
 
 
 def set_kernel_choice(which, value):
@@ -140,7 +142,7 @@ def lib():
             _lib.zt_pipeline_main_stream.restype = C.c_void_p
         _lib.zt_version.restype = C.c_char_p
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
-                     "zt_affinity_train_workspace_bytes"):
+                     "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib

@@ -23,6 +23,7 @@ SOURCES = {
     "tppr_prepass.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=DPP"],
     "tppr_stream.hip": ["-ffp-contract=off"],
     "tppr_io.hip": [],
+    "tppr_query.hip": ["-ffp-contract=off"],
     "tppr_prune.hip": ["-ffp-contract=off"],
     "aggregate.hip": [],
     "aggregate_wide.hip": [],
@@ -33,6 +34,7 @@ SOURCES = {
     "attention.hip": [],
     "scoring.hip": [],
     "scoring_train.hip": [],
+    "rank.hip": [],
     "train_tail.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],

@@ -149,3 +149,56 @@ def _eval_edge_prediction_native(model, negative_edge_sampler, data, batch_size)
     if measured != nb:
         raise RuntimeError("%d of %d batches were measured" % (measured, nb))
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Evaluation by rank: one positive against many negatives (MRR, Hits@k)
+# ---------------------------------------------------------------------------------------------------------------------
+def rank_metrics(prob, cand_idx=None, out=None, ranks=False):
+    """zt_rank_metrics on float32 CUDA probabilities [Q, C]: column 0 is the positive, rank = 1 + #{c >= 1 present : p_c > p_0}
+    + 0.5 #{c >= 1 present : p_c == p_0} -- the mean of the optimistic and the pessimistic rank; ``cand_idx`` [Q, C] (or None:
+    all present) marks absent entries with -1, and a query whose positive is absent is skipped.  ADDS (sum of 1 / rank, Hits@1,
+    Hits@3, Hits@10, queries counted) to the float64 [5] tensor ``out`` (None: a fresh one of zeros) and returns it -- with
+    ``ranks=True`` (out, rank [Q]; 0 for a skipped query).  No host synchronisation."""
+    import ctypes as C
+    from ._capi import check, lib, ptr, stream_ptr
+    if not (prob.is_cuda and prob.dtype == torch.float32 and prob.dim() == 2):
+        raise ValueError("rank_metrics takes a float32 CUDA tensor [Q, C]")
+    Q, Cn = prob.shape
+    acc = out if out is not None else torch.zeros(5, dtype=torch.float64, device=prob.device)
+    rk = torch.zeros(Q, dtype=torch.float32, device=prob.device) if ranks else None
+    ix = None if cand_idx is None else cand_idx.to(prob.device, torch.int32).contiguous()
+    if Q == 0 or Cn == 0:
+        return (acc, rk) if ranks else acc
+    check(lib().zt_rank_metrics(ptr(prob.contiguous()), ptr(ix), C.c_int64(Q), C.c_int64(Cn), ptr(rk), ptr(acc), stream_ptr()),
+          "zt_rank_metrics")
+    return (acc, rk) if ranks else acc
+
+
+@torch.no_grad()
+def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_size=200, n_negatives=100):
+    """Link prediction by rank, what temporal-graph benchmarks report: per batch, ``B * n_negatives`` negatives from ONE
+    ``sampler.sample`` call, reshaped [B, n_negatives]; every source ranks [destination | its negatives] read-only from the
+    state BEFORE the batch (TGN.rank_candidates), zt_rank_metrics accumulates on the device; then the state advances with the
+    ordinary eval step, whose single negative is the first column.  Returns dict(mrr, hits1, hits3, hits10) from one host
+    read at the end.  The model runs without the native pipeline."""
+    assert negative_edge_sampler.seed is not None
+    negative_edge_sampler.reset_random_state()
+    model = model.eval()
+    if not model.test_mode:                                      # (as the eval step begins)
+        model.update_memory_in_test(model.memory)
+        model.test_mode = True
+    n = data.n_interactions
+    acc = torch.zeros(5, dtype=torch.float64, device=model.device)
+    for s in range(0, n, batch_size):
+        e = min(n, s + batch_size)
+        _, negatives = negative_edge_sampler.sample((e - s) * n_negatives)
+        negatives = np.asarray(negatives).reshape(e - s, n_negatives)
+        cands = np.concatenate([np.asarray(data.destinations[s:e]).reshape(-1, 1), negatives], axis=1)
+        prob = model.rank_candidates(data.sources[s:e], data.timestamps[s:e], cands)
+        rank_metrics(prob.float(), None, out=acc)
+        model.compute_temporal_embeddings(data.sources[s:e], data.destinations[s:e], negatives[:, 0], data.timestamps[s:e],
+                                          data.edge_idxs[s:e], n_neighbors, False)
+    a = acc.cpu().numpy()                                        # (the one host read of the pass)
+    q = a[4] if a[4] > 0 else float("nan")
+    return dict(mrr=float(a[0] / q), hits1=float(a[1] / q), hits3=float(a[2] / q), hits10=float(a[3] / q))

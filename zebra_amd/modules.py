@@ -621,6 +621,15 @@ class GraphDiffusionEmbedding(nn.Module):
             return self.pruning_topk_device(nodes_d, ts_d, check_status=check_status)
         raise ValueError("tppr_strategy must be 'streaming' or 'pruning'")
 
+    def query_device(self, nodes_d, ts_d, check_status=True):
+        """T-PPR rows of arbitrary (node, time) pairs -- int32[N], float64[N] -- read-only: the streaming strategy reads
+        the live state without an update (tppr_finder.query_device), the pruning strategy's walk never writes."""
+        if self.tppr_strategy == "streaming":
+            return self.tppr_finder.query_device(nodes_d, ts_d, -1, check_status=check_status)
+        if self.tppr_strategy == "pruning":
+            return self.pruning_topk_device(nodes_d, ts_d, check_status=check_status)
+        raise ValueError("tppr_strategy must be 'streaming' or 'pruning'")
+
     def _weights_key(self):
         """Identity + in-place version of every weight the kernels read: the padded copies in the workspace are
         remade only when this changes (an optimizer step, load_state_dict, .to())."""

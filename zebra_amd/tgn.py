@@ -156,6 +156,114 @@ class TGN(torch.nn.Module):
                                 C.c_int64(st["max_B"]), C.c_int32(1 if ready else 0), stream_ptr()), "zt_affinity")
         return prob
 
+    # ------------------------------------------------------------------ read-only queries and ranking
+    def _as_device(self, a, dtype):
+        """numpy array, list or tensor -> contiguous 1-D+ tensor of ``dtype`` on this model's device"""
+        if torch.is_tensor(a):
+            return a.to(self.device, dtype).contiguous()
+        npd = {torch.int32: np.int32, torch.float64: np.float64}[dtype]
+        return torch.from_numpy(np.ascontiguousarray(a, npd)).to(self.device)
+
+    @torch.no_grad()
+    def embed_nodes(self, nodes, timestamps, check_status=True):
+        """Embeddings of arbitrary nodes at arbitrary times from the model's CURRENT state, read-only: numpy arrays or
+        tensors in, a float32 [N, D (n_tppr + 1)] CUDA tensor out.  The T-PPR rows come from ``query_device`` (no update),
+        the forward is the eval one (``embed_device`` on the memory table); no message is stored, no memory row, no T-PPR
+        dictionary and no ``batch_counter`` changes.  RuntimeError when the model is not in test mode -- messages of
+        training batches are pending: run ``update_memory_in_test`` through an eval step first -- or when the native
+        pipeline is enabled: its streams and the batches it has queried ahead are not covered by this call."""
+        if getattr(self, "_pipe", None) is not None:
+            raise RuntimeError("embed_nodes does not cover the native pipeline (its streams, and batches queried ahead, "
+                               "whose T-PPR updates are applied already): call enable_pipeline(False) first")
+        if not self.test_mode:
+            raise RuntimeError("embed_nodes needs the model in test mode: messages of training batches are pending; run an "
+                               "eval step (step_device / compute_temporal_embeddings(train=False)) first")
+        nodes_d = self._as_device(nodes, torch.int32).reshape(-1)
+        ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
+        if nodes_d.numel() != ts_d.numel():
+            raise ValueError("embed_nodes takes one timestamp per node")
+        em = self.embedding_module
+        if nodes_d.numel() == 0:
+            return torch.empty((0, self.embedding_dimension * (em.n_tppr + 1)), dtype=torch.float32, device=self.device)
+        on, oe, od, ow = em.query_device(nodes_d, ts_d, check_status=check_status)
+        return em.embed_device(self.memory.memory, nodes_d, on, oe, od, ow, check_status=check_status, memory_obj=self.memory)
+
+    @torch.no_grad()
+    def rank_scores(self, emb_q, emb_c, cand_idx=None, check_status=True):
+        """prob [Q, C] = sigmoid(affinity_score(emb_q[q], emb_c[cand_idx[q, c]])): one source against many candidates.
+        ``cand_idx`` int32 [Q, C] names rows of ``emb_c`` (-1: absent, probability 0) or is None: every query takes all of
+        ``emb_c``.  float32 CUDA embeddings of a width zt_affinity_rank takes (H % 4 == 0, 4 <= H <= 4352) go through it
+        (csrc/rank.hip); anything else through torch's composition, a chunk of queries at a time."""
+        a = self.affinity_score
+        Q, H = emb_q.shape
+        Nc = emb_c.shape[0]
+        C_ = Nc if cand_idx is None else cand_idx.shape[1]
+        hip = (emb_q.is_cuda and emb_c.is_cuda and emb_q.dtype == torch.float32 and emb_c.dtype == torch.float32
+               and H % 4 == 0 and _capi.RANK_MIN_H <= H <= _capi.RANK_MAX_H)
+        if not hip:
+            out = torch.zeros((Q, C_), dtype=emb_q.dtype, device=emb_q.device)
+            if Q == 0 or C_ == 0:
+                return out
+            step = max(1, (1 << 24) // max(1, C_ * 2 * H))
+            for s in range(0, Q, step):
+                q = emb_q[s:s + step]
+                if cand_idx is None:
+                    ec = emb_c.unsqueeze(0).expand(q.shape[0], Nc, H)
+                    live = None
+                else:
+                    ix = cand_idx[s:s + step].long()
+                    if int(ix.max()) >= Nc or int(ix.min()) < -1:
+                        raise IndexError("rank_scores: candidate index out of range")
+                    live = ix >= 0
+                    ec = emb_c[ix.clamp(min=0)]
+                x = torch.cat([q.unsqueeze(1).expand(-1, C_, -1), ec], dim=2)
+                p = a.fc2(a.act(a.fc1(x))).squeeze(2).sigmoid()
+                out[s:s + step] = p if live is None else torch.where(live, p, torch.zeros_like(p))
+            return out
+        prob = torch.empty((Q, C_), dtype=torch.float32, device=self.device)
+        if Q == 0 or C_ == 0:
+            return prob
+        need = int(lib().zt_affinity_rank_workspace_bytes(C.c_int64(Q), C.c_int64(Nc), C.c_int32(H)))
+        ws = getattr(self, "_rank_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._rank_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        w = _capi.AffinityWeights()
+        w.fc1_w, w.fc1_b, w.fc2_w, w.fc2_b = (a.fc1.weight.data_ptr(), a.fc1.bias.data_ptr(), a.fc2.weight.data_ptr(),
+                                              a.fc2.bias.data_ptr())
+        ix = None if cand_idx is None else cand_idx.to(self.device, torch.int32).contiguous()
+        check(lib().zt_affinity_rank(ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), ptr(ix),
+                                     C.c_int64(C_), C.c_int32(H), C.byref(w), ptr(prob), ptr(ws), stream_ptr()),
+              "zt_affinity_rank")
+        if check_status and ix is not None:
+            st = int(ws[:4].view(torch.int32).item())           # the call's status word: first int32 of the workspace
+            if st != 0:
+                raise IndexError("zt_affinity_rank: candidate index out of range (status %d)" % st)
+        return prob
+
+    @torch.no_grad()
+    def rank_candidates(self, sources, timestamps, candidates, check_status=True):
+        """prob [Q, C] (CUDA) of ``sources[q]`` interacting with each of its candidates at ``timestamps[q]``, read-only
+        (``embed_nodes``): ``candidates`` is [Q, C] (-1: absent, probability 0) or [C], shared by all queries.  Every
+        distinct (candidate, time of its query) pair is embedded once."""
+        src_d = self._as_device(sources, torch.int32).reshape(-1)
+        ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
+        cand = self._as_device(candidates, torch.int32)
+        Q = src_d.numel()
+        if cand.dim() == 1:
+            cand = cand.unsqueeze(0).expand(Q, -1)
+        if cand.dim() != 2 or cand.shape[0] != Q or ts_d.numel() != Q:
+            raise ValueError("rank_candidates takes sources [Q], timestamps [Q] and candidates [Q, C] or [C]")
+        cand = cand.contiguous()
+        emb_q = self.embed_nodes(src_d, ts_d, check_status=check_status)
+        live = cand >= 0
+        t_of = ts_d.unsqueeze(1).expand_as(cand)
+        pairs = torch.stack([cand[live].to(torch.float64), t_of[live]])          # (node ids are exact in float64)
+        uniq, inv = torch.unique(pairs, dim=1, return_inverse=True)
+        emb_c = self.embed_nodes(uniq[0].to(torch.int32), uniq[1].contiguous(), check_status=check_status)
+        cand_idx = torch.full(cand.shape, -1, dtype=torch.int32, device=self.device)
+        cand_idx[live] = inv.to(torch.int32)
+        return self.rank_scores(emb_q, emb_c, cand_idx, check_status=check_status)
+
     def _score_pairs(self, s, dd, n):
         """The scorer as torch composes it (tgn_model.py:185-188): (pos [B, 1], neg [B, 1]) under autograd."""
         n_samples = s.shape[0]

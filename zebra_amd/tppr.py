@@ -281,6 +281,41 @@ class tppr_finder:
     def check_status(self):
         check(lib().zt_tppr_status(self._live.h, stream_ptr()), "zt_tppr_stream")
 
+    # ------------------------------------------------------------- read-only queries
+    def query_device(self, nodes_d, ts_d, model=-1, check_status=True):
+        """The rows ``stream_device`` would emit for arbitrary nodes at arbitrary times, WITHOUT an update
+        (zt_tppr_query: extract_streaming_tppr, utils/util.py:447-469, on the live state): int32[N] nodes and
+        float64[N] timestamps -- one per node -- in, four [n_models][N][k] CUDA tensors out.  Nothing of the state
+        is written.  Call it on a stream ordered after the state's writers (the current stream, without a pipeline).
+        An id outside [0, num_nodes) gives an all-zero row and, with ``check_status``, IndexError."""
+        N = nodes_d.numel()
+        if ts_d.numel() != N:
+            raise ValueError("query_device takes one timestamp per node")
+        nm = self.n_tppr if model < 0 else 1
+        d = nodes_d.device
+        on = torch.empty((nm, N, self.k), dtype=torch.int32, device=d)
+        oe = torch.empty_like(on)
+        od = torch.empty((nm, N, self.k), dtype=torch.float32, device=d)
+        ow = torch.empty_like(od)
+        if N == 0:                                  # (an empty tensor has no address to hand over: nothing to enqueue)
+            return on, oe, od, ow
+        if getattr(self, "_qstatus", None) is None:
+            self._qstatus = torch.zeros(1, dtype=torch.int32, device=d)
+        check(lib().zt_tppr_query(self._live.h, ptr(nodes_d), ptr(ts_d), C.c_int64(N), C.c_int32(model), ptr(on), ptr(oe),
+                                  ptr(od), ptr(ow), ptr(self._qstatus), stream_ptr()), "zt_tppr_query")
+        if check_status:
+            st = int(self._qstatus.item())
+            if st != 0:
+                self._qstatus.zero_()
+                raise IndexError("zt_tppr_query: node id out of range (status %d)" % st)
+        return on, oe, od, ow
+
+    def query_topk(self, nodes, timestamps):
+        """``query_device`` for host arrays: lists of per-model [N, k] arrays, like ``streaming_topk``."""
+        n = torch.from_numpy(np.ascontiguousarray(nodes, np.int32)).to(self._dev)
+        t = torch.from_numpy(np.ascontiguousarray(timestamps, np.float64)).to(self._dev)
+        return self._lists(*self.query_device(n, t, -1))
+
     @staticmethod
     def _lists(on, oe, od, ow):
         return ([a for a in on.cpu().numpy()], [a for a in oe.cpu().numpy()], [a for a in od.cpu().numpy()],
