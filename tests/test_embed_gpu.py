@@ -320,24 +320,28 @@ def test_out_gru_gate_gives_up_and_reports():
     tgn.enable_pipeline(False)
 
 
-@pytest.mark.parametrize("group,look,ragged,release", [(2, 5, False, 0), (3, 8, True, 0), (4, 11, False, 0), (2, 2, False, 0),
-                                                       (3, 1, True, 0), (8, 25, True, 0), (3, 8, True, _capi.RELEASE_LAUNCH),
-                                                       (4, 11, False, _capi.RELEASE_LAUNCH)])
-def test_grouped_tppr_launches_match_sequential(group, look, ragged, release):
+_GROUPED = [(2, 5, False, 0), (3, 8, True, 0), (4, 11, False, 0), (2, 2, False, 0), (3, 1, True, 0), (8, 25, True, 0),
+            (3, 8, True, _capi.RELEASE_LAUNCH), (4, 11, False, _capi.RELEASE_LAUNCH)]
+
+
+@pytest.mark.parametrize("group,look,ragged,release,tppr_cus", [c + (0,) for c in _GROUPED] + [(4, 11, False, 0, 32)],
+                         ids=["%d-%d-%s-%d" % c for c in _GROUPED] + ["4-11-False-0-masked"])
+def test_grouped_tppr_launches_match_sequential(group, look, ragged, release, tppr_cus):
     """zt_pipeline_set_group: the streaming T-PPR update of `group` consecutive batches as ONE launch (edges in
     order across the batches, every batch's rows in its own block) must not change any result -- whole batches and
     row shards, a full view ahead (3 * group - 1 batches), a short one (smaller groups come out), and a stream
     whose last batch is shorter.  release: how the aggregation of a batch learns that its rows are written -- the
     library's pick (round 6: a counter per batch inside the launch, the main stream passes a gate per batch) or the
-    event behind the whole launch (ZT_CHOICE_GROUP_RELEASE)."""
+    event behind the whole launch (ZT_CHOICE_GROUP_RELEASE).  tppr_cus > 0: CU-masked streams, where the gate of a whole batch
+    this small rides inside its aggregation kernel (tests/test_launch_plan_cpu.py lists the gate form every case reaches)."""
     _capi.set_kernel_choice(_capi.CHOICE_GROUP_RELEASE, release)
     try:
-        _grouped_launches_match_sequential(group, look, ragged)
+        _grouped_launches_match_sequential(group, look, ragged, tppr_cus)
     finally:
         _capi.set_kernel_choice(_capi.CHOICE_GROUP_RELEASE, 0)
 
 
-def _grouped_launches_match_sequential(group, look, ragged):
+def _grouped_launches_match_sequential(group, look, ragged, tppr_cus=0):
     name = "d100_f1"
     N, E, D, F, T, k, al, be, seed, bs, nb = I.EMBED_CASES[name]
     src, dst, neg, ts, eidx = I.make_stream("general", N, E, seed)
@@ -352,7 +356,7 @@ def _grouped_launches_match_sequential(group, look, ragged):
     for mode in ("seq", "grouped", "grouped_rows"):
         tgn = build_tgn(N, E + 1, D, F, T, k, al, be, w, efeat).eval()
         if mode != "seq":
-            tgn.enable_pipeline(tppr_cus=0, max_batch=64, group=group)
+            tgn.enable_pipeline(tppr_cus=tppr_cus, max_batch=64, group=group)
         embs = []
         main = getattr(tgn, "main_stream", None) or torch.cuda.current_stream()
         with torch.cuda.stream(main):

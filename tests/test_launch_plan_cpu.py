@@ -294,3 +294,254 @@ def test_held_back_output_layers(hooks, shape, want):
     p = memory_plan(hooks, rows, D, msg, gru_choice=gc, held=held)
     got = (p["out"], p["lds_f"], p["n_src_wgs"], p["n_nb_wgs"], p["out_tiles"], p["target"], p["participants"])
     assert got == (HELD[want[0]],) + want[1:]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# One step of the pipeline (zt::pipeline_step_plan / zt::pipeline_group_plan, csrc/pipeline.hip; through the test hooks
+# zt_test_step_plan / zt_test_group_plan).  Every gate form releases the same rows, so the GPU suite cannot tell a step that took
+# the wrong one, or that added a packet; this table can.  Each row is what the step did before the choice moved into one
+# function, read off the predicates of zt_pipeline_step_ahead / make_group as they were (whole = rows [0, 3B); n = row_hi - row_lo):
+#   this member's gate: carried  = its slot is released by member and its bit of Slot::tail_gated is set: nothing is enqueued
+#                       inside   = by member, masked and whole and 0 < n <= 2048 and no avg_topk: offered to embed_ex
+#                       front    = by member otherwise: k_member_gate in front of the aggregation
+#                                  (inside / front: behind the slot's `filled` unless the slot was waited for already)
+#                       event    = not by member (a group of one, pruning, the release by launch, by launch-full): the main
+#                                  stream waits for the launch's event unless the slot was waited for already
+#   gather   = streaming and not whole;  k_avg_topk = avg_topk and whole;  scored = n > 0 and scoring and whole;
+#   measured = scored and metrics;  late zt_project_memory = proj_table and no padded W_m yet;  exchange = one is attached
+#   the GRU update is the main stream's last item = not scored, no late zt_project_memory, no exchange
+#   tail offer = that, and whole and n > 0 and not ZT_RELEASE_MEMBER_FRONT and a valid batch follows whose slot exists, is by
+#                member and launched, whose bit is not set yet and which does not ride inside ITS aggregation (masked and
+#                3 next_B <= 2048 and no avg_topk); behind that slot's `filled` unless it was waited for already
+#   make_group: by member = streaming and the release is neither ZT_RELEASE_LAUNCH nor ZT_RELEASE_LAUNCH_FULL (a slot is then
+#                released by member where it holds more than one batch); at most min(want, 8) batches, except under
+#                ZT_RELEASE_LAUNCH with n_more <= want followers in sight: n_more - 1, at least 1; pruning: always 1
+GATE = {"carried": 0, "event": 1, "front": 2, "inside": 3}
+MEMBER, LAUNCH, LAUNCH_FULL, MEMBER_FRONT = 1, 2, 3, 4           # ZT_RELEASE_*
+STEP_KEYS = ("gate", "wait_filled", "wait_launch", "gather", "avg_topk", "scored", "measured", "gru_is_last", "tail_offer",
+             "tail_wait_filled", "late_project", "exchange")
+# the batch that follows, as the slots show it in the steady state: in a launched slot released by member, waited for
+NEXT = dict(B=1024, in_slot=True, by_member=True, launched=True, waited=True, tail_gated=False)
+
+
+def step_plan(hooks, streaming=True, masked=True, release=0, B=1024, rows=None, scoring=False, metrics=False, exchange=False,
+              avg_topk=False, proj_table=True, wm_ready=True, by_member=True, tail_gated=False, waited=False, nxt=None):
+    """rows: (row_lo, row_hi), None = the whole batch; nxt: the batch that follows (NEXT's keys), None = nothing in sight"""
+    lo, hi = rows if rows is not None else (0, 3 * B)
+    n = nxt or dict(B=0, in_slot=False, by_member=False, launched=False, waited=False, tail_gated=False)
+    out = (C.c_int64 * 12)(*([-1] * 12))
+    i32 = lambda v: C.c_int32(int(v))
+    rc = hooks.zt_test_step_plan(i32(streaming), i32(masked), i32(release), C.c_int64(B), C.c_int64(lo), C.c_int64(hi),
+                                 i32(scoring), i32(metrics), i32(exchange), i32(avg_topk), i32(proj_table), i32(wm_ready),
+                                 i32(by_member), i32(tail_gated), i32(waited), i32(nxt is not None), C.c_int64(n["B"]),
+                                 i32(n["in_slot"]), i32(n["by_member"]), i32(n["launched"]), i32(n["waited"]),
+                                 i32(n["tail_gated"]), out)
+    assert rc == 0
+    return dict(zip(STEP_KEYS, list(out)))
+
+
+# facts -> (gate form, wait for `filled`, wait for the launch's event).  Only a whole batch qualifies and 3 B is never 2048:
+# B = 682 is the largest whole batch of at most 2048 rows (2046), B = 683 the smallest beyond (2049)
+GATES = [
+    (dict(B=682), ("inside", 1, 0)),
+    (dict(B=683), ("front", 1, 0)),
+    (dict(B=682, masked=False), ("front", 1, 0)),
+    (dict(B=683, masked=False), ("front", 1, 0)),
+    (dict(B=200), ("inside", 1, 0)),                                          # C2
+    (dict(B=4096), ("front", 1, 0)),                                          # C5
+    (dict(B=682, avg_topk=True), ("front", 1, 0)),
+    (dict(B=682, rows=(341, 2041)), ("front", 1, 0)),                         # a shard
+    (dict(B=682, rows=(0, 2045)), ("front", 1, 0)),
+    (dict(B=682, rows=(1, 2046)), ("front", 1, 0)),
+    (dict(B=682, rows=(0, 0)), ("front", 1, 0)),                              # n_rows = 0
+    (dict(B=682, rows=(2046, 2046)), ("front", 1, 0)),
+    (dict(B=682, tail_gated=True), ("carried", 0, 0)),
+    (dict(B=4096, tail_gated=True), ("carried", 0, 0)),
+    (dict(B=4096, tail_gated=True, waited=True), ("carried", 0, 0)),
+    (dict(B=682, waited=True), ("inside", 0, 0)),
+    (dict(B=4096, waited=True), ("front", 0, 0)),
+    # the release by launch and by launch-full: make_group gives no slot by_member
+    (dict(B=682, release=LAUNCH, by_member=False), ("event", 0, 1)),
+    (dict(B=682, release=LAUNCH_FULL, by_member=False), ("event", 0, 1)),
+    (dict(B=4096, release=LAUNCH, by_member=False, waited=True), ("event", 0, 0)),
+    (dict(B=4096, release=LAUNCH_FULL, by_member=False, waited=True), ("event", 0, 0)),
+    # ZT_RELEASE_MEMBER_FRONT moves no gate of the step's own
+    (dict(B=682, release=MEMBER_FRONT), ("inside", 1, 0)),
+    (dict(B=4096, release=MEMBER_FRONT), ("front", 1, 0)),
+    (dict(B=4096, release=MEMBER), ("front", 1, 0)),
+    # a group of one (a batch nobody queried ahead, group = 1) whatever the release; the tail bit of such a slot is never read
+    (dict(B=682, by_member=False), ("event", 0, 1)),
+    (dict(B=682, by_member=False, waited=True), ("event", 0, 0)),
+    (dict(B=682, by_member=False, tail_gated=True), ("event", 0, 1)),
+    (dict(B=4096, by_member=False, masked=False), ("event", 0, 1)),
+    # pruning: one batch per query, never by member
+    (dict(B=1000, streaming=False, masked=False, by_member=False), ("event", 0, 1)),
+    (dict(B=1000, streaming=False, masked=False, by_member=False, rows=(1000, 2000)), ("event", 0, 1)),
+]
+
+
+@pytest.mark.parametrize("facts,want", GATES, ids=[str(f) for f, _ in GATES])
+def test_step_gate_form(hooks, facts, want):
+    p = step_plan(hooks, **facts)
+    assert (p["gate"], p["wait_filled"], p["wait_launch"]) == (GATE[want[0]], want[1], want[2])
+    assert p["tail_offer"] == 0 and p["tail_wait_filled"] == 0           # nothing in sight: nothing to carry
+
+
+# facts -> (gather, k_avg_topk, scored, measured, late zt_project_memory, exchange, the GRU update is the last item)
+ITEMS = [
+    (dict(), (0, 0, 0, 0, 0, 0, 1)),
+    (dict(proj_table=False, wm_ready=False), (0, 0, 0, 0, 0, 0, 1)),
+    (dict(wm_ready=False), (0, 0, 0, 0, 1, 0, 0)),                            # the first step: W_m is padded by its aggregation
+    (dict(scoring=True), (0, 0, 1, 0, 0, 0, 0)),
+    (dict(scoring=True, metrics=True), (0, 0, 1, 1, 0, 0, 0)),
+    (dict(metrics=True), (0, 0, 0, 0, 0, 0, 1)),
+    (dict(scoring=True, metrics=True, rows=(0, 3071)), (1, 0, 0, 0, 0, 0, 1)),    # a shard is not scored
+    (dict(scoring=True, rows=(0, 0)), (1, 0, 0, 0, 0, 0, 1)),
+    (dict(avg_topk=True), (0, 1, 0, 0, 0, 0, 1)),
+    (dict(avg_topk=True, rows=(0, 1536)), (1, 0, 0, 0, 0, 0, 1)),
+    (dict(exchange=True, rows=(1536, 3072)), (1, 0, 0, 0, 0, 1, 0)),
+    (dict(exchange=True), (0, 0, 0, 0, 0, 1, 0)),
+    (dict(exchange=True, wm_ready=False, rows=(0, 1536)), (1, 0, 0, 0, 1, 1, 0)),
+    (dict(streaming=False, by_member=False, rows=(0, 1536)), (0, 0, 0, 0, 0, 0, 1)),   # pruning queries the shard's rows only
+    (dict(streaming=False, by_member=False, scoring=True, metrics=True), (0, 0, 1, 1, 0, 0, 0)),
+]
+
+
+@pytest.mark.parametrize("facts,want", ITEMS, ids=[str(f) for f, _ in ITEMS])
+def test_step_items(hooks, facts, want):
+    p = step_plan(hooks, **facts)
+    got = tuple(p[k] for k in ("gather", "avg_topk", "scored", "measured", "late_project", "exchange", "gru_is_last"))
+    assert got == want
+
+
+# facts (the batch that follows: NEXT unless given) -> (the tail gate is offered, behind the next slot's `filled`)
+TAIL = [
+    (dict(), (1, 0)),                                                         # the case where it is made (C5's steady state)
+    (dict(nxt=dict(NEXT, waited=False)), (1, 1)),                             # the first member of a new group
+    (dict(B=4096, nxt=dict(NEXT, B=4096)), (1, 0)),
+    (dict(masked=False, B=20, nxt=dict(NEXT, B=20)), (1, 0)),                 # unmasked: no gate rides inside an aggregation
+    (dict(proj_table=False, wm_ready=False), (1, 0)),
+    (dict(by_member=False), (1, 0)),                                          # a batch queried alone in front of a group
+    (dict(tail_gated=True, waited=True), (1, 0)),
+    (dict(avg_topk=True, B=200, nxt=dict(NEXT, B=200)), (1, 0)),              # the statistics keep the next gate out of its aggregation
+    # each single reason that withdraws it
+    (dict(scoring=True), (0, 0)),
+    (dict(exchange=True), (0, 0)),
+    (dict(wm_ready=False), (0, 0)),                                           # proj_table without a ready W_m
+    (dict(rows=(0, 3071)), (0, 0)),                                           # a shard
+    (dict(rows=(1024, 3072)), (0, 0)),
+    (dict(rows=(0, 0)), (0, 0)),                                              # n_rows = 0
+    (dict(release=MEMBER_FRONT), (0, 0)),
+    (dict(nxt=None), (0, 0)),                                                 # no next batch
+    (dict(nxt=dict(NEXT, in_slot=False, by_member=False, launched=False, waited=False)), (0, 0)),
+    (dict(nxt=dict(NEXT, launched=False, waited=False)), (0, 0)),
+    (dict(nxt=dict(NEXT, by_member=False)), (0, 0)),
+    (dict(nxt=dict(NEXT, tail_gated=True)), (0, 0)),
+    (dict(nxt=dict(NEXT, B=682)), (0, 0)),                                    # the next batch rides inside its aggregation
+    (dict(B=200, nxt=dict(NEXT, B=200, waited=False)), (0, 0)),               # C2
+    (dict(nxt=dict(NEXT, B=683)), (1, 0)),
+    (dict(release=LAUNCH, by_member=False, nxt=dict(NEXT, by_member=False)), (0, 0)),
+]
+
+
+@pytest.mark.parametrize("facts,want", TAIL, ids=[str(f) for f, _ in TAIL])
+def test_step_tail_offer(hooks, facts, want):
+    facts = dict(facts)
+    facts.setdefault("nxt", NEXT)
+    p = step_plan(hooks, **facts)
+    assert (p["tail_offer"], p["tail_wait_filled"]) == want
+    if want[0]:
+        assert p["gru_is_last"] == 1
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("avg_topk", [False, True])
+@pytest.mark.parametrize("B", [682, 683, 1024])
+def test_tail_offer_and_next_gate_agree(hooks, masked, avg_topk, B):
+    """Step b's view of batch b + 1 against batch b + 1's own plan: the same batch gets exactly one gate.  If b offers the tail
+    gate, b + 1 (its bit set by the GRU kernel that took the offer) passes none; if b + 1 waits inside its aggregation, b offers
+    nothing; and where b offers nothing, b + 1 (bit clear) passes a gate of its own."""
+    for release in (0, MEMBER, MEMBER_FRONT):
+        for waited in (False, True):
+            b = step_plan(hooks, masked=masked, avg_topk=avg_topk, release=release, B=B, waited=True,
+                          nxt=dict(NEXT, B=B, waited=waited))
+            own = step_plan(hooks, masked=masked, avg_topk=avg_topk, release=release, B=B, waited=waited or bool(b["tail_offer"]))
+            after_offer = step_plan(hooks, masked=masked, avg_topk=avg_topk, release=release, B=B, tail_gated=True, waited=True)
+            if b["tail_offer"]:
+                assert after_offer["gate"] == GATE["carried"]
+                assert own["gate"] == GATE["front"]                  # what the offer replaces: never a gate inside the aggregation
+                assert b["tail_wait_filled"] == int(not waited)      # the wait for `filled` moves with the gate, once per group
+            if own["gate"] == GATE["inside"]:
+                assert not b["tail_offer"]
+            assert own["gate"] in (GATE["front"], GATE["inside"])    # bit clear: a gate of its own, one
+            assert bool(b["tail_offer"]) == (release != MEMBER_FRONT and own["gate"] == GATE["front"])
+
+
+def group_plan(hooks, streaming, release, want, n_more):
+    out = (C.c_int64 * 2)(-1, -1)
+    assert hooks.zt_test_group_plan(C.c_int32(int(streaming)), C.c_int32(release), C.c_int32(want), C.c_int32(n_more), out) == 0
+    return out[0], out[1]
+
+
+# ZT_RELEASE_LAUNCH: (want, n_more) -> batches the group may take (the taper: n_more - 1 where n_more <= want, at least 1)
+TAPER = {
+    (1, 0): 1, (1, 1): 1, (1, 2): 1,
+    (2, 0): 1, (2, 1): 1, (2, 2): 1, (2, 3): 2,
+    (4, 0): 1, (4, 1): 1, (4, 2): 1, (4, 3): 2, (4, 4): 3, (4, 5): 4,
+    (8, 0): 1, (8, 1): 1, (8, 2): 1, (8, 7): 6, (8, 8): 7, (8, 9): 8,
+}
+
+
+@pytest.mark.parametrize("want", [1, 2, 4, 8])
+def test_group_size_and_release(hooks, want):
+    for n_more in sorted({0, 1, 2, want - 1, want, want + 1}):
+        for release in (0, MEMBER, MEMBER_FRONT):
+            assert group_plan(hooks, True, release, want, n_more) == (1, want)           # by member: full whatever is in sight
+        assert group_plan(hooks, True, LAUNCH_FULL, want, n_more) == (0, want)           # the event without the taper
+        assert group_plan(hooks, True, LAUNCH, want, n_more) == (0, TAPER[(want, n_more)])
+        for release in (0, MEMBER, LAUNCH, LAUNCH_FULL, MEMBER_FRONT):                    # pruning: always 1, never by member
+            assert group_plan(hooks, False, release, want, n_more) == (0, 1)
+
+
+def test_group_size_is_capped(hooks):
+    """ZT_MAX_GROUP = 8 (zt_pipeline_set_group refuses more; make_group clamped all the same)"""
+    assert group_plan(hooks, True, 0, 9, 20) == (1, 8)
+    assert group_plan(hooks, True, LAUNCH, 9, 20) == (0, 8)
+    assert group_plan(hooks, True, LAUNCH, 9, 9) == (0, 8)     # (the clamp comes first: 9 followers against a want of 8)
+    assert group_plan(hooks, True, LAUNCH, 9, 8) == (0, 7)
+
+
+# The gate forms the GPU tests reach (every form by at least one): test -> configuration of its steps -> form
+REACH = [
+    # test_tail_gate_gpu.py: CU-masked, bs 1024 (a last batch of 700: 2100 rows), groups of 4 and 8
+    ("tail_gate: the library's pick, first member of a group", dict(B=1024), "front"),
+    ("tail_gate: the library's pick, a later member", dict(B=1024, tail_gated=True, waited=True), "carried"),
+    ("tail_gate: the ragged last batch", dict(B=700, tail_gated=True, waited=True), "carried"),
+    ("tail_gate: ZT_RELEASE_MEMBER_FRONT", dict(B=1024, release=MEMBER_FRONT, waited=True), "front"),
+    ("tail_gate: ZT_RELEASE_LAUNCH", dict(B=1024, release=LAUNCH, by_member=False), "event"),
+    ("tail_gate: blind (every batch alone)", dict(B=1024, by_member=False), "event"),
+    # test_grouped_tppr_launches_match_sequential: bs 20, groups of 2 .. 8; unmasked, and one CU-masked case
+    ("grouped: whole batches", dict(B=20, masked=False), "front"),
+    ("grouped: whole batches, a later member", dict(B=20, masked=False, tail_gated=True, waited=True), "carried"),
+    ("grouped: row shards", dict(B=20, masked=False, rows=(10, 55)), "front"),
+    ("grouped: ZT_RELEASE_LAUNCH", dict(B=20, masked=False, release=LAUNCH, by_member=False), "event"),
+    ("grouped: CU-masked, whole batches", dict(B=20, masked=True), "inside"),
+    ("grouped: CU-masked, row shards", dict(B=20, masked=True, rows=(10, 55)), "front"),
+    # test_pipelined_step_matches_sequential: one batch per launch
+    ("pipelined: streaming", dict(B=20, masked=False, by_member=False), "event"),
+    ("pipelined: streaming, CU-masked", dict(B=20, masked=True, by_member=False), "event"),
+    ("pipelined: pruning", dict(B=20, streaming=False, masked=False, by_member=False), "event"),
+    # test_bench_path_vs_oracle_c5_launch_shapes: CU-masked, bs 4096; groups of 2 by launch, groups of 4 by member
+    ("c5 launch shapes: groups of 2", dict(B=4096, release=LAUNCH, by_member=False), "event"),
+    ("c5 launch shapes: groups of 4, first member", dict(B=4096), "front"),
+    ("c5 launch shapes: groups of 4, a later member", dict(B=4096, tail_gated=True, waited=True), "carried"),
+]
+
+
+@pytest.mark.parametrize("name,facts,want", REACH, ids=[r[0] for r in REACH])
+def test_gate_forms_the_gpu_tests_reach(hooks, name, facts, want):
+    assert step_plan(hooks, **facts)["gate"] == GATE[want]
+
+
+def test_gpu_tests_reach_every_gate_form():
+    assert {r[2] for r in REACH} == set(GATE)

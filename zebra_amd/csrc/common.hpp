@@ -145,6 +145,45 @@ struct MetricsPlan {
 };
 // Pure host code (no HIP calls): refused for B <= 0 and beyond METRICS_MAX_B pairs
 MetricsPlan link_metrics_plan(int64_t B);
+// One step of the pipeline (pipeline.hip: pipeline_step_plan): where the wait for this batch's T-PPR rows goes and what the
+// step puts behind its GRU update.  The gate of a member: carried = the GRU kernel of the step before waited for its rows (no
+// gate here); event = the main stream waits for the launch's event; front = k_member_gate in front of the aggregation;
+// in_aggregation = the gate is offered to the aggregation kernel (embed_ex).  Every form releases the same rows: the choice is
+// speed only, and the GPU suite cannot tell one from another (tests/test_launch_plan_cpu.py).
+enum class GateForm { carried = 0, event = 1, front = 2, in_aggregation = 3 };
+struct StepFacts {
+    bool streaming, masked;            // the strategy; the T-PPR stream and the main stream own disjoint compute units
+    int release;                       // ZT_CHOICE_GROUP_RELEASE
+    long long B, row_lo, row_hi;       // the batch and the rows of it this step embeds
+    bool scoring, metrics, exchange, avg_topk, proj_table;      // what is attached to the pipeline
+    bool wm_ready;                     // the padded W_m is in the embed workspace (the GRU kernel refreshes the projected rows)
+    bool by_member, tail_gated, waited;      // this member's slot; its bit of Slot::tail_gated
+    bool have_next;                    // a valid batch follows; the rest describes it
+    long long next_B;
+    bool next_in_slot, next_by_member, next_launched, next_waited, next_tail_gated;
+};
+struct StepPlan {
+    GateForm gate;
+    bool wait_filled;                  // front / in_aggregation: the main stream waits for the slot's `filled` first (once per group)
+    bool wait_launch;                  // event: ... for the launch's event (once per launch)
+    bool gather;                       // a shard's rows of a streaming launch are brought together
+    bool avg_topk;                     // k_avg_topk runs
+    bool scored, measured;
+    bool gru_is_last;                  // the GRU update is the last thing the step puts on the main stream
+    bool tail_offer;                   // the next member's gate is offered to the GRU kernel's tail ...
+    bool tail_wait_filled;             // ... behind the next slot's `filled`
+    bool late_project;                 // zt_project_memory behind the GRU update (no padded W_m yet)
+    bool exchange;
+};
+// Pure host code (no HIP calls, no pointer of the pipeline)
+StepPlan pipeline_step_plan(const StepFacts &f);
+// A launch group (pipeline.hip: make_group): released by member or by the launch's event, and how many batches it may take.
+// want: zt_pipeline_set_group; n_more: the batches in sight behind the first
+struct GroupPlan {
+    bool by_member;
+    int limit;
+};
+GroupPlan pipeline_group_plan(bool streaming, int release, int want, int n_more);
 // zt_link_metrics with a second destination: row (or NULL) receives the batch's three values whatever `accumulate` does to out
 // (the metrics tail of the native step, pipeline.hip: the running sum and the per-batch table from one launch)
 int link_metrics_launch(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int accumulate, double *row_dev,

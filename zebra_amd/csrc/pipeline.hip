@@ -20,7 +20,7 @@
 // group.  The caller shows the batches that follow (zt_pipeline_step_ahead); with fewer than 3 * group of
 // them in sight the groups simply come out smaller.  The pruning strategy has no state to carry: group = 1.
 //
-// RELEASE BY MEMBER (round 6).  The aggregation of a group's batch b needs batch b's T-PPR rows, not the end of the launch
+// RELEASE BY MEMBER.  The aggregation of a group's batch b needs batch b's T-PPR rows, not the end of the launch
 // that wrote them: k_stream counts, per member of the group, the (edge, model) tasks whose rows are out (write-through
 // stores; Slot::mdone), and the main stream passes a one-wave gate kernel (k_member_gate: bounded wait, ZT_ERR_TIMEOUT to the
 // status word and the pipeline's latch) instead of waiting for the launch's event.  So the main stream follows the T-PPR
@@ -45,7 +45,7 @@ struct zt_pipeline {
     hipStream_t side, main_s, plan_s;
     zt::embed_out_deferred out_gru;     // the output layers of the step at hand, held back for k_out_gru (memory_update.hip)
     hipStream_t msg_s;         // the message build of the current batch, beside its aggregation (reads the memory tables only)
-    hipEvent_t step_begin, msgs_done;
+    hipEvent_t msgs_done;
     int group;                 // batches per T-PPR launch (streaming)
     bool masked;               // the T-PPR stream and the main stream own disjoint compute units (zt_pipeline_create: tppr_cus > 0)
     struct Slot {
@@ -79,8 +79,7 @@ struct zt_pipeline {
     float *sh_od, *sh_ow;
     bool embed_ready, gru_ready;
     int32_t cell;              // zt_pipeline_set_cell: ZT_CELL_GRU (0, as created) or ZT_CELL_RNN
-    hipEvent_t entry;          // main stream at the moment a group is staged: the batches' tensors are written by then
-    bool entry_recorded;       // ... recorded in the step call under way (only the calls that stage a group need it)
+    hipEvent_t entry;          // main stream when a step call begins: everything the caller enqueued before it (the batches' tensors)
     float *avg_topk;           // zt_pipeline_set_stats: mean row sum of model 0's weights over [src | dst] (or NULL)
     // zt_pipeline_set_scoring: the link scorer behind the aggregation of every whole-batch step (or off)
     // On the main stream: on a stream of its own (measured: C5 0.421 instead of 0.41 ms/step, C4 0.256 instead of 0.208) it
@@ -109,6 +108,72 @@ struct zt_pipeline {
     int *latch_host, *latch_dev;
     int tail_gates;            // steps whose GRU kernel carried the next batch's gate (zt_pipeline_tail_gates)
 };
+
+// ---- the plans: what a step and a launch group do, decided from plain facts (no HIP call, no pointer of the pipeline;
+// tests/test_launch_plan_cpu.py pins both through zt_test_step_plan / zt_test_group_plan) ----
+
+// Released by member (the library's pick) the main stream follows the T-PPR stream at a distance of one batch whatever the
+// group's size, so a group is as large as asked.  Released by the launch's event the aggregation of a group's FIRST batch
+// waits for the whole launch, and after the last launch of a region the main stream still has every batch of it to
+// aggregate: where the view ahead ends the groups taper -- with n_more followers in sight a group takes at most n_more - 1
+// along, the last three batches of a region are queried one by one, and a full group needs want + 1 followers in sight
+// (synth.pipeline_look).  ZT_RELEASE_LAUNCH_FULL: the event without the taper.
+GroupPlan zt::pipeline_group_plan(bool streaming, int release, int want, int n_more)
+{
+    if (!streaming) return {false, 1};               // the pruning strategy has no state to carry from batch to batch
+    if (want > MAX_GROUP) want = MAX_GROUP;
+    if (release == ZT_RELEASE_LAUNCH && n_more <= want) want = n_more >= 2 ? n_more - 1 : 1;
+    return {release != ZT_RELEASE_LAUNCH && release != ZT_RELEASE_LAUNCH_FULL, want};
+}
+
+// Whether the gate of a member whose step embeds n_rows rows may ride inside its aggregation kernel.  Small whole batches: their
+// steps are bound by the main stream, the gate is open when the kernel arrives, and a kernel of its own in front would be a
+// packet of every step.  Only where the T-PPR stream has compute units of its own: a persistent aggregation kernel that waits on
+// EVERY compute unit of an unmasked device, registers full, would keep out the very launch it waits for.  Large batches keep the
+// one-wave kernel in front: a resident aggregation kernel that waits leaves the next group's prepass the T-PPR stream's
+// compute units only ("The step as one call").  The statistics kernel reads the rows first: the gate goes in front.
+static bool gate_in_aggregation(bool masked, bool avg_topk, bool whole, long long n_rows)
+{
+    return masked && whole && n_rows > 0 && n_rows <= 2048 && !avg_topk;
+}
+
+// embed_impl (aggregate.hip) still turns an offered gate into a front kernel where its own plan picks an aggregation kernel
+// that cannot wait, and gru_update_ex (memory_update.hip) answers whether the GRU kernel it launched carried the tail gate: both
+// depend on those files' plans and stay there.
+StepPlan zt::pipeline_step_plan(const StepFacts &f)
+{
+    const long long n_rows = f.row_hi - f.row_lo;
+    const bool whole = f.row_lo == 0 && f.row_hi == 3 * f.B;
+    StepPlan s = {};
+    if (!f.by_member) {
+        s.gate = GateForm::event;                    // a group of one, the pruning strategy, the release by launch
+        s.wait_launch = !f.waited;
+    } else if (f.tail_gated) {
+        s.gate = GateForm::carried;
+    } else {
+        // The counters are zeroed by the group's staging kernel, on another stream, and what the slot's previous group left there
+        // IS a full count: the gate must not look before `filled` (recorded behind the staging and the plan), once per group.
+        s.gate = gate_in_aggregation(f.masked, f.avg_topk, whole, n_rows) ? GateForm::in_aggregation : GateForm::front;
+        s.wait_filled = !f.waited;
+    }
+    s.gather = f.streaming && !whole;                // streaming T-PPR emits all 3B rows of every model
+    s.avg_topk = f.avg_topk && whole;
+    s.scored = n_rows > 0 && f.scoring && whole;
+    s.measured = s.scored && f.metrics;
+    s.late_project = f.proj_table && !f.wm_ready;    // (else the refresh of the projected rows rides inside the GRU kernel)
+    s.exchange = f.exchange;
+    s.gru_is_last = !s.scored && !s.late_project && !s.exchange;
+    // The tail offer: the wait for the NEXT member's rows at the tail of this step's GRU kernel, where that kernel is the last
+    // thing the step puts on the main stream and the next member would otherwise pass a gate kernel of its own.  Only a step
+    // that embeds its whole batch offers it: the batch that follows is then embedded whole too (callers shard every batch
+    // alike), and its 3 next_B rows are what the predicate above is asked about -- a member that waits inside its aggregation
+    // has nothing to carry.  ZT_RELEASE_MEMBER_FRONT keeps every gate in front of its own step (validation).
+    s.tail_offer = s.gru_is_last && whole && n_rows > 0 && f.release != ZT_RELEASE_MEMBER_FRONT && f.have_next && f.next_in_slot &&
+                   f.next_by_member && f.next_launched && !f.next_tail_gated &&
+                   !gate_in_aggregation(f.masked, f.avg_topk, true, 3 * f.next_B);
+    s.tail_wait_filled = s.tail_offer && !f.next_waited;
+    return s;
+}
 
 namespace {
 
@@ -173,11 +238,34 @@ bool valid_batch(const zt_pipeline *p, const zt_batch *b)
     return b != nullptr && b->src && b->dst && b->neg && b->ts && b->eidx && b->B > 0 && b->B <= p->d.max_B;
 }
 
-// A new group from `first` and up to want - 1 of the batches that follow it (equal sizes, the last may be shorter;
+using Slot = zt_pipeline::Slot;
+
+// `st` waits for `ev` unless it is complete already: no wait packet for an event recorded steps ago (~5 us of
+// command-processor time each)
+int wait_unless_complete(hipStream_t st, hipEvent_t ev)
+{
+    if (hipEventQuery(ev) != hipSuccess) { (void)hipGetLastError(); ZT_HIP(hipStreamWaitEvent(st, ev, 0)); }
+    return ZT_OK;
+}
+
+// member j's block inside a slot: its ids ([src | dst | neg] of that batch) and its part of the four output arrays
+struct MemberRows {
+    const int32_t *nodes, *on, *oe;
+    const float *od, *ow;
+};
+MemberRows member_rows(const zt_pipeline *p, const Slot &s, int j)
+{
+    size_t mo = 0;
+    int64_t off = 0;
+    for (int q = 0; q < j; ++q) { mo += (size_t)p->d.M * 3 * s.B[q] * p->d.k; off += s.B[q]; }
+    return {s.nodes_m + 3 * off, s.on + mo, s.oe + mo, s.od + mo, s.ow + mo};
+}
+
+// A new group from `first` and up to gp.limit - 1 of the batches that follow it (equal sizes, the last may be shorter;
 // one T-PPR launch must cover it), staged on stream `st` once the slot's previous user is done.
 // record = false: the caller records `filled` itself (behind the prepass it enqueues after the copy).
-int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int n_more, int want, hipStream_t st,
-               zt_pipeline::Slot **out, bool record)
+int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int n_more, const GroupPlan &gp, hipStream_t st,
+               Slot **out, bool record)
 {
     // a slot whose group is used up, else the next in turn (its `consumed` event orders the reuse)
     int pick = -1;
@@ -201,7 +289,7 @@ int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int 
         }
     }
     p->next_slot = (pick + 1) % 3;
-    zt_pipeline::Slot &s = p->slot[pick];
+    Slot &s = p->slot[pick];
     GroupPtrs g;
     memset(&g, 0, sizeof(g));
     auto add = [&](const zt_batch *b) {
@@ -209,18 +297,7 @@ int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int 
         g.B[g.n] = b->B; g.off[g.n] = g.Btot; g.Btot += b->B; ++g.n;
     };
     add(first);
-    if (want > MAX_GROUP) want = MAX_GROUP;
-    // Leave followers in sight: the aggregation of a group's FIRST batch waits for the whole launch, and after the LAST
-    // launch of a stream (or of a timed region) the main stream still has every batch of that launch to aggregate.  So
-    // where the view ahead ends the groups taper -- with n_more followers in sight a group takes at most n_more - 1 of
-    // them along: the last THREE batches of a region are queried one by one (round 4; two before: the driver's 20-step
-    // run ended with a two-batch launch and two aggregations behind it) and the aggregation of each runs beside the update
-    // of the next.  A full group needs want + 1 followers in sight (synth.pipeline_look).
-    // (round 6: with the batches of a launch released one by one -- see the top of the file -- neither holds: no taper)
-    const int release = zt::kernel_choice(ZT_CHOICE_GROUP_RELEASE);
-    const bool by_member = streaming && release != ZT_RELEASE_LAUNCH && release != ZT_RELEASE_LAUNCH_FULL;
-    if (!by_member && release != ZT_RELEASE_LAUNCH_FULL && n_more <= want) want = n_more >= 2 ? n_more - 1 : 1;
-    for (int q = 0; streaming && q < n_more && g.n < want; ++q) {
+    for (int q = 0; q < n_more && g.n < gp.limit; ++q) {
         const zt_batch *b = more + q;
         // members are equally long, except that the last one may be shorter; everything fits one launch and the slot
         if (!valid_batch(p, b) || g.B[g.n - 1] != first->B || b->B > first->B || g.Btot + b->B > TPPR_MAX_LAUNCH ||
@@ -231,19 +308,10 @@ int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int 
     if (s.used) ZT_HIP(hipStreamWaitEvent(st, s.consumed, 0));
     // (released by member, `consumed` says that every batch's rows were written and read -- not that the launch that wrote
     //  them has ended: its last waves may still be on their way out.  The slot's ids and counters are not touched before it has.)
-    if (s.used && s.by_member && s.launched && hipEventQuery(s.ready_ev) != hipSuccess) {
-        (void)hipGetLastError();
-        ZT_HIP(hipStreamWaitEvent(st, s.ready_ev, 0));
-    }
+    if (s.used && s.by_member && s.launched) { const int rc = wait_unless_complete(st, s.ready_ev); if (rc != ZT_OK) return rc; }
     // the batches' tensors may have been produced on the caller's stream just before this call (the main stream is
-    // ordered behind it): the staging copy must not read them earlier
-    // (`entry` was recorded when the step call began -- BEFORE the main stream was told to wait for the current group's
-    //  T-PPR update: recorded here, behind that wait, it held the staging and the plan of the NEXT groups back until the
-    //  current update was done; a quarter of a millisecond at the start of a timed region)
-    if (st != p->main_s) {
-        if (!p->entry_recorded) { ZT_HIP(hipEventRecord(p->entry, p->main_s)); p->entry_recorded = true; }
-        ZT_HIP(hipStreamWaitEvent(st, p->entry, 0));
-    }
+    // ordered behind it): the staging copy must not read them earlier than `entry`, which every step records first
+    ZT_HIP(hipStreamWaitEvent(st, p->entry, 0));
     k_stage_group<<<(unsigned)((g.Btot + 255) / 256), 256, 0, st>>>(g, s.nodes, s.nodes_m, s.ts,
                                                                      reinterpret_cast<long long *>(s.eidx), streaming ? 0 : 1, s.mdone);
     ZT_LAUNCH_CHECK();
@@ -254,26 +322,41 @@ int make_group(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int 
     s.od = reinterpret_cast<float *>(s.buf + 2 * per); s.ow = reinterpret_cast<float *>(s.buf + 3 * per);
     for (int j = 0; j < g.n; ++j) { s.key[j] = g.eidx[j]; s.B[j] = g.B[j]; }
     s.n = g.n; s.n_done = 0; s.Btot = g.Btot; s.token = 0; s.launched = false; s.used = true; s.waited = false;
-    s.by_member = by_member && g.n > 1;
+    s.by_member = gp.by_member && g.n > 1;
     s.tail_gated = 0u;
     s.q_lo = 0; s.q_hi = 0;
     *out = &s;
     return ZT_OK;
 }
 
+// A group that no earlier step has seen, staged on the plan stream; streaming: its dependency prepass follows the staging
+// copy there (beside the current batch's update, not behind it on the T-PPR stream) and `filled` follows both.
+int stage_group_ahead(zt_pipeline *p, const zt_batch *first, const zt_batch *more, int n_more, int release, Slot **out)
+{
+    const bool streaming = p->d.tppr != nullptr;
+    int rc = make_group(p, first, more, n_more, pipeline_group_plan(streaming, release, p->group, n_more), p->plan_s, out, !streaming);
+    if (rc != ZT_OK || !streaming) return rc;
+    Slot *n = *out;
+    rc = zt_tppr_plan(p->d.tppr, n->nodes, n->eidx, n->Btot, 3, -1, &n->token, p->plan_s);
+    const hipError_t e = hipEventRecord(n->filled, p->plan_s);     // (a plan that failed too: whoever waits for the slot goes on)
+    if (rc != ZT_OK) return rc;
+    ZT_HIP(e);
+    return ZT_OK;
+}
+
 // the T-PPR query of the slot's group on the side stream; rows [row_lo, row_hi) only for the pruning strategy
-int launch_tppr(zt_pipeline *p, zt_pipeline::Slot &s, int64_t row_lo, int64_t row_hi)
+int launch_tppr(zt_pipeline *p, Slot &s, int64_t row_lo, int64_t row_hi)
 {
     const zt_pipeline_desc &d = p->d;
-    // (a group staged steps ago: no wait packet in front of the query -- ~5 us of command-processor time each)
-    if (hipEventQuery(s.filled) != hipSuccess) { (void)hipGetLastError(); ZT_HIP(hipStreamWaitEvent(p->side, s.filled, 0)); }
+    int rc = wait_unless_complete(p->side, s.filled);                  // (as a rule the group was staged steps ago)
+    if (rc != ZT_OK) return rc;
     s.ready_ev = s.ready;
     if (d.tppr != nullptr) {
         // `filled` was recorded behind the prepass (when there is one): no second wait; the event the update kernel
         // records for the plan set doubles as this slot's `ready`
         hipEvent_t done = nullptr;
-        int rc = zt::tppr_stream_ex(d.tppr, s.nodes, s.ts, s.eidx, s.Btot, 3, 1, -1, s.on, s.oe, s.od, s.ow, s.token, p->side,
-                                    true, &done, s.n > 1 ? (int32_t)s.B[0] : 0, s.by_member ? s.mdone : nullptr);
+        rc = zt::tppr_stream_ex(d.tppr, s.nodes, s.ts, s.eidx, s.Btot, 3, 1, -1, s.on, s.oe, s.od, s.ow, s.token, p->side,
+                                true, &done, s.n > 1 ? (int32_t)s.B[0] : 0, s.by_member ? s.mdone : nullptr);
         if (rc != ZT_OK) return rc;
         if (s.by_member) {
             // nobody waits for this launch on the main stream; the slot's NEXT user does (make_group), and for that the plan
@@ -288,8 +371,8 @@ int launch_tppr(zt_pipeline *p, zt_pipeline::Slot &s, int64_t row_lo, int64_t ro
         // rows whose dictionary is empty are left untouched by the query (utils/util.py:185): the kernel writes them as zeros
         // (a memset in front of every query was a packet on this stream -- ~6 us of every C4 step, which this stream bounds)
         const int64_t n = row_hi - row_lo;
-        int rc = zt::pruned_topk_multi_fill(d.csr, s.nodes_m + row_lo, s.ts + row_lo, n, d.width, d.depth, d.M, d.alpha, d.beta, d.k,
-                                            s.on, s.oe, s.od, s.ow, d.status, p->side);      // every model in one walk
+        rc = zt::pruned_topk_multi_fill(d.csr, s.nodes_m + row_lo, s.ts + row_lo, n, d.width, d.depth, d.M, d.alpha, d.beta, d.k,
+                                        s.on, s.oe, s.od, s.ow, d.status, p->side);      // every model in one walk
         if (rc != ZT_OK) return rc;
     }
     ZT_HIP(hipEventRecord(s.ready, p->side));
@@ -344,7 +427,6 @@ extern "C" int zt_pipeline_create(zt_pipeline **out, const zt_pipeline_desc *des
     *p->latch_host = 0;
     ZT_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->latch_dev), p->latch_host, 0));
     p->out_gru.latch = p->latch_dev;
-    ZT_HIP(hipEventCreateWithFlags(&p->step_begin, hipEventDisableTiming | zt::sync_event_flags()));
     ZT_HIP(hipEventCreateWithFlags(&p->msgs_done, hipEventDisableTiming | zt::sync_event_flags()));
     ZT_HIP(hipEventCreateWithFlags(&p->scored[0], hipEventDisableTiming | zt::sync_event_flags()));
     ZT_HIP(hipEventCreateWithFlags(&p->scored[1], hipEventDisableTiming | zt::sync_event_flags()));
@@ -388,7 +470,7 @@ extern "C" int zt_pipeline_destroy(zt_pipeline *p)
     (void)hipStreamDestroy(p->msg_s);
     (void)hipEventDestroy(p->scored[0]); (void)hipEventDestroy(p->scored[1]);
     (void)hipEventDestroy(p->met_done[0]); (void)hipEventDestroy(p->met_done[1]);
-    (void)hipEventDestroy(p->entry); (void)hipEventDestroy(p->step_begin); (void)hipEventDestroy(p->msgs_done);
+    (void)hipEventDestroy(p->entry); (void)hipEventDestroy(p->msgs_done);
     if (p->latch_host) (void)hipHostFree(p->latch_host);
     delete p;
     return ZT_OK;
@@ -508,6 +590,274 @@ extern "C" int zt_pipeline_update(zt_pipeline *p, const zt_pipeline_desc *desc, 
     return ZT_OK;
 }
 
+namespace {
+
+// One step call under way: its arguments, its plan, what its stages hand to each other, and the stages in the order they
+// run.  The host issues every call of a step in ONE order across the four streams, and the event records depend on it: no
+// stage moves past another.
+struct Step {
+    zt_pipeline *p;
+    const zt_pipeline_desc &d;
+    const zt_batch *cur, *ahead;
+    int n_ahead;
+    int64_t row_lo, row_hi, pos_lo, pos_hi;
+    float *out;
+    int64_t B, n_rows;
+    int release;               // ZT_CHOICE_GROUP_RELEASE, read once per call
+    StepFacts f;
+    StepPlan plan;
+    Slot *s;                   // the slot that holds `cur`, as its member j
+    int j;
+    Slot *nxt;                 // the slot that holds ahead[0], as its member jn (or NULL)
+    int jn;
+    zt::member_gate gate;      // this member's gate where it is offered to the aggregation kernel (else word = NULL)
+    MemberRows r;              // this member's ids and T-PPR rows (a shard: the compact copies)
+    int msg_dim;
+    int32_t *gru_cnt, *gru_rows;      // the GRU workspace's counter and row list: the message build fills them
+    const float *wm_p;         // the padded W_m in the embed workspace, once it is there (else NULL)
+
+    // the facts about the pipeline, the call and this member's slot (those about the batch that follows: look_at_next_member)
+    void look()
+    {
+        B = cur->B; n_rows = row_hi - row_lo;
+        release = zt::kernel_choice(ZT_CHOICE_GROUP_RELEASE);
+        msg_dim = 2 * d.D + d.F + d.T;
+        gru_cnt = reinterpret_cast<int32_t *>(d.gru_ws);
+        gru_rows = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d.gru_ws) + zt_gru_rows_offset(d.D, msg_dim));
+        wm_p = (d.proj_table != nullptr && p->embed_ready) ? zt::embed_wm_ptr(d.embed_ws, 3 * d.max_B, d.D, d.F, d.T, d.M, d.k) : nullptr;
+        s = find_slot(p, cur, &j);
+        // (pruning: a query made ahead covers the rows derived for it from the step that made it; if this call asks for other
+        //  rows -- the roundings differ when 3B is not divisible by the world size and the batch sizes change -- query again:
+        //  the strategy carries no state)
+        if (d.csr != nullptr && s != nullptr && s->launched && (s->q_lo != row_lo || s->q_hi != row_hi)) s->launched = false;
+        f.streaming = d.tppr != nullptr; f.masked = p->masked; f.release = release;
+        f.B = B; f.row_lo = row_lo; f.row_hi = row_hi;
+        f.scoring = p->aff_on; f.metrics = p->met_sum != nullptr; f.exchange = p->xchg != nullptr;
+        f.avg_topk = p->avg_topk != nullptr; f.proj_table = d.proj_table != nullptr; f.wm_ready = wm_p != nullptr;
+        // (a batch nobody has queried ahead gets a group of its own, released by its launch's event; a launch made in this
+        //  call has not been waited for)
+        if (s != nullptr) {
+            f.by_member = s->by_member; f.tail_gated = (s->tail_gated & (1u << j)) != 0u;
+            f.waited = s->launched && s->waited;
+        }
+    }
+
+    // ---- this batch's T-PPR query: made ahead by an earlier step, or now ----
+    int query_this_batch()
+    {
+        if (s == nullptr) {
+            // a batch nobody has queried ahead is queried ALONE: the aggregation waits for this launch, and a group would
+            // make it wait for the followers' updates as well; they form the next group, which runs beside this batch
+            const int rc = make_group(p, cur, ahead, n_ahead, pipeline_group_plan(f.streaming, release, 1, n_ahead), p->side, &s, true);
+            if (rc != ZT_OK) return rc;
+            j = 0;
+        }
+        return s->launched ? ZT_OK : launch_tppr(p, *s, row_lo, row_hi);
+    }
+
+    // ---- this member's rows, not the launch: the gate in the form the plan chose ----
+    int pass_gate()
+    {
+        gate = {nullptr, 0, p->latch_dev, d.status};
+        if (plan.gate == GateForm::carried) return ZT_OK;    // the GRU kernel of the previous step waited for these rows at its tail
+        if (plan.gate == GateForm::event) {
+            if (plan.wait_launch) { ZT_HIP(hipStreamWaitEvent(p->main_s, s->ready_ev, 0)); s->waited = true; }
+            return ZT_OK;
+        }
+        if (plan.wait_filled) {
+            const int rc = wait_unless_complete(p->main_s, s->filled);
+            if (rc != ZT_OK) return rc;
+            s->waited = true;
+        }
+        gate.word = s->mdone + j; gate.target = (int32_t)(s->B[j] * d.M);      // one count per (edge, model) task of k_stream
+        if (plan.gate == GateForm::in_aggregation) return ZT_OK;      // embed_ex takes it along
+        const int rc = zt::member_gate_launch(gate, d.status, p->main_s);
+        gate.word = nullptr;
+        return rc;
+    }
+
+    // ---- the group after this one is queried beside this group's aggregation; the one after that is planned ----
+    int query_ahead()
+    {
+        int a = s->n - 1 - j;                     // ahead[0 .. a) are the rest of this group
+        if (a >= n_ahead || !valid_batch(p, ahead + a)) return ZT_OK;
+        int jq = 0;
+        Slot *n = find_slot(p, ahead + a, &jq);
+        if (n == nullptr) {                       // not planned by an earlier step (the start of a stream)
+            const int rc = stage_group_ahead(p, ahead + a, ahead + a + 1, n_ahead - a - 1, release, &n);
+            if (rc != ZT_OK) return rc;
+        }
+        if (!n->launched) {
+            // the shard of a LATER batch is the same fraction of its rows (callers shard every batch alike)
+            const int64_t Bn = n->B[0];
+            const int rc = launch_tppr(p, *n, Bn == B ? row_lo : (row_lo * 3 * Bn) / (3 * B), Bn == B ? row_hi : (row_hi * 3 * Bn) / (3 * B));
+            if (rc != ZT_OK) return rc;
+        }
+        a += n->n - jq;                           // ahead[a] now follows that group
+        Slot *q = nullptr;
+        if (a < n_ahead && valid_batch(p, ahead + a) && find_slot(p, ahead + a, &jq) == nullptr)
+            return stage_group_ahead(p, ahead + a, ahead + a + 1, n_ahead - a - 1, release, &q);
+        return ZT_OK;
+    }
+
+    // what the slots say about the batch that follows, now that the groups ahead are staged and launched
+    void look_at_next_member()
+    {
+        f.waited = s->waited;
+        f.have_next = n_ahead > 0 && valid_batch(p, ahead);
+        nxt = f.have_next ? find_slot(p, ahead, &jn) : nullptr;
+        f.next_B = f.have_next ? ahead->B : 0;
+        f.next_in_slot = nxt != nullptr;
+        if (nxt == nullptr) return;
+        f.next_by_member = nxt->by_member; f.next_launched = nxt->launched; f.next_waited = nxt->waited;
+        f.next_tail_gated = (nxt->tail_gated & (1u << jn)) != 0u;
+    }
+
+    // ---- P2 (first half): the rows [row_lo, row_hi) of member j, and the statistics over them ----
+    int gather_rows()
+    {
+        r = member_rows(p, *s, j);
+        if (plan.gather) {                        // bring this shard's rows of every model together
+            const size_t w = (size_t)n_rows * d.k * 4, pitch = (size_t)3 * B * d.k * 4, o2 = (size_t)row_lo * d.k;
+            ZT_HIP(hipMemcpy2DAsync(p->sh_on, w, r.on + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
+            ZT_HIP(hipMemcpy2DAsync(p->sh_oe, w, r.oe + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
+            ZT_HIP(hipMemcpy2DAsync(p->sh_od, w, r.od + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
+            ZT_HIP(hipMemcpy2DAsync(p->sh_ow, w, r.ow + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
+            r.on = p->sh_on; r.oe = p->sh_oe; r.od = p->sh_od; r.ow = p->sh_ow;
+        }
+        if (plan.avg_topk) {
+            k_avg_topk<<<1, 256, 0, p->main_s>>>(r.ow, 2 * B, d.k, p->avg_topk);
+            ZT_LAUNCH_CHECK();
+        }
+        return ZT_OK;
+    }
+
+    // ---- P3 (first half), on a stream of its own: the last messages of the endpoints at positions [pos_lo, pos_hi).  They
+    // read the memory tables as everything enqueued on the main stream before this call leaves them (the previous batch's GRU,
+    // a caller's row exchange: `entry`) and nothing the aggregation writes; the GRU update waits for them. ----
+    int build_messages()
+    {
+        ZT_HIP(hipStreamWaitEvent(p->msg_s, p->entry, 0));
+        // Every endpoint of the batch gets a message here and is updated by the GRU below: in this protocol (eval steps, entered
+        // with no flag pending -- step_device flushes first) "flagged among the batch's endpoints after the store" IS the list
+        // of winners the message kernel already makes.  So the kernel hands its list to the GRU directly (the GRU workspace's
+        // row list and counter; k_last_pos zeroes the counter) and sets no flag: Memory.clear_messages for the same ids would
+        // clear it again -- and the compaction kernel (k_select_flagged) leaves the step.
+        bool cnt_zeroed = false;
+        const int rc = zt::store_messages_ex(d.memory, d.last_update, d.efeat, d.ew.time_w, d.num_nodes, d.num_edges, d.D, d.F, d.T,
+                                             cur->src, cur->dst, cur->ts, cur->eidx, B, pos_lo, pos_hi, d.messages, d.msg_ts, d.flags,
+                                             d.scratch, gru_rows, gru_cnt, d.status, gru_cnt, p->msg_s, &cnt_zeroed, false);
+        if (rc != ZT_OK) return rc;
+        if (!cnt_zeroed) ZT_HIP(hipMemsetAsync(gru_cnt, 0, sizeof(int), p->msg_s));       // (B == 0 cannot get here; belt and braces)
+        ZT_HIP(hipEventRecord(p->msgs_done, p->msg_s));
+        return ZT_OK;
+    }
+
+    // ---- P2: aggregate.  The wait for the message build sits between the aggregation and the output layers -- the messages
+    // are ready long before the aggregation ends -- so that the GRU follows the output layers without a packet in between.
+    // The output layers are held back: gru_update_ex launches them in ONE kernel with the GRU update where both take their
+    // tiled forms (k_out_gru), otherwise in front of it. ----
+    int aggregate()
+    {
+        if (n_rows == 0) return ZT_OK;
+        const int rc = zt::embed_ex(d.memory, d.efeat, d.num_nodes, d.num_edges, d.D, d.F, d.T, r.nodes + row_lo, n_rows, d.M, d.k, r.on,
+                                    r.oe, r.od, r.ow, &d.ew, out, d.embed_ws, d.status, d.proj_table, p->embed_ready ? 1 : 0, p->main_s,
+                                    p->msgs_done, &p->out_gru, gate.word ? &gate : nullptr);
+        if (rc == ZT_OK) p->embed_ready = true;
+        return rc;
+    }
+
+    // ---- P3: the GRU update over the messages built beside the aggregation; the refresh of the projected rows rides inside
+    // the GRU kernel once the padded W_m is in the embed workspace.  Where the plan offers it, one thread of the kernel's first
+    // workgroup waits for the NEXT member's rows once it is through with its own tile, and the next step finds its bit set.
+    // The kernel boundary between this GRU and the next aggregation stays, so the rows are read by a kernel that starts after
+    // the count was seen, as behind k_member_gate.  (The price: the next step's `entry` record lies behind this wait.) ----
+    int update_memory()
+    {
+        if (n_rows == 0) ZT_HIP(hipStreamWaitEvent(p->main_s, p->msgs_done, 0));      // (no aggregation waited for the messages)
+        zt::member_gate tail = {nullptr, 0, p->latch_dev, d.status};
+        if (plan.tail_offer) {
+            // (a new group's counters, as in front of its own gate: behind `filled`, once per group -- the very wait the next
+            //  step would otherwise make; as a rule the event is complete and asking is enough)
+            if (plan.tail_wait_filled) {
+                const int rc = wait_unless_complete(p->main_s, nxt->filled);
+                if (rc != ZT_OK) return rc;
+                nxt->waited = true;
+            }
+            tail.word = nxt->mdone + jn; tail.target = (int32_t)(nxt->B[jn] * d.M);
+        }
+        bool carried = false;
+        const int rc = zt::gru_update_ex(d.memory, d.last_update, d.messages, d.msg_ts, d.flags, d.num_nodes, d.D, msg_dim, r.nodes, 2 * B,
+                                         nullptr, &d.gw, d.gru_ws, p->gru_ready ? 1 : 0, wm_p, wm_p ? d.proj_table : nullptr, p->main_s,
+                                         true, true, n_rows > 0 ? &p->out_gru : nullptr, p->cell, tail.word ? &tail : nullptr, &carried);
+        if (rc != ZT_OK) return rc;
+        if (carried) { nxt->tail_gated |= 1u << jn; p->tail_gates++; }        // (only a gate that was offered is carried)
+        p->gru_ready = true;
+        return ZT_OK;
+    }
+
+    // ---- compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written; AP / AUC / accuracy of
+    // these 2B probabilities beside the next step (message stream) ----
+    int score_and_measure()
+    {
+        if (!plan.scored) return ZT_OK;
+        const int par = p->score_n & 1;
+        float *prob = p->prob + (size_t)par * 2 * d.max_B;
+        if (p->met_pending[par]) {               // the metrics kernel of two steps ago still reads this half
+            ZT_HIP(hipStreamWaitEvent(p->main_s, p->met_done[par], 0));
+            p->met_pending[par] = false;
+        }
+        int rc = zt_affinity(out, B, d.D * (d.M + 1), &p->aff, prob, p->aff_ws, d.max_B, p->aff_ready ? 1 : 0, p->main_s);
+        if (rc != ZT_OK) return rc;
+        ZT_HIP(hipEventRecord(p->scored[par], p->main_s));
+        p->aff_ready = true;
+        p->score_n++;
+        p->score_B = B;
+        if (!plan.measured) return ZT_OK;
+        ZT_HIP(hipStreamWaitEvent(p->msg_s, p->scored[par], 0));
+        rc = zt::link_metrics_launch(prob, prob + B, B, p->met_sum, 1, p->met_rows ? p->met_rows + 3 * p->met_n : nullptr, p->msg_s);
+        if (rc != ZT_OK) return rc;
+        ZT_HIP(hipEventRecord(p->met_done[par], p->msg_s));
+        p->met_pending[par] = true;
+        p->met_last = par;
+        p->met_n++;
+        return ZT_OK;
+    }
+
+    // ---- the projected rows of the updated nodes where the GRU kernel could not refresh them; multi-GPU: the rows every
+    // rank's GRU update rewrote, all-gathered and scattered into the local tables, and the projected table follows the rows
+    // the other ranks wrote (this rank's own were refreshed by its GRU kernel) ----
+    int refresh_and_exchange()
+    {
+        int rc = ZT_OK;
+        if (plan.late_project)
+            rc = zt_project_memory(d.memory, d.num_nodes, d.D, d.F, d.T, &d.ew, 1, gru_rows, gru_cnt, 2 * B, d.proj_table, d.embed_ws,
+                                   3 * d.max_B, d.M, d.k, p->main_s);
+        if (rc != ZT_OK || !plan.exchange) return rc;
+        const int32_t *xids = nullptr;
+        int64_t n_x = 0;
+        rc = zt::exchange_step(p->xchg, gru_rows, gru_cnt, p->main_s, &xids, &n_x);
+        if (rc != ZT_OK || d.proj_table == nullptr) return rc;
+        rc = zt_project_memory(d.memory, d.num_nodes, d.D, d.F, d.T, &d.ew, p->embed_ready ? 1 : 0, xids, nullptr, n_x, d.proj_table,
+                               d.embed_ws, 3 * d.max_B, d.M, d.k, p->main_s);
+        if (rc == ZT_OK) p->embed_ready = true;    // (a rank whose row shard was empty: the padded weights were made just now)
+        return rc;
+    }
+
+    // ---- the member is used up; with the last one the slot is free again ----
+    int retire_member()
+    {
+        s->key[j] = nullptr;
+        if (++s->n_done >= s->n) {
+            ZT_HIP(hipEventRecord(s->consumed, p->main_s));
+            s->n = 0;
+        }
+        return ZT_OK;
+    }
+};
+
+}  // namespace
+
 extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const zt_batch *ahead, int32_t n_ahead,
                                       int64_t row_lo, int64_t row_hi, int64_t pos_lo, int64_t pos_hi, float *out_emb_dev)
 {
@@ -523,260 +873,28 @@ extern "C" int zt_pipeline_step_ahead(zt_pipeline *p, const zt_batch *cur, const
                   "layers and the GRU update, memory_update.hip); that step's memory update is incomplete", st);
         return st;
     }
-    const zt_pipeline_desc &d = p->d;
-    const int64_t B = cur->B, n_rows = row_hi - row_lo;
-    const bool pruning = d.csr != nullptr;
-    const bool whole = row_lo == 0 && row_hi == 3 * B;
-    const int want = pruning ? 1 : p->group;
-    const bool scored = n_rows > 0 && p->aff_on && whole, measured = scored && p->met_sum != nullptr;
-    if (measured && p->met_rows != nullptr && p->met_n >= p->met_cap) {      // (before anything of this step is enqueued)
+    Step t = {p, p->d, cur, ahead, n_ahead, row_lo, row_hi, pos_lo, pos_hi, out_emb_dev};
+    t.look();
+    // The plan is made twice from the same facts: here for the gate and the step's own items, and again once the groups ahead
+    // are staged and launched (query_ahead) -- only then do the slots say what the tail of the GRU kernel may carry.
+    t.plan = zt::pipeline_step_plan(t.f);
+    if (t.plan.measured && p->met_rows != nullptr && p->met_n >= p->met_cap) {      // (before anything of this step is enqueued)
         set_error("zt_pipeline_step: the per-batch metrics table has %lld rows and this step is batch %lld", (long long)p->met_cap,
                   (long long)p->met_n);
         return ZT_ERR_ARG;
     }
-    // the shard of a LATER batch is the same fraction of its rows (callers shard every batch alike)
-    auto shard_of = [&](int64_t Bn, int64_t *lo, int64_t *hi) {
-        *lo = Bn == B ? row_lo : (row_lo * 3 * Bn) / (3 * B);
-        *hi = Bn == B ? row_hi : (row_hi * 3 * Bn) / (3 * B);
-    };
-    int rc, j = 0;
-    // ---- this batch's T-PPR query: made ahead by an earlier step, or now (with as many followers as allowed) ----
-    zt_pipeline::Slot *s = find_slot(p, cur, &j);
-    // `entry` = everything the caller enqueued before this call: what a group staged on another stream must wait for
-    // (make_group).  Recorded up front -- BEFORE the main stream is told to wait for the T-PPR update -- by the calls
-    // that stage groups as a rule: a batch nobody has seen, or the first member of its group (the group after next is
-    // planned then).  The other members' steps skip it, and the wait for an update the main stream has already been
-    // told to wait for: two packets less between the GRU of one batch and the aggregation of the next (~5 us of
-    // command-processor time each; round 4).  A call that stages a group after all records it late (make_group).
-    // (round 5: every step records it -- the message kernels wait for it too, where they used to wait for an event of their
-    //  own recorded BEHIND the wait for the T-PPR update: one packet less per step on the main stream, and the message build
-    //  no longer waits for an update it does not read)
+    // `entry` = everything the caller enqueued before this call: what a group staged on another stream and the message build
+    // wait for.  Recorded up front, BEFORE the main stream is told to wait for the T-PPR update: behind that wait it would
+    // hold the staging and the plan of the NEXT groups, and the message build, back until the current update was done.
     ZT_HIP(hipEventRecord(p->entry, p->main_s));
-    p->entry_recorded = true;
-    // (a batch nobody has queried ahead is queried ALONE: the aggregation waits for this launch, and a group would
-    //  make it wait for the followers' updates as well; they form the next group, which runs beside this batch)
-    if (s == nullptr) { rc = make_group(p, cur, ahead, n_ahead, 1, p->side, &s, true); if (rc != ZT_OK) return rc; j = 0; }
-    // (pruning: a query made ahead covers the rows shard_of() derived for it; if this call asks for other rows --
-    //  the roundings differ when 3B is not divisible by the world size and the batch sizes change -- query again:
-    //  the strategy carries no state)
-    if (pruning && s->launched && (s->q_lo != row_lo || s->q_hi != row_hi)) s->launched = false;
-    if (!s->launched) { rc = launch_tppr(p, *s, row_lo, row_hi); if (rc != ZT_OK) return rc; }
-    // this member's rows, not the launch: one count per (edge, model) task (k_stream's general queue).  Small batches, where
-    // the aggregation is the first reader of the rows on the main stream: the wait rides inside the aggregation kernel
-    // (embed_ex) -- their steps are bound by the main stream, the gate is open when the kernel arrives, and a kernel of its own
-    // in front would be ~13 us of every step (C2 0.083 -> 0.080 ms/step).  Large batches: a one-wave kernel here (bounded wait,
-    // ZT_ERR_TIMEOUT to the status word and the pipeline's latch: aggregate.hip, member_gate_launch).  Measured on
-    // C5 (0.296 against 0.305 ms/step at 200 steps): while the main stream waits for the T-PPR update, a persistent aggregation
-    // kernel that is already resident fills all of its compute units' registers, and the prepass kernels of the next launch
-    // group -- on a stream without a CU mask -- are left with the T-PPR stream's compute units, beside the hub chains.
-    zt::member_gate gate = {nullptr, 0, p->latch_dev, d.status};
-    if (s->by_member && (s->tail_gated & (1u << j)) != 0u) {
-        // the GRU kernel of the previous step waited for this batch's rows at its tail (below): nothing to pass here
-    } else if (s->by_member) {
-        // The counters are zeroed by the group's staging kernel, on another stream: the gate must not look at them before that
-        // kernel has run -- what is left there from the slot's previous group IS a full count.  In practice the staging is two
-        // launch groups ahead of this step; by construction it is this wait, once per group (`filled` is recorded behind the
-        // staging and the plan; the T-PPR launch that counts waits for it too).
-        if (!s->waited) {
-            if (hipEventQuery(s->filled) != hipSuccess) { (void)hipGetLastError(); ZT_HIP(hipStreamWaitEvent(p->main_s, s->filled, 0)); }
-            s->waited = true;
-        }
-        gate.word = s->mdone + j; gate.target = (int32_t)(s->B[j] * d.M);
-        // (inside the kernel only where the T-PPR stream has compute units of its own: a persistent aggregation kernel that
-        //  waits on EVERY compute unit of an unmasked device, registers full, would keep out the very launch it waits for)
-        if (!(p->masked && whole && n_rows > 0 && n_rows <= 2048 && p->avg_topk == nullptr)) {
-            rc = zt::member_gate_launch(gate, d.status, p->main_s);
-            if (rc != ZT_OK) return rc;
-            gate.word = nullptr;
-        }
-    } else if (!s->waited) { ZT_HIP(hipStreamWaitEvent(p->main_s, s->ready_ev, 0)); s->waited = true; }
-    // ---- the group after this one is queried beside this group's aggregation; the one after that is planned ----
-    int a = s->n - 1 - j;                     // ahead[0 .. a) are the rest of this group
-    if (a < n_ahead && valid_batch(p, ahead + a)) {
-        int jn = 0;
-        zt_pipeline::Slot *n = find_slot(p, ahead + a, &jn);
-        if (n == nullptr) {
-            // not planned by an earlier step (the start of a stream): its prepass goes to the plan stream all the same,
-            // beside the current batch's update, not behind it on the T-PPR stream
-            rc = make_group(p, ahead + a, ahead + a + 1, n_ahead - a - 1, want, p->plan_s, &n, pruning);
-            if (rc != ZT_OK) return rc;
-            if (!pruning) {
-                rc = zt_tppr_plan(d.tppr, n->nodes, n->eidx, n->Btot, 3, -1, &n->token, p->plan_s);
-                if (rc != ZT_OK) { (void)hipEventRecord(n->filled, p->plan_s); return rc; }
-                ZT_HIP(hipEventRecord(n->filled, p->plan_s));
-            }
-        }
-        if (!n->launched) {
-            int64_t nlo, nhi;
-            shard_of(n->B[0], &nlo, &nhi);
-            rc = launch_tppr(p, *n, nlo, nhi);
-            if (rc != ZT_OK) return rc;
-        }
-        a += n->n - jn;                       // ahead[a] now follows that group
-        if (a < n_ahead && valid_batch(p, ahead + a) && find_slot(p, ahead + a, &jn) == nullptr) {
-            zt_pipeline::Slot *q;
-            rc = make_group(p, ahead + a, ahead + a + 1, n_ahead - a - 1, want, p->plan_s, &q, pruning);   // streaming: `filled`
-            if (rc != ZT_OK) return rc;                                                              // follows the prepass
-            if (!pruning) {
-                rc = zt_tppr_plan(d.tppr, q->nodes, q->eidx, q->Btot, 3, -1, &q->token, p->plan_s);
-                if (rc != ZT_OK) { (void)hipEventRecord(q->filled, p->plan_s); return rc; }
-                ZT_HIP(hipEventRecord(q->filled, p->plan_s));
-            }
-        }
-    }
-    // ---- P2: gather + aggregate for rows [row_lo, row_hi) of member j ----
-    size_t mo = 0;                            // first element of member j's block in each output array
-    int64_t off = 0;
-    for (int q = 0; q < j; ++q) { mo += (size_t)d.M * 3 * s->B[q] * d.k; off += s->B[q]; }
-    const int32_t *nodes_cur = s->nodes_m + 3 * off;
-    const int32_t *on = s->on + mo, *oe = s->oe + mo;
-    const float *od = s->od + mo, *ow = s->ow + mo;
-    if (!pruning && !whole) {
-        // streaming T-PPR emits all 3B rows of every model: bring this shard's rows together
-        const size_t w = (size_t)n_rows * d.k * 4, pitch = (size_t)3 * B * d.k * 4, o2 = (size_t)row_lo * d.k;
-        ZT_HIP(hipMemcpy2DAsync(p->sh_on, w, on + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
-        ZT_HIP(hipMemcpy2DAsync(p->sh_oe, w, oe + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
-        ZT_HIP(hipMemcpy2DAsync(p->sh_od, w, od + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
-        ZT_HIP(hipMemcpy2DAsync(p->sh_ow, w, ow + o2, pitch, w, d.M, hipMemcpyDeviceToDevice, p->main_s));
-        on = p->sh_on; oe = p->sh_oe; od = p->sh_od; ow = p->sh_ow;
-    }
-    if (p->avg_topk != nullptr && whole) {
-        k_avg_topk<<<1, 256, 0, p->main_s>>>(ow, 2 * B, d.k, p->avg_topk);
-        ZT_LAUNCH_CHECK();
-    }
-    // ---- P3 (first half), on a stream of its own: the last messages of the endpoints at positions [pos_lo, pos_hi).  They
-    // read the memory tables as everything enqueued on the main stream so far leaves them (the previous batch's GRU, a
-    // caller's row exchange) and nothing the aggregation writes; the GRU below waits for them.
-    ZT_HIP(hipStreamWaitEvent(p->msg_s, p->entry, 0));
-    // Every endpoint of the batch gets a message here and is updated by the GRU below: in this protocol (eval steps, entered
-    // with no flag pending -- step_device flushes first) "flagged among the batch's endpoints after the store" IS the list of
-    // winners the message kernel already makes.  So the kernel hands its list to the GRU directly (the GRU workspace's row
-    // list and counter; k_last_pos zeroes the counter) and sets no flag: Memory.clear_messages for the same ids would clear
-    // it again -- and the compaction kernel (k_select_flagged) leaves the step.
-    bool cnt_zeroed = false;
-    const int msg_dim = 2 * d.D + d.F + d.T;
-    char *gws = reinterpret_cast<char *>(d.gru_ws);
-    int32_t *gru_cnt = reinterpret_cast<int32_t *>(gws);
-    int32_t *gru_rows = reinterpret_cast<int32_t *>(gws + zt_gru_rows_offset(d.D, msg_dim));
-    rc = zt::store_messages_ex(d.memory, d.last_update, d.efeat, d.ew.time_w, d.num_nodes, d.num_edges, d.D, d.F, d.T,
-                               cur->src, cur->dst, cur->ts, cur->eidx, B, pos_lo, pos_hi, d.messages, d.msg_ts, d.flags,
-                               d.scratch, gru_rows, gru_cnt, d.status, gru_cnt, p->msg_s, &cnt_zeroed, false);
-    if (rc != ZT_OK) return rc;
-    if (!cnt_zeroed) ZT_HIP(hipMemsetAsync(gru_cnt, 0, sizeof(int), p->msg_s));       // (B == 0 cannot get here; belt and braces)
-    ZT_HIP(hipEventRecord(p->msgs_done, p->msg_s));
-    const float *wm_p = (d.proj_table != nullptr && p->embed_ready) ? zt::embed_wm_ptr(d.embed_ws, 3 * d.max_B, d.D, d.F, d.T, d.M, d.k)
-                                                                     : nullptr;
-    bool msgs_waited = false;
-    if (n_rows > 0) {
-        // (the wait for the message build sits between the aggregation and the output layer -- the messages are ready long
-        //  before the aggregation ends -- so that the GRU follows the output layer without a packet in between)
-        msgs_waited = true;
-        // (the output layers are held back: gru_update_ex below launches them in ONE kernel with the GRU update where both take
-        //  their tiled forms -- k_out_gru --, otherwise in front of it)
-        rc = zt::embed_ex(d.memory, d.efeat, d.num_nodes, d.num_edges, d.D, d.F, d.T, nodes_cur + row_lo, n_rows, d.M, d.k, on, oe,
-                          od, ow, &d.ew, out_emb_dev, d.embed_ws, d.status, d.proj_table, p->embed_ready ? 1 : 0, p->main_s,
-                          msgs_waited ? p->msgs_done : nullptr, &p->out_gru, gate.word ? &gate : nullptr);
-        if (rc != ZT_OK) return rc;
-        p->embed_ready = true;
-    }
-    // ---- P3: the GRU update over the messages built beside the aggregation; the refresh of the projected rows rides
-    // inside the GRU kernel once the padded W_m is in the embed workspace ----
-    if (!msgs_waited) ZT_HIP(hipStreamWaitEvent(p->main_s, p->msgs_done, 0));
-    // THE GATE AT THE TAIL OF THE GRU (round 8).  Large batches pass the gate of the release by member as a one-wave kernel in
-    // front of the aggregation (above): ~7 us of kernel + a kernel boundary of every step of a main stream that, on C5, is level
-    // with the T-PPR stream.  Where this step's GRU kernel is the LAST thing the step puts on the main stream and the next
-    // batch's slot is launched and released by member, the wait for the NEXT batch's rows rides at the tail of that kernel
-    // instead: one thread of its first workgroup, once that thread is through with its tile -- one resident workgroup of a
-    // kernel that is running out, so (unlike a persistent aggregation kernel waiting on every compute unit) it keeps the next
-    // group's prepass out of nothing.  The next step then finds its bit set.  The kernel boundary between this GRU and the next aggregation stays, so the rows are read by a
-    // kernel that starts after the count was seen, as behind k_member_gate.
-    // The counters of a NEW group are zeroed by its staging kernel on another stream, and what the slot's previous group left
-    // there is a full count (see the gate in front): the GRU kernel is ordered behind the group's `filled` event first, once per
-    // group -- the very wait the next step would otherwise put in front of its own gate; as a rule the event is complete
-    // (staged two launch groups ahead) and asking is enough.
-    // What it costs: the NEXT step's `entry` record on the main stream now lies behind this wait, and the message stream and
-    // the staging of later groups wait for `entry` (make_group: an `entry` behind the wait for the T-PPR update once cost a
-    // quarter of a millisecond at the start of a region).  So wherever the T-PPR stream is the slower one, the next step's
-    // message build and the staging two groups ahead start one gate-wait later: round 6 saw the 20-step region lose 0.8 % to
-    // it while the steady state gained; profiles/r8/experiments/launch_head_packets_gate_ab.log has both regions.
-    // ZT_RELEASE_MEMBER_FRONT keeps every gate in front of its own step (validation).
-    zt::member_gate tail = {nullptr, 0, p->latch_dev, d.status};
-    zt_pipeline::Slot *nxt = nullptr;
-    int jn = 0;
-    const bool tail_off = zt::kernel_choice(ZT_CHOICE_GROUP_RELEASE) == ZT_RELEASE_MEMBER_FRONT;
-    const bool gru_is_last = !tail_off && whole && n_rows > 0 && !p->aff_on && p->xchg == nullptr && (d.proj_table == nullptr || wm_p != nullptr);
-    if (gru_is_last && n_ahead > 0 && valid_batch(p, ahead)) {
-        nxt = find_slot(p, ahead, &jn);
-        // (a step of a small batch on CU-masked streams passes its gate inside its aggregation kernel: nothing to carry for it)
-        const bool next_in_kernel = p->masked && 3 * ahead->B <= 2048 && p->avg_topk == nullptr;
-        if (nxt != nullptr && nxt->by_member && nxt->launched && !next_in_kernel && (nxt->tail_gated & (1u << jn)) == 0u) {
-            if (!nxt->waited) {
-                if (hipEventQuery(nxt->filled) != hipSuccess) { (void)hipGetLastError(); ZT_HIP(hipStreamWaitEvent(p->main_s, nxt->filled, 0)); }
-                nxt->waited = true;
-            }
-            tail.word = nxt->mdone + jn; tail.target = (int32_t)(nxt->B[jn] * d.M);
-        }
-    }
-    bool carried = false;
-    rc = zt::gru_update_ex(d.memory, d.last_update, d.messages, d.msg_ts, d.flags, d.num_nodes, d.D, msg_dim, nodes_cur, 2 * B,
-                           nullptr, &d.gw, d.gru_ws, p->gru_ready ? 1 : 0, wm_p, wm_p ? d.proj_table : nullptr, p->main_s, true, true,
-                           n_rows > 0 ? &p->out_gru : nullptr, p->cell, tail.word ? &tail : nullptr, &carried);
-    if (rc != ZT_OK) return rc;
-    if (carried && nxt != nullptr) { nxt->tail_gated |= 1u << jn; p->tail_gates++; }
-    p->gru_ready = true;
-    if (scored) {                                // compute_edge_probabilities' scorer (model/tgn_model.py:185-188) on the rows just written
-        const int par = p->score_n & 1;
-        float *prob = p->prob + (size_t)par * 2 * d.max_B;
-        if (p->met_pending[par]) {               // the metrics kernel of two steps ago still reads this half
-            ZT_HIP(hipStreamWaitEvent(p->main_s, p->met_done[par], 0));
-            p->met_pending[par] = false;
-        }
-        rc = zt_affinity(out_emb_dev, B, d.D * (d.M + 1), &p->aff, p->prob + (size_t)par * 2 * d.max_B, p->aff_ws, d.max_B,
-                         p->aff_ready ? 1 : 0, p->main_s);
-        if (rc != ZT_OK) return rc;
-        ZT_HIP(hipEventRecord(p->scored[par], p->main_s));
-        p->aff_ready = true;
-        p->score_n++;
-        p->score_B = B;
-        if (measured) {                          // AP / AUC / accuracy of these 2B probabilities, beside the next step (message stream)
-            ZT_HIP(hipStreamWaitEvent(p->msg_s, p->scored[par], 0));
-            rc = zt::link_metrics_launch(prob, prob + B, B, p->met_sum, 1, p->met_rows ? p->met_rows + 3 * p->met_n : nullptr, p->msg_s);
-            if (rc != ZT_OK) return rc;
-            ZT_HIP(hipEventRecord(p->met_done[par], p->msg_s));
-            p->met_pending[par] = true;
-            p->met_last = par;
-            p->met_n++;
-        }
-    }
-    if (d.proj_table != nullptr && wm_p == nullptr) {
-        char *gw = reinterpret_cast<char *>(d.gru_ws);
-        rc = zt_project_memory(d.memory, d.num_nodes, d.D, d.F, d.T, &d.ew, 1,
-                               reinterpret_cast<const int32_t *>(gw + zt_gru_rows_offset(d.D, msg_dim)),
-                               reinterpret_cast<const int32_t *>(gw), 2 * B, d.proj_table, d.embed_ws, 3 * d.max_B, d.M, d.k,
-                               p->main_s);
-        if (rc != ZT_OK) return rc;
-    }
-    // ---- multi-GPU: the rows every rank's GRU update rewrote, all-gathered and scattered into the local tables; the
-    // projected table follows the rows the other ranks wrote (this rank's own were refreshed by its GRU kernel) ----
-    if (p->xchg != nullptr) {
-        const int32_t *xids = nullptr;
-        int64_t n_x = 0;
-        rc = zt::exchange_step(p->xchg, gru_rows, gru_cnt, p->main_s, &xids, &n_x);
-        if (rc != ZT_OK) return rc;
-        if (d.proj_table != nullptr) {
-            rc = zt_project_memory(d.memory, d.num_nodes, d.D, d.F, d.T, &d.ew, p->embed_ready ? 1 : 0, xids, nullptr, n_x, d.proj_table,
-                                   d.embed_ws, 3 * d.max_B, d.M, d.k, p->main_s);
-            if (rc != ZT_OK) return rc;
-            p->embed_ready = true;                 // (a rank whose row shard was empty: the padded weights were made just now)
-        }
-    }
-    // the member is used up; with the last one the slot is free again
-    s->key[j] = nullptr;
-    if (++s->n_done >= s->n) {
-        ZT_HIP(hipEventRecord(s->consumed, p->main_s));
-        s->n = 0;
-    }
-    return ZT_OK;
+    int rc;
+    if ((rc = t.query_this_batch()) != ZT_OK || (rc = t.pass_gate()) != ZT_OK || (rc = t.query_ahead()) != ZT_OK) return rc;
+    t.look_at_next_member();
+    t.plan = zt::pipeline_step_plan(t.f);
+    if ((rc = t.gather_rows()) != ZT_OK || (rc = t.build_messages()) != ZT_OK || (rc = t.aggregate()) != ZT_OK ||
+        (rc = t.update_memory()) != ZT_OK || (rc = t.score_and_measure()) != ZT_OK || (rc = t.refresh_and_exchange()) != ZT_OK)
+        return rc;
+    return t.retire_member();
 }
 
 // n consecutive whole-batch steps from ONE host call: the per-batch loop of evaluation/evaluation.py:19-45 (and of a bulk

@@ -45,6 +45,22 @@ int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F,
  * ZT_CHOICE_SCORE selection.  out[7] = form (0 refused, 1 latency, 2 tiled, 3 generic latency, 4 generic tiled: the ZT_SCORE_*
  * values), KC, ET (the specialised forms' template arguments, else 0), grid x, grid y, threads per workgroup, dynamic LDS. */
 int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64_t *out);
+/* Test hook: one pipeline step's choices (zt::pipeline_step_plan, host code only).  The facts, 0 / 1 unless said otherwise:
+ * streaming (else pruning), masked, release (the ZT_CHOICE_GROUP_RELEASE value), B, row_lo, row_hi, scoring, metrics, exchange,
+ * avg_topk, proj_table (each: attached), wm_ready (the padded W_m is in the embed workspace); the current member's slot:
+ * by_member, its tail_gated bit, waited; the batch that follows: have_next, next_B, next_in_slot, and that slot's by_member,
+ * launched, waited and the member's tail_gated bit.  out[12] = gate form (0 carried by the previous GRU kernel, 1 the launch's
+ * event, 2 a kernel in front, 3 offered to the aggregation kernel), wait for `filled` first, wait for the launch's event,
+ * shard gather, k_avg_topk, scored, measured, the GRU update is the main stream's last item, the tail gate is offered for the
+ * next member, that needs the next slot's `filled`, late zt_project_memory, exchange. */
+int zt_test_step_plan(int32_t streaming, int32_t masked, int32_t release, int64_t B, int64_t row_lo, int64_t row_hi,
+                      int32_t scoring, int32_t metrics, int32_t exchange, int32_t avg_topk, int32_t proj_table, int32_t wm_ready,
+                      int32_t by_member, int32_t tail_gated, int32_t waited, int32_t have_next, int64_t next_B,
+                      int32_t next_in_slot, int32_t next_by_member, int32_t next_launched, int32_t next_waited,
+                      int32_t next_tail_gated, int64_t *out);
+/* Test hook: a launch group's release and size limit (zt::pipeline_group_plan).  want: zt_pipeline_set_group; n_more: batches
+ * in sight behind the first.  out[2] = released by member (before "and more than one member"), batches it may take. */
+int zt_test_group_plan(int32_t streaming, int32_t release, int32_t want, int32_t n_more, int64_t *out);
 
 #ifdef __cplusplus
 }

@@ -149,3 +149,30 @@ extern "C" int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64
     for (int i = 0; i < 7; ++i) out[i] = v[i];
     return ZT_OK;
 }
+
+extern "C" int zt_test_step_plan(int32_t streaming, int32_t masked, int32_t release, int64_t B, int64_t row_lo, int64_t row_hi,
+                                 int32_t scoring, int32_t metrics, int32_t exchange, int32_t avg_topk, int32_t proj_table,
+                                 int32_t wm_ready, int32_t by_member, int32_t tail_gated, int32_t waited, int32_t have_next,
+                                 int64_t next_B, int32_t next_in_slot, int32_t next_by_member, int32_t next_launched,
+                                 int32_t next_waited, int32_t next_tail_gated, int64_t *out)
+{
+    if (!out) return ZT_ERR_ARG;
+    const StepFacts f{streaming != 0, masked != 0, release, (long long)B, (long long)row_lo, (long long)row_hi, scoring != 0,
+                      metrics != 0, exchange != 0, avg_topk != 0, proj_table != 0, wm_ready != 0, by_member != 0, tail_gated != 0,
+                      waited != 0, have_next != 0, (long long)next_B, next_in_slot != 0, next_by_member != 0, next_launched != 0,
+                      next_waited != 0, next_tail_gated != 0};
+    const StepPlan sp = pipeline_step_plan(f);
+    const int64_t v[12] = {(int64_t)sp.gate, sp.wait_filled, sp.wait_launch, sp.gather, sp.avg_topk, sp.scored, sp.measured,
+                           sp.gru_is_last, sp.tail_offer, sp.tail_wait_filled, sp.late_project, sp.exchange};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return ZT_OK;
+}
+
+extern "C" int zt_test_group_plan(int32_t streaming, int32_t release, int32_t want, int32_t n_more, int64_t *out)
+{
+    if (!out) return ZT_ERR_ARG;
+    const GroupPlan gp = pipeline_group_plan(streaming != 0, release, want, n_more);
+    out[0] = gp.by_member;
+    out[1] = gp.limit;
+    return ZT_OK;
+}
