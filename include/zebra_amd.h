@@ -802,6 +802,57 @@ int64_t zt_affinity_rank_workspace_bytes(int64_t Q, int64_t Nc, int32_t H);
 int zt_affinity_rank(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
                      const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w,
                      float *prob_dev, void *workspace_dev, void *stream);
+/* The K likeliest candidates of every query (csrc/rank_topk.hip) without prob[Q][C]: emb_q_dev, emb_c_dev, cand_idx_dev (NULL:
+ * every query takes all Nc rows in order, C == Nc), the weights, the width bound and the status word (first int32 of the
+ * workspace; ZT_ERR_RANGE for an index >= Nc or < -1, that pair counts as absent) are zt_affinity_rank's, and every pair's
+ * probability has the bits zt_affinity_rank writes for it (csrc/rank_pair.hpp: one pair sum for both).
+ *   top_idx_dev [Q][K] (int32) = idx_base + c, c the column in [0, C); top_prob_dev [Q][K] = the probabilities: the K present
+ *   candidates with the largest probability in descending order, equal probabilities in ascending index; slots beyond the
+ *   number of present candidates read -1 and 0.  Present: the index is >= 0 and in range, the global column idx_base + c
+ *   differs from skip_dev[q] (skip_dev NULL, or -1 for a query: nothing left out), and the probability is not NaN -- nor the
+ *   candidate's projected row, which a NaN anywhere in its embedding makes NaN throughout (the pair sum's relu would drop it:
+ *   zt_affinity_rank writes a finite number for such a row; here it is never selected).  The order
+ *   on (probability, index) is strict: the result is a function of the inputs alone, whatever the workspace, slabs or grid.
+ *   accumulate != 0: the K entries already in top_idx_dev / top_prob_dev (index -1: an empty slot) compete with this call's
+ *   candidates; the caller keeps their indices outside [idx_base, idx_base + C).  A pool given in pieces, in any order, gives
+ *   the bits of one call over the whole pool.
+ * 1 <= K <= ZT_TOPK_MAX_K (K <= 0: ZT_ERR_ARG; above: ZT_ERR_UNSUPPORTED); idx_base < 0 or idx_base + C > INT32_MAX: ZT_ERR_ARG.
+ * Q = 0: ZT_OK, nothing touched.  C = 0: ZT_OK, the output filled with -1 and 0, or left alone under accumulate.  Argument
+ * checks come before any device call.
+ * workspace_dev, 16-byte aligned, of workspace_bytes bytes as the caller states them: P_q, one list of K keys per query and span,
+ * and P_c of ONE SLAB of candidate rows -- the pool is walked a slab at a time (per slab: the f32 MFMA GEMM, the pair kernel
+ * over spans of candidate columns with a running top-K per wave, the merge kernel), so no "Q x C pairs exceed one launch" bound
+ * applies and memory does not grow with the pool.  zt_affinity_topk_workspace_bytes(Q, Nc, H, K) is the recommended size
+ * (-1: H or K unsupported, or a negative size); it stops growing once Nc exceeds the plan's slab cap (128 MiB of P_c, or 2^18 rows).  Its
+ * value for Nc = 32 is the smallest size accepted (ZT_ERR_ARG below it).
+ * zt_affinity_topk_plan is where the form, the slab rows, the spans and the grids are decided (host code only; indexed != 0:
+ * cand_idx is given).  No float atomics, no workgroup waits for another: two calls give the same bits. */
+#define ZT_TOPK_MAX_K 256
+#define ZT_TOPK_FORM_LANE 1  /* K <= 64: a wave's list is one 64-bit key per lane */
+#define ZT_TOPK_FORM_LANE4 2 /* 64 < K <= 256: four keys per lane */
+#define ZT_TOPK_PLAN_FIELDS 12
+/* plan_out[ZT_TOPK_PLAN_FIELDS], all int64:
+ *   [0] form         ZT_TOPK_FORM_*
+ *   [1] wave_queries queries a wave scores each candidate row against: 4 (shared pool: the row's registers are reused) or 1
+ *   [2] q_tiles      tiles of 4 queries
+ *   [3] slab_rows    rows of P_c the workspace holds (a multiple of 32)
+ *   [4] n_slabs      slabs the pool is walked in: n_slabs * slab_rows >= Nc
+ *   [5] span_cols    candidate columns per span (shared pool: of a slab's rows; indexed: of the C index columns)
+ *   [6] n_spans      spans per slab
+ *   [7] grid_pairs   workgroups of the pair kernel, per slab: q_tiles * n_spans
+ *   [8] grid_merge   workgroups of the merge kernel, per slab
+ *   [9] lists_offset byte offset of the per-span lists in the workspace
+ *  [10] pc_offset    byte offset of the slab's P_c
+ *  [11] min_bytes    the smallest workspace accepted
+ * ZT_ERR_ARG for NULL plan_out, a negative size, C != Nc without indices or a workspace below min_bytes; K and H as above. */
+int64_t zt_affinity_topk_workspace_bytes(int64_t Q, int64_t Nc, int32_t H, int32_t K);
+int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                     const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w,
+                     int32_t K, const int32_t *skip_dev, int64_t idx_base, int32_t accumulate,
+                     int32_t *top_idx_dev, float *top_prob_dev,
+                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+int zt_affinity_topk_plan(int64_t Q, int64_t Nc, int64_t C, int32_t H, int32_t K, int32_t indexed,
+                          int64_t workspace_bytes, int64_t *plan_out);
 /* Ranks, MRR and Hits@k of prob_dev [Q][C] (cand_idx_dev as above, may be NULL: every entry present).  Column 0 is the
  * positive:  rank = 1 + #{c >= 1 present : p_c > p_0} + 0.5 #{c >= 1 present : p_c == p_0}, the mean of the optimistic and
  * the pessimistic rank.  A query whose column 0 is absent is skipped and not counted.  rank_dev [Q] (or NULL) receives the

@@ -35,6 +35,7 @@ SYMBOLS = [
     "zt_link_metrics_plan", "zt_pipeline_set_metrics", "zt_pipeline_metrics",
     "zt_link_bce_forward", "zt_link_bce_backward", "zt_adam_step", "zt_adam_plan",
     "zt_tppr_query", "zt_affinity_rank_workspace_bytes", "zt_affinity_rank", "zt_rank_metrics",
+    "zt_affinity_topk_workspace_bytes", "zt_affinity_topk", "zt_affinity_topk_plan",
 ]
 
 
@@ -55,6 +56,10 @@ METRICS_MAX_B = 16384
 MSG_ONE, MSG_TWO = 1, 2
 ADAM_CHUNK, ADAM_MAX_TENSORS = 4096, 64                         # zt_adam_plan / zt_adam_step
 RANK_MIN_H, RANK_MAX_H = 4, 4352                                # zt_affinity_rank's hidden widths (H % 4 == 0)
+TOPK_MAX_K = 256                                                # zt_affinity_topk
+TOPK_FORM_LANE, TOPK_FORM_LANE4 = 1, 2                          # zt_affinity_topk_plan
+TOPK_PLAN_FIELDS = ("form", "wave_queries", "q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid_pairs", "grid_merge",
+                    "lists_offset", "pc_offset", "min_bytes")
 
 
 def set_kernel_choice(which, value):
@@ -142,7 +147,7 @@ def lib():
             _lib.zt_pipeline_main_stream.restype = C.c_void_p
         _lib.zt_version.restype = C.c_char_p
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
-                     "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes"):
+                     "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib
@@ -185,6 +190,15 @@ def link_metrics_plan(B):
     out = (C.c_int64 * 4)()
     check(lib().zt_link_metrics_plan(C.c_int64(B), out), "zt_link_metrics_plan")
     return dict(form=int(out[0]), threads=int(out[1]), n2=int(out[2]), lds_bytes=int(out[3]))
+
+
+def topk_plan(Q, Nc, C_, H, K, indexed, workspace_bytes):
+    """zt_affinity_topk_plan: the form, slab rows, spans and grids of one zt_affinity_topk call over C_ candidate columns (host
+    code only)."""
+    out = (C.c_int64 * len(TOPK_PLAN_FIELDS))()
+    check(lib().zt_affinity_topk_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H), C.c_int32(K),
+                                      C.c_int32(1 if indexed else 0), C.c_int64(workspace_bytes), out), "zt_affinity_topk_plan")
+    return {name: int(out[i]) for i, name in enumerate(TOPK_PLAN_FIELDS)}
 
 
 def adam_plan(numel):

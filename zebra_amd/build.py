@@ -35,6 +35,7 @@ SOURCES = {
     "scoring.hip": [],
     "scoring_train.hip": [],
     "rank.hip": [],
+    "rank_topk.hip": [],
     "train_tail.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],

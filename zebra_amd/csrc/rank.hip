@@ -7,27 +7,19 @@
 //                      which is no GEMM (the relu sits inside the sum over h): k_rank_pairs.
 //   zt_rank_metrics    rank of column 0 among the present candidates of each query, and MRR / Hits@1,3,10 sums.
 #include "common.hpp"
+#include "rank_pair.hpp"
 
 using namespace zt;
 
 namespace {
-
-constexpr int RANK_MIN_H = 4, RANK_MAX_H = 4352;   // 256 x 17: the widest hidden layer D <= 256 and 16 models give
-constexpr int RK_TQ = 4;            // query rows per workgroup: one per wave
-constexpr int RK_GROUP = 16;        // lanes that share one pair: 16 x float4 = 64 consecutive h per step
-constexpr int RK_NC = 8;            // candidates per lane group, their loads in flight together
-constexpr int RK_TC = (WAVE / RK_GROUP) * RK_NC;   // 32 candidates per workgroup
-constexpr int RK_HC = 1024;         // h per chunk: (RK_TQ + 1) x 4 KB of LDS
-constexpr size_t RK_HEAD = 256;     // bytes in front of P_q in the workspace: the status word
-
-inline bool rank_width_ok(int H) { return H >= RANK_MIN_H && H <= RANK_MAX_H && H % 4 == 0; }
 
 // One workgroup: RK_TQ queries x RK_TC candidate slots.  Wave w owns query q0 + w; each of its four 16-lane groups owns RK_NC
 // slots.  The (P_q + b1) rows of the tile and w2 lie in LDS one chunk of RK_HC columns at a time; a lane walks the chunk in
 // steps of 64 columns, its float4 of the query row and of w2 from LDS (the four groups of a wave read the same address: a
 // broadcast) against one 16-byte vector of each of its candidates' rows from memory.  A pair's sum: lane l of its group adds
 // columns 4l .. 4l + 3 of every 64 in ascending order into one accumulator, then the sixteen lanes are folded by xor 8, 4, 2, 1
-// -- one association whatever the tile, no atomics: the same bits on every run.
+// -- one association whatever the tile, no atomics: the same bits on every run.  The arithmetic is rank_pair.hpp's, shared with
+// the top-K scorer (rank_topk.hip).
 __global__ __launch_bounds__(WAVE * RK_TQ) void k_rank_pairs(const float *__restrict__ Pq, const float *__restrict__ Pc,
                                                              const int *__restrict__ cand_idx, long long Q, long long Nc,
                                                              long long C, int H, long long ctiles,
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(WAVE * RK_TQ) void k_rank_pairs(const float *__rest
             if (r == RK_TQ) { s_w[c4] = b; continue; }
             float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
             if (q0 + r < Q) p = *reinterpret_cast<const float4 *>(Pq + (q0 + r) * H + h0 + 4 * c4);
-            s_q[r][c4] = make_float4(p.x + b.x, p.y + b.y, p.z + b.z, p.w + b.w);
+            s_q[r][c4] = rk_query_bias(p, b);
         }
         __syncthreads();
         for (int c4 = gl; c4 < hn / 4; c4 += RK_GROUP) {
@@ -81,24 +73,15 @@ __global__ __launch_bounds__(WAVE * RK_TQ) void k_rank_pairs(const float *__rest
             }
             const float4 pq = s_q[wave][c4], w = s_w[c4];
 #pragma unroll
-            for (int j = 0; j < RK_NC; ++j) {
-                acc[j] = fmaf(w.x, fmaxf(pq.x + pc[j].x, 0.f), acc[j]);
-                acc[j] = fmaf(w.y, fmaxf(pq.y + pc[j].y, 0.f), acc[j]);
-                acc[j] = fmaf(w.z, fmaxf(pq.z + pc[j].z, 0.f), acc[j]);
-                acc[j] = fmaf(w.w, fmaxf(pq.w + pc[j].w, 0.f), acc[j]);
-            }
+            for (int j = 0; j < RK_NC; ++j) acc[j] = rk_pair_step(acc[j], w, pq, pc[j]);
         }
     }
     const float bias2 = b2[0];
 #pragma unroll
     for (int j = 0; j < RK_NC; ++j) {
-        float s = acc[j];
-        s += __shfl_xor(s, 8, WAVE);
-        s += __shfl_xor(s, 4, WAVE);
-        s += __shfl_xor(s, 2, WAVE);
-        s += __shfl_xor(s, 1, WAVE);
+        const float s = rk_fold16(acc[j]);
         const long long c = c0 + j;
-        if (gl == 0 && q < Q && c < C) prob[q * C + c] = row[j] >= 0 ? 1.f / (1.f + expf(-(s + bias2))) : 0.f;
+        if (gl == 0 && q < Q && c < C) prob[q * C + c] = row[j] >= 0 ? rk_prob(s, bias2) : 0.f;
     }
 }
 

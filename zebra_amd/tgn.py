@@ -253,7 +253,12 @@ class TGN(torch.nn.Module):
             cand = cand.unsqueeze(0).expand(Q, -1)
         if cand.dim() != 2 or cand.shape[0] != Q or ts_d.numel() != Q:
             raise ValueError("rank_candidates takes sources [Q], timestamps [Q] and candidates [Q, C] or [C]")
-        cand = cand.contiguous()
+        emb_q, emb_c, cand_idx = self._embed_candidates(src_d, ts_d, cand.contiguous(), check_status)
+        return self.rank_scores(emb_q, emb_c, cand_idx, check_status=check_status)
+
+    def _embed_candidates(self, src_d, ts_d, cand, check_status):
+        """(emb_q, emb_c, cand_idx) of sources [Q] at times [Q] and their candidates [Q, C] (-1: absent): every distinct
+        (candidate, time of its query) pair is embedded once, cand_idx names its row of emb_c."""
         emb_q = self.embed_nodes(src_d, ts_d, check_status=check_status)
         live = cand >= 0
         t_of = ts_d.unsqueeze(1).expand_as(cand)
@@ -262,7 +267,153 @@ class TGN(torch.nn.Module):
         emb_c = self.embed_nodes(uniq[0].to(torch.int32), uniq[1].contiguous(), check_status=check_status)
         cand_idx = torch.full(cand.shape, -1, dtype=torch.int32, device=self.device)
         cand_idx[live] = inv.to(torch.int32)
-        return self.rank_scores(emb_q, emb_c, cand_idx, check_status=check_status)
+        return emb_q, emb_c, cand_idx
+
+    @torch.no_grad()
+    def topk_scores(self, emb_q, emb_c, k, cand_idx=None, skip=None, idx_base=0, out=None, check_status=True,
+                    workspace_bytes=None):
+        """(idx [Q, k] int32, prob [Q, k] float32): for every query the ``k`` present candidates of ``rank_scores`` with the
+        largest probability, descending, equal probabilities in ascending index; slots beyond the present candidates read -1
+        and 0.  ``idx`` is ``idx_base`` + the column in [0, C).  Present: ``cand_idx`` (if given) is >= 0, the probability is not
+        NaN -- nor any element of the candidate's embedding -- and ``idx_base`` + column differs from ``skip[q]`` (int32 [Q],
+        -1: none).  ``out=(idx, prob)``: the entries already
+        there (-1: empty) compete with this call's candidates and the result is written into them -- a pool given in pieces, with
+        ``idx_base`` set accordingly, gives the bits of one call.  Where ``rank_scores`` would call zt_affinity_rank and
+        k <= 256 this is zt_affinity_topk (csrc/rank_topk.hip): prob[Q, C] is never written and the workspace does not grow
+        with the pool (``workspace_bytes``: its size, zt_affinity_topk_workspace_bytes by default).  Anything else computes
+        ``rank_scores`` a chunk of queries at a time and selects by stable sorts with the same rule."""
+        a = self.affinity_score
+        Q, H = emb_q.shape
+        Nc = emb_c.shape[0]
+        C_ = Nc if cand_idx is None else cand_idx.shape[1]
+        k = int(k)
+        if k <= 0:
+            raise ValueError("topk_scores: k must be positive")
+        if idx_base < 0 or idx_base + C_ > 0x7fffffff:
+            raise ValueError("topk_scores: idx_base + C exceeds the int32 indices of the result")
+        dev = emb_q.device
+        if out is not None:
+            top_idx, top_prob = out
+            if (top_idx.shape != (Q, k) or top_prob.shape != (Q, k) or top_idx.dtype != torch.int32 or top_prob.dtype != torch.float32
+                    or top_idx.device != dev or top_prob.device != dev or not top_idx.is_contiguous() or not top_prob.is_contiguous()):
+                raise ValueError("topk_scores: out is (idx [Q, k] int32, prob [Q, k] float32), contiguous, on the embeddings' device")
+        hip = (emb_q.is_cuda and emb_c.is_cuda and emb_q.dtype == torch.float32 and emb_c.dtype == torch.float32
+               and H % 4 == 0 and _capi.RANK_MIN_H <= H <= _capi.RANK_MAX_H and k <= _capi.TOPK_MAX_K)
+        if not hip:
+            if out is None:
+                top_idx = torch.full((Q, k), -1, dtype=torch.int32, device=dev)
+                top_prob = torch.zeros((Q, k), dtype=torch.float32, device=dev)
+            if Q == 0 or C_ == 0:
+                return top_idx, top_prob
+            col = torch.arange(C_, device=dev, dtype=torch.int64) + int(idx_base)
+            step = max(1, (1 << 24) // max(1, C_))
+            for s in range(0, Q, step):
+                ix = None if cand_idx is None else cand_idx[s:s + step]
+                p = self.rank_scores(emb_q[s:s + step], emb_c, ix, check_status=check_status).to(torch.float32)
+                live = ~torch.isnan(p)
+                nan_row = torch.isnan(emb_c).any(dim=1)          # (the kernels' relu drops a NaN: such a row is a NaN candidate)
+                if ix is None:
+                    live &= ~nan_row.unsqueeze(0)
+                else:
+                    ixd = ix.to(dev).long()
+                    live &= (ixd >= 0) & (ixd < Nc)
+                    live &= ~nan_row[ixd.clamp(0, max(Nc - 1, 0))]
+                if skip is not None:
+                    live &= col.unsqueeze(0) != skip[s:s + step].to(dev, torch.int64).unsqueeze(1)
+                # this call's candidates behind the incoming list; absent entries sort last (probabilities are >= 0)
+                n = p.shape[0]
+                all_i = torch.cat([top_idx[s:s + step].to(torch.int64), col.unsqueeze(0).expand(n, -1)], dim=1)
+                all_p = torch.cat([top_prob[s:s + step], p], dim=1)
+                all_live = torch.cat([top_idx[s:s + step] >= 0, live], dim=1)
+                all_p = torch.where(all_live, all_p, torch.full_like(all_p, -1.0))
+                o1 = torch.sort(all_i, dim=1, stable=True).indices               # ascending index, then a stable sort by
+                o2 = torch.sort(all_p.gather(1, o1), dim=1, descending=True, stable=True).indices[:, :k]    # probability
+                sel = o1.gather(1, o2)
+                got = all_live.gather(1, sel)
+                kk = sel.shape[1]
+                top_idx[s:s + step, :kk] = torch.where(got, all_i.gather(1, sel), torch.full_like(sel, -1)).to(torch.int32)
+                top_prob[s:s + step, :kk] = torch.where(got, all_p.gather(1, sel), torch.zeros_like(all_p[:, :kk]))
+            return top_idx, top_prob
+        accumulate = out is not None
+        if not accumulate:
+            top_idx = torch.empty((Q, k), dtype=torch.int32, device=self.device)
+            top_prob = torch.empty((Q, k), dtype=torch.float32, device=self.device)
+        if Q == 0:
+            return top_idx, top_prob
+        need = int(lib().zt_affinity_topk_workspace_bytes(C.c_int64(Q), C.c_int64(Nc), C.c_int32(H), C.c_int32(k)))
+        if workspace_bytes is not None:
+            need = int(workspace_bytes)
+        ws = getattr(self, "_topk_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._topk_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        w = _capi.AffinityWeights()
+        w.fc1_w, w.fc1_b, w.fc2_w, w.fc2_b = (a.fc1.weight.data_ptr(), a.fc1.bias.data_ptr(), a.fc2.weight.data_ptr(),
+                                              a.fc2.bias.data_ptr())
+        ix = None if cand_idx is None else cand_idx.to(self.device, torch.int32).contiguous()
+        sk = None if skip is None else skip.to(self.device, torch.int32).contiguous()
+        if sk is not None and sk.numel() != Q:
+            raise ValueError("topk_scores: skip holds one column per query")
+        check(lib().zt_affinity_topk(ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), ptr(ix),
+                                     C.c_int64(C_), C.c_int32(H), C.byref(w), C.c_int32(k), ptr(sk), C.c_int64(int(idx_base)),
+                                     C.c_int32(1 if accumulate else 0), ptr(top_idx), ptr(top_prob), ptr(ws), C.c_int64(need),
+                                     stream_ptr()), "zt_affinity_topk")
+        if check_status and ix is not None and C_ > 0:
+            st = int(ws[:4].view(torch.int32).item())           # the call's status word: first int32 of the workspace
+            if st != 0:
+                raise IndexError("zt_affinity_topk: candidate index out of range (status %d)" % st)
+        return top_idx, top_prob
+
+    @torch.no_grad()
+    def recommend(self, sources, timestamps, k, candidates=None, exclude_self=True, pool_chunk=65536):
+        """(nodes [Q, k] int32, prob [Q, k] float32): the ``k`` likeliest partners of every source among ``candidates``, -1 and 0
+        in empty slots; read-only, and raises where ``embed_nodes`` raises.
+        ``candidates=None``: every node id 1 .. n_nodes - 1 (0 is the padding id), without the source's own id under
+        ``exclude_self``; a 1-D list: a pool shared by all queries (-1: absent).  Both are embedded ``pool_chunk`` rows at a time
+        and each chunk goes through ``topk_scores`` with accumulate, so memory does not depend on the pool; ``timestamps`` is
+        then a scalar or all equal (ValueError otherwise: a candidate's embedding depends on the query's time).
+        ``candidates`` [Q, C] (-1: absent) takes per-query times: ``rank_candidates``' de-duplication, then ``topk_scores``."""
+        src_d = self._as_device(sources, torch.int32).reshape(-1)
+        Q = src_d.numel()
+        ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
+        if ts_d.numel() == 1 and Q != 1:
+            ts_d = ts_d.expand(Q).contiguous()
+        k = int(k)
+        if ts_d.numel() != Q or k <= 0 or int(pool_chunk) <= 0:
+            raise ValueError("recommend takes sources [Q], timestamps [Q] or a scalar, k > 0 and pool_chunk > 0")
+        cand = None if candidates is None else self._as_device(candidates, torch.int32)
+        if cand is not None and cand.dim() == 2:
+            if cand.shape[0] != Q:
+                raise ValueError("recommend takes candidates [Q, C] or [C]")
+            emb_q, emb_c, cand_idx = self._embed_candidates(src_d, ts_d, cand.contiguous(), True)
+            idx, prob = self.topk_scores(emb_q, emb_c, k, cand_idx=cand_idx)
+            nodes = torch.where(idx >= 0, cand.gather(1, idx.clamp(min=0).long()), torch.full_like(idx, -1))
+            return nodes, prob
+        if cand is not None and cand.dim() != 1:
+            raise ValueError("recommend takes candidates [Q, C] or [C]")
+        if Q > 0 and bool((ts_d != ts_d[0]).any()):
+            raise ValueError("recommend: a shared pool needs one query time (a scalar, or all timestamps equal): a candidate's "
+                             "embedding depends on it; give candidates [Q, C] for per-query times")
+        emb_q = self.embed_nodes(src_d, ts_d)
+        n_pool = self.n_nodes - 1 if cand is None else cand.numel()
+        idx = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+        prob = torch.zeros((Q, k), dtype=torch.float32, device=self.device)
+        if Q == 0 or n_pool <= 0:
+            return idx, prob
+        skip = (src_d - 1) if (cand is None and exclude_self) else None      # node id v is column v - 1 of the pool 1 .. n - 1
+        for s in range(0, n_pool, int(pool_chunk)):
+            e = min(n_pool, s + int(pool_chunk))
+            ids = torch.arange(s + 1, e + 1, dtype=torch.int32, device=self.device) if cand is None else cand[s:e]
+            emb_c = self.embed_nodes(ids.clamp(min=0), ts_d[:1].expand(e - s).contiguous())
+            cix = None
+            if cand is not None and bool((ids < 0).any()):                 # absent entries of a shared list: through indices
+                cix = torch.where(ids >= 0, torch.arange(e - s, dtype=torch.int32, device=self.device),
+                                  torch.full_like(ids, -1)).unsqueeze(0).expand(Q, -1).contiguous()
+            self.topk_scores(emb_q, emb_c, k, cand_idx=cix, skip=skip, idx_base=s, out=(idx, prob))
+        if cand is None:
+            nodes = torch.where(idx >= 0, idx + 1, idx)
+        else:
+            nodes = torch.where(idx >= 0, cand[idx.clamp(min=0).long()], torch.full_like(idx, -1))
+        return nodes, prob
 
     def _score_pairs(self, s, dd, n):
         """The scorer as torch composes it (tgn_model.py:185-188): (pos [B, 1], neg [B, 1]) under autograd."""
