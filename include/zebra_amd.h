@@ -720,7 +720,12 @@ typedef struct {
 
 /*   src [N][D], src_time [N][T], nbr_feat [N][k][D], edge_feat [N][k][F],
  *   nbr_time [N][k][T], mask uint8 [N][k] (non-zero = padding)
- *   -> out [N][out_dim], attn_w [N][k] (head-averaged attention weights). */
+ *   -> out [N][out_dim], attn_w [N][k] (head-averaged attention weights).
+ *   Shapes taken: 1 <= n_head <= 4 dividing E; k <= 80; and one workgroup's tile -- a query row's k key rows, rounded
+ *   up to 16, at width Ek, their projection at width E and three 16-row blocks as wide as the widest of E + D, hidden
+ *   and out_dim -- within 158 KB of LDS (D = T = 100, F = 172: k <= 48; D = F = T = 172: k <= 16; D = T = 224, F = 1:
+ *   k <= 16; D = T = 228 and wider: none).  Any other shape: zt_attention_workspace_bytes returns -1 and
+ *   zt_temporal_attention ZT_ERR_UNSUPPORTED before anything is launched; there is no fall-back. */
 int64_t zt_attention_workspace_bytes(int32_t D, int32_t F, int32_t T, int32_t n_head,
                                      int32_t hidden, int32_t out_dim, int32_t k);
 int zt_temporal_attention(const float *src_dev, const float *src_time_dev,

@@ -10,10 +10,10 @@ which the reference's own class produced (tests/golden/gen_golden.py).
 import numpy as np
 
 
-def temporal_attention(src, src_t, nbr, nbr_t, edge, mask, w, n_head):
+def temporal_attention(src, src_t, nbr, nbr_t, edge, mask, w, n_head, f64=False):
     """src [N,D], src_t [N,1,T], nbr [N,k,D], nbr_t [N,k,T], edge [N,k,F], mask bool [N,k] (True = padding);
     w = dict(q_w, k_w, v_w, in_b, out_w, out_b, m1_w, m1_b, m2_w, m2_b) in torch layout.
-    Returns (out [N,Dout], attn_w [N,k])."""
+    Returns (out [N,Dout], attn_w [N,k]), rounded to float32 unless f64 (tests/test_attention_f64_gpu.py)."""
     f8 = np.float64
     N, k, _ = nbr.shape
     query = np.concatenate([src[:, None, :], src_t], axis=2).astype(f8)[:, 0, :]        # :51-52  [N,E]
@@ -42,4 +42,6 @@ def temporal_attention(src, src_t, nbr, nbr_t, edge, mask, w, n_head):
     aw[invalid] = 0                                                                      # :66
     h = np.concatenate([o, src.astype(f8)], axis=1) @ w["m1_w"].astype(f8).T + w["m1_b"].astype(f8)
     out = np.maximum(h, 0) @ w["m2_w"].astype(f8).T + w["m2_b"].astype(f8)              # :67, util.py:23-26
+    if f64:
+        return out, aw
     return out.astype(np.float32), aw.astype(np.float32)

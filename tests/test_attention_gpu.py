@@ -35,11 +35,27 @@ def _run(layer, x):
     return out.cpu().numpy(), aw.cpu().numpy()
 
 
+@pytest.fixture
+def attention_calls(monkeypatch):
+    """[n]: calls of lib().zt_temporal_attention from here on (the HIP kernel is what ran, not forward_torch)"""
+    from zebra_amd import _capi
+    lib = _capi.lib()
+    calls, fwd = [0], lib.zt_temporal_attention
+
+    def counted(*args):
+        calls[0] += 1
+        return fwd(*args)
+
+    monkeypatch.setattr(lib, "zt_temporal_attention", counted)
+    return calls
+
+
 @pytest.mark.parametrize("name", list(I.ATTENTION_CASES))
-def test_temporal_attention_matches_reference_layer(name):
+def test_temporal_attention_matches_reference_layer(name, attention_calls):
     D, F, T, k, N, heads, seed = I.ATTENTION_CASES[name]
     g = golden("g9_attention_" + name)
     out, aw = _run(_layer(D, F, T, heads, I.attention_weights(D, F, T, seed)), I.attention_inputs(D, F, T, k, N, seed))
+    assert attention_calls[0] == 1
     assert out.shape == g["out"].shape and aw.shape == g["attn_w"].shape
     assert np.abs(out - g["out"]).max() <= 1e-4
     assert np.abs(aw - g["attn_w"]).max() <= 1e-5
@@ -47,12 +63,13 @@ def test_temporal_attention_matches_reference_layer(name):
 
 
 @pytest.mark.parametrize("D,F,T,k,N,heads", [(100, 172, 100, 20, 600, 2), (100, 1, 100, 40, 257, 2), (20, 4, 12, 5, 70, 4)])
-def test_temporal_attention_matches_oracle(D, F, T, k, N, heads):
+def test_temporal_attention_matches_oracle(D, F, T, k, N, heads, attention_calls):
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import attention_np
     w = I.attention_weights(D, F, T, 900 + k)
     x = I.attention_inputs(D, F, T, k, N, 900 + k)
     out, aw = _run(_layer(D, F, T, heads, w), x)
+    assert attention_calls[0] == 1
     want_out, want_w = attention_np.temporal_attention(*x, w, heads)
     assert np.abs(out - want_out).max() <= 1e-4
     assert np.abs(aw - want_w).max() <= 1e-5

@@ -68,6 +68,7 @@ def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "zebra_amd.h"))
+    hook_headers = headers + [os.path.join(CSRC, "test_hooks.h")]      # the hooks' own declarations
     objs = []
     rebuilt = False
     for src, extra in SOURCES.items():
@@ -92,7 +93,7 @@ def build(force=False, verbose=False):
     for src, extra in HOOK_SOURCES.items():
         sp = os.path.join(CSRC, src)
         op = os.path.join(LIBDIR, src.replace(".hip", ".o"))
-        if force or _newer(sp, op) or any(_newer(h, op) for h in headers):
+        if force or _newer(sp, op) or any(_newer(h, op) for h in hook_headers):
             subprocess.run([hipcc] + COMMON + extra + ["-c", sp, "-o", op], check=True)
             hrebuilt = True
         hobjs.append(op)

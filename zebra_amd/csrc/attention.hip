@@ -78,12 +78,6 @@ __device__ inline void lds_linear(const float *X, int ldx, int mt, const float *
     }
 }
 
-struct AttnDims {
-    int D, F, T, E, Ek, heads, hd, hidden, out_dim, k;
-    int Ep, Ekp, E2p, Hp, Op;       // padded widths: E, Ek, E+D, hidden, out_dim
-    int rq, mt, lda, ldk, ldq;
-};
-
 __global__ __launch_bounds__(ATT_THREADS) void k_temporal_attention(
     AttnDims d, long long N, const float *__restrict__ src, const float *__restrict__ src_t,
     const float *__restrict__ nf, const float *__restrict__ ef, const float *__restrict__ ntf,
@@ -207,9 +201,14 @@ __global__ __launch_bounds__(ATT_THREADS) void k_temporal_attention(
     }
 }
 
-bool attn_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, AttnDims &d, size_t &lds, size_t off[8],
-               size_t &ws)
+}  // namespace
+
+// The one place that decides which shapes the layer takes and how a workgroup is tiled (common.hpp; pinned without a GPU
+// through zt_test_attention_plan, tests/test_attention_cpu.py).
+bool zt::attention_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, AttnDims &d, size_t &lds, size_t off[8],
+                        size_t &ws)
 {
+    if (D <= 0 || F < 0 || T <= 0 || k <= 0 || hidden <= 0 || out_dim <= 0) return false;
     d.D = D; d.F = F; d.T = T; d.E = D + T; d.Ek = D + F + T; d.heads = heads; d.hidden = hidden; d.out_dim = out_dim;
     d.k = k;
     if (heads <= 0 || heads > 4 || d.E % heads) return false;
@@ -223,16 +222,18 @@ bool attn_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, A
         const size_t kv = std::max((size_t)m * 16 * d.ldk, (size_t)16 * d.ldq);   // K/V tile, later the merger input
         return ((size_t)m * 16 * d.lda + kv) * 4 + (size_t)2 * 16 * d.ldq * 4 + (size_t)m * 16 * 4 * 4 + 64;
     };
-    while (mt > 1 && bytes(mt) > 158 * 1024) --mt;
+    while (mt > 1 && bytes(mt) > ATT_LDS_BOUND) --mt;
     int rq = (mt * 16) / k;
     if (rq < 1) {
         mt = (k + 15) / 16; rq = 1;
-        if (mt > ATT_MAX_MT || bytes(mt) > 158 * 1024) return false;
+        if (mt > ATT_MAX_MT) return false;
     }
     if (rq > 16) rq = 16;
     mt = (rq * k + 15) / 16;
     d.rq = rq; d.mt = mt;
     lds = bytes(mt);
+    // the tile that is launched must fit: the loop above stops at one M-tile whether or not that one fits (D = T = 228, k = 10)
+    if (lds > ATT_LDS_BOUND) return false;
     size_t o = 0;
     auto take = [&](size_t b) { size_t r = o; o += (b + 255) & ~(size_t)255; return r; };
     off[0] = take((size_t)d.Ep * d.Ep * 4);    // Wq
@@ -245,15 +246,12 @@ bool attn_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, A
     return true;
 }
 
-}  // namespace
-
 extern "C" int64_t zt_attention_workspace_bytes(int32_t D, int32_t F, int32_t T, int32_t n_head, int32_t hidden,
                                                 int32_t out_dim, int32_t k)
 {
     AttnDims d;
     size_t lds, off[8], ws;
-    if (D <= 0 || F < 0 || T <= 0 || k <= 0 || hidden <= 0 || out_dim <= 0) return -1;
-    if (!attn_plan(D, F, T, n_head, hidden, out_dim, k, d, lds, off, ws)) return -1;
+    if (!attention_plan(D, F, T, n_head, hidden, out_dim, k, d, lds, off, ws)) return -1;
     return (int64_t)ws;
 }
 
@@ -272,8 +270,8 @@ extern "C" int zt_temporal_attention(const float *src_dev, const float *src_time
     }
     AttnDims d;
     size_t lds, off[8], ws;
-    if (!attn_plan(D, F, T, n_head, hidden, out_dim, k, d, lds, off, ws)) {
-        set_error("zt_temporal_attention: unsupported shape (heads<=4, E %% heads == 0, k rows must fit the LDS tile)");
+    if (!attention_plan(D, F, T, n_head, hidden, out_dim, k, d, lds, off, ws)) {
+        set_error("zt_temporal_attention: unsupported shape (heads<=4, E %% heads == 0, k <= 80 rows must fit the LDS tile)");
         return ZT_ERR_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;

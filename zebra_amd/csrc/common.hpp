@@ -184,6 +184,19 @@ struct GroupPlan {
     int limit;
 };
 GroupPlan pipeline_group_plan(bool streaming, int release, int want, int n_more);
+// The attention layer's tile for one shape (attention.hip: attention_plan).  One workgroup takes rq query rows (at most 16) and
+// their rq * k key rows in mt 16-row M-tiles (at most 5); lda / ldk / ldq are the leading dimensions of its LDS regions.
+struct AttnDims {
+    int D, F, T, E, Ek, heads, hd, hidden, out_dim, k;
+    int Ep, Ekp, E2p, Hp, Op;       // padded widths: E, Ek, E+D, hidden, out_dim
+    int rq, mt, lda, ldk, ldq;
+};
+constexpr size_t ATT_LDS_BOUND = 158 * 1024;
+// Pure host code (no HIP calls).  false: the shape is refused (a bad width, heads outside 1 ... 4 or not dividing E, a query
+// row's k key rows beyond 5 M-tiles, or a tile whose dynamic LDS `lds` would exceed ATT_LDS_BOUND).  off[0 .. 5]: the padded
+// weights' offsets in the workspace of `ws` bytes
+bool attention_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, AttnDims &d, size_t &lds, size_t off[8],
+                    size_t &ws);
 // zt_link_metrics with a second destination: row (or NULL) receives the batch's three values whatever `accumulate` does to out
 // (the metrics tail of the native step, pipeline.hip: the running sum and the per-batch table from one launch)
 int link_metrics_launch(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int accumulate, double *row_dev,

@@ -45,6 +45,10 @@ int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F,
  * ZT_CHOICE_SCORE selection.  out[7] = form (0 refused, 1 latency, 2 tiled, 3 generic latency, 4 generic tiled: the ZT_SCORE_*
  * values), KC, ET (the specialised forms' template arguments, else 0), grid x, grid y, threads per workgroup, dynamic LDS. */
 int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64_t *out);
+/* Test hook: the attention layer's tile for one shape (zt::attention_plan, host code only).  out[4] = supported (0 / 1), rq (query
+ * rows per workgroup), mt (16-row M-tiles of key rows), dynamic LDS bytes; the last three are 0 where the shape is refused. */
+int zt_test_attention_plan(int32_t D, int32_t F, int32_t T, int32_t n_head, int32_t hidden, int32_t out_dim, int32_t k,
+                           int64_t *out);
 /* Test hook: one pipeline step's choices (zt::pipeline_step_plan, host code only).  The facts, 0 / 1 unless said otherwise:
  * streaming (else pruning), masked, release (the ZT_CHOICE_GROUP_RELEASE value), B, row_lo, row_hi, scoring, metrics, exchange,
  * avg_topk, proj_table (each: attached), wm_ready (the padded W_m is in the embed workspace); the current member's slot:

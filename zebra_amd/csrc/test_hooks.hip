@@ -150,6 +150,18 @@ extern "C" int zt_test_affinity_plan(int64_t B, int32_t H, int32_t choice, int64
     return ZT_OK;
 }
 
+extern "C" int zt_test_attention_plan(int32_t D, int32_t F, int32_t T, int32_t n_head, int32_t hidden, int32_t out_dim, int32_t k,
+                                      int64_t *out)
+{
+    if (!out) return ZT_ERR_ARG;
+    AttnDims d;
+    size_t lds = 0, off[8], ws = 0;
+    const bool ok = attention_plan(D, F, T, n_head, hidden, out_dim, k, d, lds, off, ws);
+    const int64_t v[4] = {ok ? 1 : 0, ok ? d.rq : 0, ok ? d.mt : 0, ok ? (int64_t)lds : 0};
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
+    return ZT_OK;
+}
+
 extern "C" int zt_test_step_plan(int32_t streaming, int32_t masked, int32_t release, int64_t B, int64_t row_lo, int64_t row_hi,
                                  int32_t scoring, int32_t metrics, int32_t exchange, int32_t avg_topk, int32_t proj_table,
                                  int32_t wm_ready, int32_t by_member, int32_t tail_gated, int32_t waited, int32_t have_next,

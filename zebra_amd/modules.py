@@ -894,7 +894,10 @@ class TemporalAttentionLayer(nn.Module):
         c = lambda t: t.detach().contiguous().float()
         ten = [c(src_node_features), c(src_time_features.reshape(N, T)), c(neighbors_features), c(edge_features),
                c(neighbors_time_features), neighbors_padding_mask.detach().to(torch.uint8).contiguous()]
-        wts = [c(mha.q_proj_weight), c(mha.k_proj_weight), c(mha.v_proj_weight), c(mha.in_proj_bias),
+        # F = 0: kdim == embed_dim, and nn.MultiheadAttention then keeps one packed in_proj_weight [3E][E] instead of the three
+        qkv = mha.in_proj_weight.chunk(3) if mha._qkv_same_embed_dim else (mha.q_proj_weight, mha.k_proj_weight,
+                                                                            mha.v_proj_weight)
+        wts = [c(qkv[0]), c(qkv[1]), c(qkv[2]), c(mha.in_proj_bias),
                c(mha.out_proj.weight), c(mha.out_proj.bias), c(self.merger.fc1.weight), c(self.merger.fc1.bias),
                c(self.merger.fc2.weight), c(self.merger.fc2.bias)]
         aw = _capi.AttnWeights(*[ptr(t) for t in wts])
