@@ -895,7 +895,12 @@ def test_device_side_evaluation_matches_reference_protocol():
     (evaluation/evaluation.py:7-48) -- same model, same sampler seed."""
     import math
     import types
-    sk = pytest.importorskip("sklearn.metrics")
+    try:                                 # the exact counts of oracle/metrics_exact.py hold it either way
+        import sklearn.metrics as sk
+    except ImportError:
+        sk = None
+    from test_metrics_exact_gpu import oracle as exact_oracle
+    metrics_exact = exact_oracle()
     from zebra_amd import evaluation as ev
     name = "d100_f1"
     N, E, D, F, T, k, al, be, seed, bs, nb = I.EMBED_CASES[name]
@@ -922,7 +927,7 @@ def test_device_side_evaluation_matches_reference_protocol():
     model = build_tgn(N, E + 1, D, F, T, k, al, be, w, efeat).eval()
     smp = Sampler(dst, 7)
     smp.reset_random_state()
-    aps, aucs, accs = [], [], []
+    aps, aucs, accs, exact = [], [], [], []
     with torch.no_grad():
         for b in range(math.ceil(len(src) / batch)):
             s, e = b * batch, min(len(src), (b + 1) * batch)
@@ -931,11 +936,17 @@ def test_device_side_evaluation_matches_reference_protocol():
             pos, ng = pos.cpu().numpy(), ng.cpu().numpy()
             y = np.concatenate([np.ones(e - s), np.zeros(e - s)])
             sc = np.concatenate([pos, ng])
-            aps.append(sk.average_precision_score(y, sc))
-            aucs.append(sk.roc_auc_score(y, sc))
-            accs.append(sk.accuracy_score(np.zeros(e - s), np.argmax(np.hstack([pos, ng]), axis=1)))
-    want = (np.mean(aps), np.mean(aucs), np.mean(accs))
+            exact.append(metrics_exact.link_metrics_exact(pos, ng))
+            assert exact[-1][2] == float(np.mean(np.argmax(np.hstack([pos, ng]), axis=1) == 0))
+            if sk is not None:
+                aps.append(sk.average_precision_score(y, sc))
+                aucs.append(sk.roc_auc_score(y, sc))
+                accs.append(sk.accuracy_score(np.zeros(e - s), np.argmax(np.hstack([pos, ng]), axis=1)))
+    want = np.mean(exact, axis=0)
     assert np.allclose(got, want, rtol=0, atol=1e-9), (got, want)
+    if sk is not None:
+        want = (np.mean(aps), np.mean(aucs), np.mean(accs))
+        assert np.allclose(got, want, rtol=0, atol=1e-9), (got, want)
 
 
 def test_training_step_gradients_match_reference():

@@ -1,9 +1,11 @@
 """Per-batch AP / AUC / accuracy inside the native step loop (csrc/scoring.hip: the two-run form of the metrics kernel for
 8193 .. 16384 pairs; csrc/pipeline.hip: zt_pipeline_set_metrics / zt_pipeline_metrics; TGN.enable_metrics / metrics;
 evaluation.eval_edge_prediction(native=True)) against the float64 torch composition of zebra_amd.evaluation on the CPU (what
-tests/test_evaluation_cpu.py holds against scikit-learn), against scikit-learn itself where it imports, and against the same
-batches stepped one by one."""
+tests/test_evaluation_cpu.py holds against exact counts), against the exact counts of oracle/metrics_exact.py, against
+scikit-learn where it imports, and against the same batches stepped one by one."""
 import math
+import os
+import sys
 import types
 
 import numpy as np
@@ -11,6 +13,7 @@ import pytest
 import torch
 
 import inputs as I
+from conftest import ROOT
 from helpers import build_tgn
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +26,15 @@ def composition(pos, neg):
     p = torch.as_tensor(np.asarray(pos.detach().cpu() if torch.is_tensor(pos) else pos)).to(torch.float64)
     n = torch.as_tensor(np.asarray(neg.detach().cpu() if torch.is_tensor(neg) else neg)).to(torch.float64)
     return np.array([float(ev.average_precision(p, n)), float(ev.roc_auc(p, n)), float(ev.accuracy(p, n))])
+
+
+def exact_metrics(pos, neg):
+    """(AP, AUC, accuracy) from integer counts: oracle/metrics_exact.py"""
+    p = os.path.join(ROOT, "oracle")
+    if p not in sys.path:
+        sys.path.insert(0, p)
+    import metrics_exact
+    return metrics_exact.link_metrics_exact(pos, neg)
 
 
 def draw(B, ties, seed=None):
@@ -67,9 +79,16 @@ def test_wide_form_matches_the_float64_composition(B, ties):
 @pytest.mark.parametrize("B", [8193, 12000, 16384])
 @pytest.mark.parametrize("ties", [False, True])
 def test_wide_form_matches_sklearn(B, ties):
-    sk = pytest.importorskip("sklearn.metrics")
+    """against the exact counts of oracle/metrics_exact.py always, and against scikit-learn where it imports"""
     pos, neg = draw(B, ties)
     got = kernel(pos, neg).cpu().numpy()
+    want = exact_metrics(pos, neg)
+    assert want[2] == float(np.mean(pos >= neg))
+    assert np.allclose(got, want, rtol=0, atol=ATOL), (got, want)
+    try:
+        import sklearn.metrics as sk
+    except ImportError:
+        return
     y = np.concatenate([np.ones(B), np.zeros(B)])
     sc = np.concatenate([pos, neg]).astype(np.float64)
     want = [sk.average_precision_score(y, sc), sk.roc_auc_score(y, sc), float(np.mean(pos >= neg))]

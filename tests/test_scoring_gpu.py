@@ -63,9 +63,14 @@ def test_affinity_follows_weight_changes():
 def test_link_metrics_kernel_matches_sklearn(B, ties):
     """zt_link_metrics (one kernel: sort, scans, curve sums in float64) against scikit-learn's average_precision_score /
     roc_auc_score / the reference's accuracy (evaluation/evaluation.py:40-45) and against the torch composition of
-    zebra_amd.evaluation, with heavy ties (scores rounded to one decimal) and without; then the accumulating form."""
-    sk = pytest.importorskip("sklearn.metrics")
+    zebra_amd.evaluation, with heavy ties (scores rounded to one decimal) and without; then the accumulating form.  The exact
+    counts of oracle/metrics_exact.py hold it whether scikit-learn imports or not."""
     from zebra_amd import evaluation as ev
+    from test_metrics_exact_gpu import oracle as exact_oracle
+    try:
+        import sklearn.metrics as sk
+    except ImportError:
+        sk = None
     rng = np.random.RandomState(B + (7 if ties else 0))
     pos = np.clip(rng.normal(0.65, 0.2, B), 0, 1).astype(np.float32)
     neg = np.clip(rng.normal(0.4, 0.2, B), 0, 1).astype(np.float32)
@@ -75,14 +80,20 @@ def test_link_metrics_kernel_matches_sklearn(B, ties):
     got = ev.link_metrics(p, n).cpu().numpy()
     y = np.concatenate([np.ones(B), np.zeros(B)])
     sc = np.concatenate([pos, neg]).astype(np.float64)
-    want = [sk.average_precision_score(y, sc), sk.roc_auc_score(y, sc) if B > 0 else 0.0, float(np.mean(pos >= neg))]
+    want = exact_oracle().link_metrics_exact(pos, neg)
+    assert want[2] == float(np.mean(pos >= neg))
     assert np.allclose(got, want, rtol=0, atol=1e-12), (got, want)
+    if sk is not None:
+        want_sk = [sk.average_precision_score(y, sc), sk.roc_auc_score(y, sc) if B > 0 else 0.0, float(np.mean(pos >= neg))]
+        assert np.allclose(got, want_sk, rtol=0, atol=1e-12), (got, want_sk)
     comp = torch.stack([ev.average_precision(p, n), ev.roc_auc(p, n), ev.accuracy(p, n)]).cpu().numpy()
     assert np.allclose(got, comp, rtol=0, atol=1e-12)
     acc = torch.zeros(3, dtype=torch.float64, device="cuda")
     ev.link_metrics(p, n, out=acc)
     ev.link_metrics(p, n, out=acc)
     assert np.allclose(acc.cpu().numpy(), 2 * np.asarray(want), rtol=0, atol=1e-11)
+    if sk is not None:
+        assert np.allclose(acc.cpu().numpy(), 2 * np.asarray(want_sk), rtol=0, atol=1e-11)
 
 
 @pytest.mark.parametrize("strategy", ["streaming"])

@@ -370,10 +370,12 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_affinity_gen_tiled(const floa
 constexpr int MT_THREADS = 1024;
 constexpr int MT_MAX = 16384;            // scores per call (2B) of the single form: 128 KB of LDS keys
 
-// float -> unsigned whose ascending order is the DESCENDING order of the floats (NaN-free scores)
+// float -> unsigned whose ascending order is the DESCENDING order of the floats (NaN-free scores).  -0.0 takes +0.0's key:
+// the two compare equal, so they are ONE threshold of the curves (by their bits they would be two)
 __device__ __forceinline__ unsigned desc_key(float x)
 {
-    const unsigned u = __float_as_uint(x);
+    const unsigned bits = __float_as_uint(x);
+    const unsigned u = bits == 0x80000000u ? 0u : bits;
     const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ~asc;
 }

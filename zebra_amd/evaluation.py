@@ -68,8 +68,8 @@ def link_metrics(pos, neg, out=None):
     up to 16384 pairs go through ONE HIP kernel (zt_link_metrics, csrc/scoring.hip: bitonic sort in LDS + the two curve
     sums, in the form zt_link_metrics_plan picks -- one sort of (key | label) words up to 8192 pairs, the positives and the
     negatives as two sorted runs beyond; ``out`` given: the values are ADDED to it there, no extra op); anything else through
-    the torch ops above -- the same definitions, which the CPU tests hold against scikit-learn and the GPU tests against each
-    other."""
+    the torch ops above -- the same definitions; the tests hold both to exact integer counts (oracle/metrics_exact.py).
+    -0.0 and +0.0 are one threshold; NaN scores are outside the contract."""
     pos, neg = pos.reshape(-1), neg.reshape(-1)
     if pos.is_cuda and pos.dtype == torch.float32 and neg.dtype == torch.float32 and 0 < pos.numel() == neg.numel() <= 16384:
         import ctypes as C
