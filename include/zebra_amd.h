@@ -858,6 +858,44 @@ int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, 
                      void *workspace_dev, int64_t workspace_bytes, void *stream);
 int zt_affinity_topk_plan(int64_t Q, int64_t Nc, int64_t C, int32_t H, int32_t K, int32_t indexed,
                           int64_t workspace_bytes, int64_t *plan_out);
+/* zt_affinity_topk with a per-query set of absent columns.  ABSENT BITS: absent_dev [Q][absent_words] (uint32),
+ * absent_words >= ceil(C / 32); bit c & 31 of word c >> 5 of row q, when set, means that the LOCAL column c in [0, C) of this
+ * call (not idx_base + c) is not present for query q; bits at columns >= C are zero.  zt_exclude_mark writes this format.
+ * Present: zt_affinity_topk's rule, and the column's bit is clear -- in the shared form every query tests its own row of bits,
+ * whatever slab or span the column falls in.  A query whose columns are all absent gives -1 and 0 in every slot.  The plan,
+ * the workspace (layout and size), the merge, accumulate, skip_dev, the NaN rule and the status word are zt_affinity_topk's;
+ * under accumulate each piece of a pool comes with its own local bits.  absent_dev == NULL: zt_affinity_topk exactly.
+ * A non-NULL absent_dev with absent_words < ceil(C / 32): ZT_ERR_ARG before any device call; every other error is
+ * zt_affinity_topk's. */
+int zt_affinity_topk_masked(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                            const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w,
+                            int32_t K, const int32_t *skip_dev, int64_t idx_base, int32_t accumulate,
+                            int32_t *top_idx_dev, float *top_prob_dev,
+                            void *workspace_dev, int64_t workspace_bytes,
+                            const uint32_t *absent_dev, int64_t absent_words, void *stream);
+/* Exclusion lists from the adjacency (csrc/seen.hip).  For query (v, t) = (q_nodes_dev[q], q_ts_dev[q]): begin_dev[q] =
+ * indptr[v], len_dev[q] = the number of v's entries with a timestamp strictly below t -- the prefix zt_csr_find_before
+ * returns, so an entry AT t is not seen.  The partners themselves are entries [begin, begin + len) of the handle's neighbour
+ * array, duplicates included.  v < 0 or v >= num_nodes: len 0, and ZT_ERR_RANGE in *status_dev (the caller zeroes it; read it
+ * once the stream has passed the call).  NULL pointers or Q < 0: ZT_ERR_ARG before any device call; Q = 0: ZT_OK, nothing
+ * touched. */
+int zt_csr_seen_ranges(const zt_csr *c, const int32_t *q_nodes_dev, const double *q_ts_dev, int64_t Q,
+                       int64_t *begin_dev, int64_t *len_dev, int32_t *status_dev, void *stream);
+/* Absent bits (above) from per-query id lists: query q's list is ids[begin_dev[q] .. begin_dev[q] + len_dev[q]), ids being
+ * ids_dev, or the handle's neighbour array when ids_dev is NULL (c may be NULL otherwise) -- a "seen" list is never copied;
+ * ranges of the handle's array are clipped to it.  Lists may hold duplicates, any order, and ids that are not in the pool,
+ * negative ones among them: those are ignored.  EVERY word of absent_dev [Q][absent_words] is written; the caller does not
+ * zero it.  How an id becomes columns:
+ *   range           cand_sorted_dev == NULL: column id - id_lo where that is in [0, C);
+ *   shared list     cand_stride == 0: cand_sorted_dev [C] holds the pool's ids in ascending order (-1 entries first) and
+ *                   cand_col_dev [C] the column each came from; every column whose id equals a list entry is set;
+ *   per-query list  cand_stride == C: the same with row q of [Q][C] tables.
+ * Integer ORs: the result is a function of the inputs alone.  NULL begin / len / absent, both c and ids_dev NULL, negative
+ * Q, C or absent_words, absent_words < ceil(C / 32), a list without its columns or another stride: ZT_ERR_ARG before any
+ * device call.  Q = 0 or absent_words = 0: ZT_OK, nothing touched. */
+int zt_exclude_mark(const zt_csr *c, const int32_t *ids_dev, const int64_t *begin_dev, const int64_t *len_dev, int64_t Q,
+                    int64_t id_lo, const int32_t *cand_sorted_dev, const int32_t *cand_col_dev, int64_t cand_stride,
+                    int64_t C, uint32_t *absent_dev, int64_t absent_words, void *stream);
 /* Ranks, MRR and Hits@k of prob_dev [Q][C] (cand_idx_dev as above, may be NULL: every entry present).  Column 0 is the
  * positive:  rank = 1 + #{c >= 1 present : p_c > p_0} + 0.5 #{c >= 1 present : p_c == p_0}, the mean of the optimistic and
  * the pessimistic rank.  A query whose column 0 is absent is skipped and not counted.  rank_dev [Q] (or NULL) receives the

@@ -36,6 +36,7 @@ SYMBOLS = [
     "zt_link_bce_forward", "zt_link_bce_backward", "zt_adam_step", "zt_adam_plan",
     "zt_tppr_query", "zt_affinity_rank_workspace_bytes", "zt_affinity_rank", "zt_rank_metrics",
     "zt_affinity_topk_workspace_bytes", "zt_affinity_topk", "zt_affinity_topk_plan",
+    "zt_affinity_topk_masked", "zt_csr_seen_ranges", "zt_exclude_mark",
 ]
 
 

@@ -36,6 +36,7 @@ SOURCES = {
     "scoring_train.hip": [],
     "rank.hip": [],
     "rank_topk.hip": [],
+    "seen.hip": [],
     "train_tail.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],

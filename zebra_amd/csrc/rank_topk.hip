@@ -6,6 +6,9 @@
 //                      registers and leaves one list per (query, span) in the workspace;
 //     k_topk_merge     a wave per query merges the spans' lists -- and the list already in the output, from the slabs before or
 //                      from the caller (accumulate) -- and writes the K results.
+//   zt_affinity_topk_masked  the same with ABSENT BITS absent[Q][W] (seen.hip writes them): a set bit takes local column c out of
+//                      query q's candidates.  k_topk_pairs<., ., true> folds the bit into `present`; the plan, the workspace and
+//                      the merge are the unmasked call's.
 //   No workgroup waits for another, no atomics but atomicExch on the status word, every loop bounded by its arguments.
 // A candidate is a 64-bit key (probability bits << 32) | ~index: probabilities are >= +0, so the bits order as unsigned, and
 // among equal probabilities the smaller index has the larger key.  Keys are distinct (indices are), the order is strict and
@@ -77,6 +80,8 @@ struct TopkArgs {
     const float *b1, *w2, *b2;
     u64 *part;                        // [Q][n_spans][K]
     int *status;
+    const unsigned *absent;           // [Q][absent_words] or NULL: read by the MASKED instantiations alone
+    long long absent_words;
 };
 
 __device__ __forceinline__ u64 tk_readlane(u64 v, int src)
@@ -147,9 +152,12 @@ __device__ __forceinline__ void tk_offer(u64 (&m)[NR], u64 &kth, u64 key, int K,
 //   NQ = 1 (indexed): wave w owns query q0 + w and walks the span's index columns 32 at a time, as k_rank_pairs does; rows
 //        outside the slab are passed over (another slab's launch takes them).
 // NR: u64 registers per lane and list (1: K <= 64; 4: K <= 256).
+// MASKED: a candidate is present only if its bit of a.absent is clear -- bit c of row q, c the LOCAL column of the call
+//        (a.r0 + mycol in the shared form: the slab's offset counts; mycol in the indexed form); every query of a wave tests
+//        its own row.  The word is loaded ahead of the pair sum, once per wave.  false: none of this is compiled in.
 // The (P_q + b1) rows and w2 lie in LDS a chunk of RK_HC columns at a time: H <= RK_HC loads them once, wider rows once per
 // step and chunk.  The pair sum is rank_pair.hpp's.
-template <int NQ, int NR>
+template <int NQ, int NR, bool MASKED = false>
 __global__ __launch_bounds__(WAVE * TK_WAVES) void k_topk_pairs(const TopkArgs a)
 {
     __shared__ float4 s_q[RK_TQ][RK_HC / 4];
@@ -211,6 +219,19 @@ __global__ __launch_bounds__(WAVE * TK_WAVES) void k_topk_pairs(const TopkArgs a
         // a NaN anywhere in a candidate's embedding makes its whole projected row NaN; the pair sum's relu (fmaxf) would drop
         // it and zt_affinity_rank writes a finite number there -- here such a candidate is a NaN candidate: never selected
         const bool nan_row = myrow >= 0 && a.Pc[(long long)myrow * H] != a.Pc[(long long)myrow * H];
+        // MASKED: the wave's RK_TC = 32 columns of this step lie in ONE word of a query's bits -- spans begin at multiples of
+        // the step and slabs at multiples of 32 rows (topk_plan) --, so the word's address is the same in every lane
+        unsigned gone[NQ];
+        if (MASKED) {
+            static_assert(RK_TC == 32, "one word of absent bits per wave and step");
+            const long long wcol = lo + t * step_cols + (shared ? __builtin_amdgcn_readfirstlane(wave) * RK_TC : 0);
+            const long long word = ((shared ? a.r0 : 0) + wcol) >> 5;      // < ceil(C / 32) wherever wcol < hi
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) {
+                const long long q = q0 + (shared ? qi : __builtin_amdgcn_readfirstlane(wave));
+                gone[qi] = (wcol < hi && q < a.Q) ? a.absent[q * a.absent_words + word] : 0u;
+            }
+        }
         int row[RK_NC];
 #pragma unroll
         for (int j = 0; j < RK_NC; ++j)          // pair j's row from the lane of this group that owns it (bit 0 of gl clear)
@@ -249,7 +270,8 @@ __global__ __launch_bounds__(WAVE * TK_WAVES) void k_topk_pairs(const TopkArgs a
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
             const float p = rk_prob(rk_fold16x8(acc[qi], gl), bias2);
-            const bool present = myrow >= 0 && !nan_row && (gl & 1) == 0 && p == p && q0 + (shared ? qi : wave) < a.Q && gcol != skipc[qi];
+            bool present = myrow >= 0 && !nan_row && (gl & 1) == 0 && p == p && q0 + (shared ? qi : wave) < a.Q && gcol != skipc[qi];
+            if (MASKED) present = present && ((gone[qi] >> (mycol & 31)) & 1u) == 0u;
             tk_offer<NR>(m[qi], kth[qi], present ? tk_key(p, gcol) : 0ull, K, lane);
         }
     }
@@ -386,13 +408,19 @@ extern "C" int zt_affinity_topk_plan(int64_t Q, int64_t Nc, int64_t C, int32_t H
     return ZT_OK;
 }
 
-extern "C" int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
-                                const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w, int32_t K,
-                                const int32_t *skip_dev, int64_t idx_base, int32_t accumulate, int32_t *top_idx_dev,
-                                float *top_prob_dev, void *workspace_dev, int64_t workspace_bytes, void *stream)
+// zt_affinity_topk and zt_affinity_topk_masked (absent_dev NULL: the former exactly)
+static int topk_run(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc, const int32_t *cand_idx_dev, int64_t C,
+                    int32_t H, const zt_affinity_weights *w, int32_t K, const int32_t *skip_dev, int64_t idx_base,
+                    int32_t accumulate, int32_t *top_idx_dev, float *top_prob_dev, void *workspace_dev, int64_t workspace_bytes,
+                    const uint32_t *absent_dev, int64_t absent_words, void *stream)
 {
     if (!emb_q_dev || !emb_c_dev || !w || !top_idx_dev || !top_prob_dev || !workspace_dev || Q < 0 || Nc < 0 || C < 0 || idx_base < 0) {
         set_error("zt_affinity_topk: bad argument");
+        return ZT_ERR_ARG;
+    }
+    if (absent_dev != nullptr && absent_words < (C + 31) / 32) {
+        set_error("zt_affinity_topk_masked: absent_words=%lld, C=%lld columns need %lld", (long long)absent_words, (long long)C,
+                  (long long)((C + 31) / 32));
         return ZT_ERR_ARG;
     }
     int rc = topk_check_shape("zt_affinity_topk", H, K);
@@ -445,6 +473,8 @@ extern "C" int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *
     a.H = H; a.K = K;
     a.b1 = w->fc1_b; a.w2 = w->fc2_w; a.b2 = w->fc2_b;
     a.part = part; a.status = status;
+    a.absent = absent_dev; a.absent_words = absent_words;
+    const bool masked = absent_dev != nullptr;
     for (long long slab = 0; slab < p.n_slabs; ++slab) {
         a.r0 = slab * p.slab_rows;
         a.rows = std::min<long long>(p.slab_rows, Nc - a.r0);
@@ -454,12 +484,18 @@ extern "C" int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *
         const unsigned g1 = (unsigned)p.grid1, g2 = (unsigned)p.grid2, th = WAVE * TK_WAVES;
         const int acc = (accumulate != 0 || slab > 0) ? 1 : 0;
         if (p.form == ZT_TOPK_FORM_LANE) {
-            if (p.nq == 1) k_topk_pairs<1, 1><<<g1, th, 0, s>>>(a);
+            if (masked) {
+                if (p.nq == 1) k_topk_pairs<1, 1, true><<<g1, th, 0, s>>>(a);
+                else k_topk_pairs<RK_TQ, 1, true><<<g1, th, 0, s>>>(a);
+            } else if (p.nq == 1) k_topk_pairs<1, 1><<<g1, th, 0, s>>>(a);
             else k_topk_pairs<RK_TQ, 1><<<g1, th, 0, s>>>(a);
             ZT_LAUNCH_CHECK();
             k_topk_merge<1><<<g2, th, 0, s>>>(part, Q, p.n_spans, K, acc, top_idx_dev, top_prob_dev);
         } else {
-            if (p.nq == 1) k_topk_pairs<1, 4><<<g1, th, 0, s>>>(a);
+            if (masked) {
+                if (p.nq == 1) k_topk_pairs<1, 4, true><<<g1, th, 0, s>>>(a);
+                else k_topk_pairs<RK_TQ, 4, true><<<g1, th, 0, s>>>(a);
+            } else if (p.nq == 1) k_topk_pairs<1, 4><<<g1, th, 0, s>>>(a);
             else k_topk_pairs<RK_TQ, 4><<<g1, th, 0, s>>>(a);
             ZT_LAUNCH_CHECK();
             k_topk_merge<4><<<g2, th, 0, s>>>(part, Q, p.n_spans, K, acc, top_idx_dev, top_prob_dev);
@@ -468,4 +504,23 @@ extern "C" int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *
         ZT_PROF_END(s, P_SCORE);
     }
     return ZT_OK;
+}
+
+extern "C" int zt_affinity_topk(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                                const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w, int32_t K,
+                                const int32_t *skip_dev, int64_t idx_base, int32_t accumulate, int32_t *top_idx_dev,
+                                float *top_prob_dev, void *workspace_dev, int64_t workspace_bytes, void *stream)
+{
+    return topk_run(emb_q_dev, Q, emb_c_dev, Nc, cand_idx_dev, C, H, w, K, skip_dev, idx_base, accumulate, top_idx_dev, top_prob_dev,
+                    workspace_dev, workspace_bytes, nullptr, 0, stream);
+}
+
+extern "C" int zt_affinity_topk_masked(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                                       const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w, int32_t K,
+                                       const int32_t *skip_dev, int64_t idx_base, int32_t accumulate, int32_t *top_idx_dev,
+                                       float *top_prob_dev, void *workspace_dev, int64_t workspace_bytes,
+                                       const uint32_t *absent_dev, int64_t absent_words, void *stream)
+{
+    return topk_run(emb_q_dev, Q, emb_c_dev, Nc, cand_idx_dev, C, H, w, K, skip_dev, idx_base, accumulate, top_idx_dev, top_prob_dev,
+                    workspace_dev, workspace_bytes, absent_dev, absent_words, stream);
 }

@@ -10,6 +10,7 @@
 // The list layout, the walk, the duplicate sum and the row writers are the same code for both (prune_walk.hpp, over a
 // wavefront or a workgroup); each kernel has its own merge (all pairs / hash table) and selection (numba_sort.hpp's
 // wave-parallel argsort / radix select), which are different algorithms for different sizes.
+#include "csr_handle.hpp"
 #include "numba_sort.hpp"
 
 #include <algorithm>
@@ -17,24 +18,6 @@
 #include <vector>
 
 using namespace zt;
-
-struct zt_csr {
-    int64_t N, E2;
-    long long *indptr;  // device [N+1]
-    int *nbr, *eid;     // device [2E]
-    double *ts;         // device [2E]
-    // host mirror (find_before on the host side of the shim, tests)
-    std::vector<long long> h_indptr;
-    std::vector<int> h_nbr, h_eid;
-    std::vector<double> h_ts;
-    // the workspace form's reservation (zt_csr_reserve_pruning); the query entry points take the handle const
-    mutable void *ws = nullptr;              // device: ws_slabs x ws_slab_bytes
-    long long ws_slab_bytes = 0;
-    int ws_slabs = 0, ws_cap_c = 0, ws_cap_f = 0, ws_models = 0;
-    hipEvent_t ws_event = nullptr;           // recorded after every workspace launch
-    mutable hipStream_t ws_stream = nullptr; // the stream of the last one
-    mutable bool ws_used = false;
-};
 
 namespace {
 

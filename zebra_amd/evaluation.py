@@ -176,13 +176,20 @@ def rank_metrics(prob, cand_idx=None, out=None, ranks=False):
 
 
 @torch.no_grad()
-def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_size=200, n_negatives=100):
+def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_size=200, n_negatives=100, filtered=False,
+                      finder=None):
     """Link prediction by rank, what temporal-graph benchmarks report: per batch, ``B * n_negatives`` negatives from ONE
     ``sampler.sample`` call, reshaped [B, n_negatives]; every source ranks [destination | its negatives] read-only from the
     state BEFORE the batch (TGN.rank_candidates), zt_rank_metrics accumulates on the device; then the state advances with the
     ordinary eval step, whose single negative is the first column.  Returns dict(mrr, hits1, hits3, hits10) from one host
-    read at the end.  The model runs without the native pipeline."""
+    read at the end.  The model runs without the native pipeline.
+    ``filtered=True`` is the filtered protocol: a negative does not count where it is one of the source's true partners --
+    a partner strictly before the edge's timestamp in ``finder`` (None: ``model.neighbor_finder``; ValueError if there is
+    none), or the edge's own destination.  The positive, column 0, always counts.  The absent columns are marked on the device
+    (TGN.absent_bits) and reach zt_rank_metrics as cand_idx = -1; still one host read at the end."""
     assert negative_edge_sampler.seed is not None
+    if filtered and finder is None and model.neighbor_finder is None:
+        raise ValueError("eval_edge_ranking(filtered=True) needs a finder: the model has no neighbor_finder")
     negative_edge_sampler.reset_random_state()
     model = model.eval()
     if not model.test_mode:                                      # (as the eval step begins)
@@ -196,7 +203,16 @@ def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_siz
         negatives = np.asarray(negatives).reshape(e - s, n_negatives)
         cands = np.concatenate([np.asarray(data.destinations[s:e]).reshape(-1, 1), negatives], axis=1)
         prob = model.rank_candidates(data.sources[s:e], data.timestamps[s:e], cands)
-        rank_metrics(prob.float(), None, out=acc)
+        cand_idx = None
+        if filtered:
+            from .tgn import absent_columns
+            cand_d = torch.from_numpy(np.ascontiguousarray(cands, np.int32)).to(model.device)
+            bits = model.absent_bits(data.sources[s:e], data.timestamps[s:e], finder if finder is not None else "seen",
+                                     candidates=cand_d)
+            gone = absent_columns(bits, cand_d.shape[1]) | (cand_d == cand_d[:, :1])
+            gone[:, 0] = False                                       # the positive is never filtered
+            cand_idx = -gone.to(torch.int32)                         # 0: present, -1: absent
+        rank_metrics(prob.float(), cand_idx, out=acc)
         model.compute_temporal_embeddings(data.sources[s:e], data.destinations[s:e], negatives[:, 0], data.timestamps[s:e],
                                           data.edge_idxs[s:e], n_neighbors, False)
     a = acc.cpu().numpy()                                        # (the one host read of the pass)

@@ -28,6 +28,14 @@ def link_score_plan(device_type, dtype, H, fused_scoring=True):
     return "hip" if (H % 4 == 0 and 4 <= H <= 768) else "torch"
 
 
+def absent_columns(absent, n_cols):
+    """bool [Q, n_cols] of absent bits [Q, W] (include/zebra_amd.h, zt_affinity_topk_masked): True where bit c & 31 of word
+    c >> 5 is set for column c"""
+    col = torch.arange(n_cols, device=absent.device, dtype=torch.int64)
+    words = absent.to(torch.int64).index_select(1, col >> 5)
+    return ((words >> (col & 31).unsqueeze(0)) & 1) != 0
+
+
 class TGN(torch.nn.Module):
     def __init__(self, neighbor_finder, node_features, edge_features, device, n_layers=2, n_heads=2, dropout=0.1,
                  use_memory=False, node_dimension=100, time_dimension=100, memory_dimension=100,
@@ -269,9 +277,86 @@ class TGN(torch.nn.Module):
         cand_idx[live] = inv.to(torch.int32)
         return emb_q, emb_c, cand_idx
 
+    # ---- per-query exclusions: absent bits (include/zebra_amd.h, zt_affinity_topk_masked) ----
+    def _exclude_lists(self, src_d, ts_d, exclude):
+        """(handle, ids, begin, len) of the per-query id lists ``exclude`` names (``absent_bits``): ranges of the finder's own
+        neighbour array (ids None: nothing is copied), or of the caller's array (handle None)."""
+        from .tppr import NeighborFinder
+        Q = src_d.numel()
+        if isinstance(exclude, str):
+            if exclude != "seen":
+                raise ValueError("exclude is \"seen\", a NeighborFinder or (ptr [Q + 1], ids)")
+            exclude = self.neighbor_finder
+            if exclude is None:
+                raise ValueError("exclude=\"seen\" needs the model's neighbor_finder; pass a NeighborFinder")
+        if isinstance(exclude, NeighborFinder):
+            begin, length = exclude.seen_ranges_device(src_d, ts_d)
+            return exclude._h, None, begin, length
+        if not (isinstance(exclude, (tuple, list)) and len(exclude) == 2):
+            raise ValueError("exclude is \"seen\", a NeighborFinder or (ptr [Q + 1], ids)")
+        lp = exclude[0] if torch.is_tensor(exclude[0]) else torch.from_numpy(np.ascontiguousarray(exclude[0], np.int64))
+        lp = lp.to(self.device, torch.int64).reshape(-1)
+        ids = self._as_device(exclude[1], torch.int32).reshape(-1)
+        if lp.numel() != Q + 1:
+            raise ValueError("exclude=(ptr, ids): ptr holds Q + 1 offsets into ids")
+        if Q > 0:                                                     # (the kernel trusts the caller's ranges: one host read)
+            bad = (lp[1:] < lp[:-1]).any() | (lp[0] < 0) | (lp[-1] > ids.numel())
+            if bool(bad):
+                raise ValueError("exclude=(ptr, ids): ptr must ascend from >= 0 to <= len(ids)")
+        if ids.numel() == 0:
+            ids = torch.zeros(1, dtype=torch.int32, device=self.device)        # (an address to hand over; never read)
+        return None, ids, lp[:-1].contiguous(), (lp[1:] - lp[:-1]).contiguous()
+
+    def _mark_absent(self, lists, Q, id_lo=None, n_cols=None, candidates=None):
+        """zt_exclude_mark: int32 [Q, ceil(C / 32)] absent bits of the lists over a range of ids or a candidate list"""
+        handle, ids, begin, length = lists
+        if candidates is None:
+            if id_lo is None or n_cols is None:
+                raise ValueError("absent_bits takes candidates, or id_lo and n_cols for the ids id_lo .. id_lo + n_cols - 1")
+            C_, srt, col, stride = int(n_cols), None, None, 0
+        else:
+            cand = candidates
+            if cand.dim() not in (1, 2) or (cand.dim() == 2 and cand.shape[0] != Q):
+                raise ValueError("absent_bits takes candidates [Q, C] or [C]")
+            C_ = cand.shape[-1]
+            srt, order = torch.sort(cand, dim=-1)
+            srt, col = srt.contiguous(), order.to(torch.int32).contiguous()
+            stride = C_ if cand.dim() == 2 else 0
+            id_lo = 0
+        if C_ < 0:
+            raise ValueError("absent_bits: n_cols must not be negative")
+        W = (C_ + 31) // 32
+        absent = torch.empty((Q, W), dtype=torch.int32, device=self.device)
+        if Q == 0 or W == 0:
+            return absent
+        check(lib().zt_exclude_mark(handle, ptr(ids), ptr(begin), ptr(length), C.c_int64(Q), C.c_int64(int(id_lo)), ptr(srt),
+                                    ptr(col), C.c_int64(stride), C.c_int64(C_), ptr(absent), C.c_int64(W), stream_ptr()),
+              "zt_exclude_mark")
+        return absent
+
+    @torch.no_grad()
+    def absent_bits(self, sources, timestamps, exclude, *, id_lo=None, n_cols=None, candidates=None):
+        """int32 [Q, ceil(C / 32)] on the device, the absent bits ``topk_scores(absent=...)`` takes: bit c & 31 of word c >> 5
+        of row q is set where column c of the pool is excluded for ``sources[q]``.  ``exclude``: "seen" -- the partners of the
+        source strictly before ``timestamps[q]`` in ``self.neighbor_finder`` (ValueError if the model has none) --, a
+        NeighborFinder to take them from, or (ptr [Q + 1] int64, ids int32): the caller's own lists, ids[ptr[q]:ptr[q + 1]]
+        for query q.  Lists may hold duplicates and ids outside the pool.  The pool: ``candidates`` [C] (shared) or [Q, C]
+        (-1: absent entries, never matched; every column that holds an excluded id is set), or the ids ``id_lo`` ..
+        ``id_lo + n_cols - 1`` in order.  The lists are built and marked on the device (zt_csr_seen_ranges, zt_exclude_mark);
+        a "seen" list is a range of the finder's own array, never copied.  IndexError for a source outside the finder."""
+        src_d = self._as_device(sources, torch.int32).reshape(-1)
+        Q = src_d.numel()
+        ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
+        if ts_d.numel() == 1 and Q != 1:
+            ts_d = ts_d.expand(Q).contiguous()
+        if ts_d.numel() != Q:
+            raise ValueError("absent_bits takes sources [Q] and timestamps [Q] or a scalar")
+        cand = None if candidates is None else self._as_device(candidates, torch.int32)
+        return self._mark_absent(self._exclude_lists(src_d, ts_d, exclude), Q, id_lo, n_cols, cand)
+
     @torch.no_grad()
     def topk_scores(self, emb_q, emb_c, k, cand_idx=None, skip=None, idx_base=0, out=None, check_status=True,
-                    workspace_bytes=None):
+                    workspace_bytes=None, absent=None):
         """(idx [Q, k] int32, prob [Q, k] float32): for every query the ``k`` present candidates of ``rank_scores`` with the
         largest probability, descending, equal probabilities in ascending index; slots beyond the present candidates read -1
         and 0.  ``idx`` is ``idx_base`` + the column in [0, C).  Present: ``cand_idx`` (if given) is >= 0, the probability is not
@@ -281,7 +366,10 @@ class TGN(torch.nn.Module):
         ``idx_base`` set accordingly, gives the bits of one call.  Where ``rank_scores`` would call zt_affinity_rank and
         k <= 256 this is zt_affinity_topk (csrc/rank_topk.hip): prob[Q, C] is never written and the workspace does not grow
         with the pool (``workspace_bytes``: its size, zt_affinity_topk_workspace_bytes by default).  Anything else computes
-        ``rank_scores`` a chunk of queries at a time and selects by stable sorts with the same rule."""
+        ``rank_scores`` a chunk of queries at a time and selects by stable sorts with the same rule.
+        ``absent``: int32 (or uint32) [Q, W >= ceil(C / 32)] absent bits (``absent_bits``) -- a set bit c & 31 of word c >> 5 of
+        row q takes the LOCAL column c of this call out of query q's candidates; the HIP path is then zt_affinity_topk_masked,
+        and the torch path honours the same bits."""
         a = self.affinity_score
         Q, H = emb_q.shape
         Nc = emb_c.shape[0]
@@ -297,6 +385,14 @@ class TGN(torch.nn.Module):
             if (top_idx.shape != (Q, k) or top_prob.shape != (Q, k) or top_idx.dtype != torch.int32 or top_prob.dtype != torch.float32
                     or top_idx.device != dev or top_prob.device != dev or not top_idx.is_contiguous() or not top_prob.is_contiguous()):
                 raise ValueError("topk_scores: out is (idx [Q, k] int32, prob [Q, k] float32), contiguous, on the embeddings' device")
+        if absent is not None:
+            if absent.dtype != torch.int32:
+                if absent.dtype != getattr(torch, "uint32", None):
+                    raise ValueError("topk_scores: absent is int32 or uint32 [Q, W]")
+                absent = absent.view(torch.int32)
+            if absent.dim() != 2 or absent.shape[0] != Q or absent.shape[1] < (C_ + 31) // 32:
+                raise ValueError("topk_scores: absent is [Q, W] with W >= ceil(C / 32)")
+            absent = absent.to(dev).contiguous()
         hip = (emb_q.is_cuda and emb_c.is_cuda and emb_q.dtype == torch.float32 and emb_c.dtype == torch.float32
                and H % 4 == 0 and _capi.RANK_MIN_H <= H <= _capi.RANK_MAX_H and k <= _capi.TOPK_MAX_K)
         if not hip:
@@ -320,6 +416,8 @@ class TGN(torch.nn.Module):
                     live &= ~nan_row[ixd.clamp(0, max(Nc - 1, 0))]
                 if skip is not None:
                     live &= col.unsqueeze(0) != skip[s:s + step].to(dev, torch.int64).unsqueeze(1)
+                if absent is not None:
+                    live &= ~absent_columns(absent[s:s + step], C_)
                 # this call's candidates behind the incoming list; absent entries sort last (probabilities are >= 0)
                 n = p.shape[0]
                 all_i = torch.cat([top_idx[s:s + step].to(torch.int64), col.unsqueeze(0).expand(n, -1)], dim=1)
@@ -353,10 +451,14 @@ class TGN(torch.nn.Module):
         sk = None if skip is None else skip.to(self.device, torch.int32).contiguous()
         if sk is not None and sk.numel() != Q:
             raise ValueError("topk_scores: skip holds one column per query")
-        check(lib().zt_affinity_topk(ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), ptr(ix),
-                                     C.c_int64(C_), C.c_int32(H), C.byref(w), C.c_int32(k), ptr(sk), C.c_int64(int(idx_base)),
-                                     C.c_int32(1 if accumulate else 0), ptr(top_idx), ptr(top_prob), ptr(ws), C.c_int64(need),
-                                     stream_ptr()), "zt_affinity_topk")
+        args = (ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), ptr(ix), C.c_int64(C_), C.c_int32(H),
+                C.byref(w), C.c_int32(k), ptr(sk), C.c_int64(int(idx_base)), C.c_int32(1 if accumulate else 0), ptr(top_idx),
+                ptr(top_prob), ptr(ws), C.c_int64(need))
+        if absent is None or absent.shape[1] == 0:                     # (C = 0: no words, and no address to hand over)
+            check(lib().zt_affinity_topk(*args, stream_ptr()), "zt_affinity_topk")
+        else:
+            check(lib().zt_affinity_topk_masked(*args, ptr(absent), C.c_int64(absent.shape[1]), stream_ptr()),
+                  "zt_affinity_topk_masked")
         if check_status and ix is not None and C_ > 0:
             st = int(ws[:4].view(torch.int32).item())           # the call's status word: first int32 of the workspace
             if st != 0:
@@ -364,14 +466,19 @@ class TGN(torch.nn.Module):
         return top_idx, top_prob
 
     @torch.no_grad()
-    def recommend(self, sources, timestamps, k, candidates=None, exclude_self=True, pool_chunk=65536):
+    def recommend(self, sources, timestamps, k, candidates=None, exclude_self=True, pool_chunk=65536, exclude=None):
         """(nodes [Q, k] int32, prob [Q, k] float32): the ``k`` likeliest partners of every source among ``candidates``, -1 and 0
         in empty slots; read-only, and raises where ``embed_nodes`` raises.
         ``candidates=None``: every node id 1 .. n_nodes - 1 (0 is the padding id), without the source's own id under
         ``exclude_self``; a 1-D list: a pool shared by all queries (-1: absent).  Both are embedded ``pool_chunk`` rows at a time
         and each chunk goes through ``topk_scores`` with accumulate, so memory does not depend on the pool; ``timestamps`` is
         then a scalar or all equal (ValueError otherwise: a candidate's embedding depends on the query's time).
-        ``candidates`` [Q, C] (-1: absent) takes per-query times: ``rank_candidates``' de-duplication, then ``topk_scores``."""
+        ``candidates`` [Q, C] (-1: absent) takes per-query times: ``rank_candidates``' de-duplication, then ``topk_scores``.
+        ``exclude`` (None: nothing more is left out): per-query lists of ids that must not come back, as ``absent_bits`` takes
+        them -- "seen": the partners each source has met strictly before its query time, from ``self.neighbor_finder``; a
+        NeighborFinder; or (ptr [Q + 1], ids).  Every pool chunk gets its absent bits on the device (Q * ceil(pool_chunk / 32)
+        words: memory still does not grow with the pool) and the fused top-K leaves those columns out, so k results come back
+        wherever k candidates remain, whatever the source's degree.  ``exclude_self`` works beside it."""
         src_d = self._as_device(sources, torch.int32).reshape(-1)
         Q = src_d.numel()
         ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
@@ -381,11 +488,15 @@ class TGN(torch.nn.Module):
         if ts_d.numel() != Q or k <= 0 or int(pool_chunk) <= 0:
             raise ValueError("recommend takes sources [Q], timestamps [Q] or a scalar, k > 0 and pool_chunk > 0")
         cand = None if candidates is None else self._as_device(candidates, torch.int32)
+        if exclude is not None:                                      # (refuses where embed_nodes does, before any device work)
+            self.embed_nodes(src_d[:0], ts_d[:0])
+            lists = self._exclude_lists(src_d, ts_d, exclude)
         if cand is not None and cand.dim() == 2:
             if cand.shape[0] != Q:
                 raise ValueError("recommend takes candidates [Q, C] or [C]")
             emb_q, emb_c, cand_idx = self._embed_candidates(src_d, ts_d, cand.contiguous(), True)
-            idx, prob = self.topk_scores(emb_q, emb_c, k, cand_idx=cand_idx)
+            absent = None if exclude is None else self._mark_absent(lists, Q, candidates=cand)
+            idx, prob = self.topk_scores(emb_q, emb_c, k, cand_idx=cand_idx, absent=absent)
             nodes = torch.where(idx >= 0, cand.gather(1, idx.clamp(min=0).long()), torch.full_like(idx, -1))
             return nodes, prob
         if cand is not None and cand.dim() != 1:
@@ -408,7 +519,11 @@ class TGN(torch.nn.Module):
             if cand is not None and bool((ids < 0).any()):                 # absent entries of a shared list: through indices
                 cix = torch.where(ids >= 0, torch.arange(e - s, dtype=torch.int32, device=self.device),
                                   torch.full_like(ids, -1)).unsqueeze(0).expand(Q, -1).contiguous()
-            self.topk_scores(emb_q, emb_c, k, cand_idx=cix, skip=skip, idx_base=s, out=(idx, prob))
+            absent = None
+            if exclude is not None:
+                absent = (self._mark_absent(lists, Q, id_lo=s + 1, n_cols=e - s) if cand is None
+                          else self._mark_absent(lists, Q, candidates=ids))
+            self.topk_scores(emb_q, emb_c, k, cand_idx=cix, skip=skip, idx_base=s, out=(idx, prob), absent=absent)
         if cand is None:
             nodes = torch.where(idx >= 0, idx + 1, idx)
         else:

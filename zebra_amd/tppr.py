@@ -412,6 +412,27 @@ class NeighborFinder:
         i = int(np.searchsorted(self._ts[lo:hi], cut_time))
         return self._nbr[lo:lo + i], self._eid[lo:lo + i], self._ts[lo:lo + i]
 
+    def seen_ranges_device(self, nodes_d, ts_d, check_status=True):
+        """(begin, len) int64 CUDA tensors: entries [begin[q], begin[q] + len[q]) of this finder's neighbour array are the
+        partners of ``nodes_d[q]`` strictly before ``ts_d[q]`` -- ``find_before``'s prefix, duplicates included
+        (zt_csr_seen_ranges; int32 nodes and float64 timestamps on the device in).  An id outside [0, num_nodes) gives an empty
+        range and, with ``check_status``, IndexError."""
+        Q = nodes_d.numel()
+        if ts_d.numel() != Q:
+            raise ValueError("seen_ranges_device takes one timestamp per node")
+        begin = torch.zeros(Q, dtype=torch.int64, device=nodes_d.device)
+        length = torch.zeros(Q, dtype=torch.int64, device=nodes_d.device)
+        if Q == 0:                                  # (an empty tensor has no address to hand over: nothing to enqueue)
+            return begin, length
+        check(lib().zt_csr_seen_ranges(self._h, ptr(nodes_d), ptr(ts_d), C.c_int64(Q), ptr(begin), ptr(length),
+                                       ptr(self._status), stream_ptr()), "zt_csr_seen_ranges")
+        if check_status:
+            st = int(self._status.item())
+            if st != 0:
+                self._status.zero_()
+                raise IndexError("zt_csr_seen_ranges: node id out of range (status %d)" % st)
+        return begin, length
+
     # ---- walks that do not fit LDS: the workspace form (csrc/tppr_prune.hip: k_pruned_topk_ws) ----
     @staticmethod
     def pruning_plan(width, depth, n_models=1, k=20, max_bytes=1 << 30):
