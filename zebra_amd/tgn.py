@@ -451,7 +451,13 @@ class TGN(torch.nn.Module):
         sk = None if skip is None else skip.to(self.device, torch.int32).contiguous()
         if sk is not None and sk.numel() != Q:
             raise ValueError("topk_scores: skip holds one column per query")
-        args = (ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), ptr(ix), C.c_int64(C_), C.c_int32(H),
+        emb_c = emb_c.contiguous()
+        if C_ == 0:                        # an empty tensor has no address: one to hand over, never read (C = 0: -1 and 0, or
+            if Nc == 0:                    # the incoming list left alone; found by test_topk_exact_gpu.py, orders-*-K1-C0)
+                emb_c = torch.zeros((1, H), dtype=torch.float32, device=self.device)
+            if ix is not None:
+                ix = torch.zeros(1, dtype=torch.int32, device=self.device)
+        args = (ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c), C.c_int64(Nc), ptr(ix), C.c_int64(C_), C.c_int32(H),
                 C.byref(w), C.c_int32(k), ptr(sk), C.c_int64(int(idx_base)), C.c_int32(1 if accumulate else 0), ptr(top_idx),
                 ptr(top_prob), ptr(ws), C.c_int64(need))
         if absent is None or absent.shape[1] == 0:                     # (C = 0: no words, and no address to hand over)
