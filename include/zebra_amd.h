@@ -941,6 +941,64 @@ int zt_pipeline_last_scores(zt_pipeline *p, void *stream, float **prob_out, int6
 int zt_pipeline_set_metrics(zt_pipeline *p, double *sum_dev, double *per_batch_dev, int64_t cap);
 int zt_pipeline_metrics(zt_pipeline *p, void *stream, int64_t *n_out);
 
+/* ------------------------------------------------------------------------ */
+/* Node classification: the decoder head (csrc/decoder.hip)                   */
+/* ------------------------------------------------------------------------ */
+#define ZT_DECODER_H1 80   /* the reference's hidden widths (MLP, utils/util.py:28-42): no others are taken */
+#define ZT_DECODER_H2 10
+typedef struct {
+    const float *fc1_w, *fc1_b;  /* fc_1 [80][H], [80] */
+    const float *fc2_w, *fc2_b;  /* fc_2 [10][80], [10] */
+    const float *fc3_w, *fc3_b;  /* fc_3 [1][10], [1]  */
+} zt_decoder_weights;            /* device pointers */
+/* The reference's node-classification decoder (evaluation/evaluation.py:51-79 applies it to the source embeddings):
+ *   z = fc3(drop(relu(fc2(drop(relu(fc1(x)))))))   x_dev [N][H] -> 80 -> 10 -> z [N]
+ * for any H with H % 4 == 0 and 4 <= H <= 4352, the widths the one-vs-many scorer takes (ZT_ERR_UNSUPPORTED otherwise, before
+ * any device call); K runs over H in chunks, LDS does not bound it.  N = 0: ZT_OK, nothing touched.  The parameters are read
+ * as they lie in the module (no packed copy, no weights_ready); x_dev and fc1_w are 16-byte aligned, the other five need
+ * no alignment, and nothing past row 10 of fc2_w, fc2_b or fc3_w is read.  Layer 1 runs on the f32 MFMA, layer 2 as one
+ * N-tile padded to 16 fed through LDS, layer 3 as ten terms in column order.  No atomics: two calls give the same bits, and
+ * the eval entry and the training entry at p = 0 give the same bits.
+ *   eval:     writes logit_dev [N] and / or prob_dev [N] = sigmoid(z); either may be NULL.  One launch.
+ *   training: dropout p in [0, 1) (0: none) from a 64-bit seed: element row * 80 + col of layer 1 and N * 80 + row * 10 + col of
+ *             layer 2 is kept, and scaled by 1 / (1 - p), where its hash passes the threshold (the aggregation's dropout;
+ *             zebra_amd/decoder.py decoder_dropout_mask is the same arithmetic in numpy).  Writes logit_dev [N] and keeps
+ *             h1_dev [N][80] and h2_dev [N][10], both after ReLU and dropout, for the backward.  One launch.
+ *   backward: from dlogit_dev [N], x_dev and the forward's h1_dev / h2_dev (p and seed as given there): d_x_dev [N][H],
+ *             d_fc1_w_dev [80][H], d_fc1_b_dev [80], d_fc2_w_dev [10][80], d_fc2_b_dev [10], d_fc3_w_dev [10], d_fc3_b_dev [1],
+ *             written, not accumulated.  An output that is not needed is NULL and its work is skipped (d_x_dev = NULL is the
+ *             usual case: the embeddings come from a frozen model).  At most three launches, no host synchronisation, no
+ *             atomics: every sum has a fixed order, two runs give the same bits.  d_x_dev and d_fc1_w_dev are 16-byte aligned.
+ * workspace_dev (backward only): zt_node_decoder_train_workspace_bytes(max_N, H) bytes (-1 = H unsupported or max_N < 0),
+ * 16-byte aligned, sized for ws_max_N >= N; it holds d(hidden 1) [N][80], d(hidden 2) [N][10] and the partial products of
+ * d_fc1_w.
+ * zt_node_decoder_plan (host code only, the one place that decides): out[ZT_DECODER_PLAN_FIELDS], all int64:
+ *   [0] arrangement  5: five waves own one N-tile each and share 16 staged rows (the pick at every N: the other form, one
+ *                    wave owning the five N-tiles of its 16 rows, value 1, measured no faster and is reached by the tests only)
+ *   [1] waves        per workgroup
+ *   [2] rows         per workgroup
+ *   [3] k_chunk      columns of x staged in LDS at a time
+ *   [4] grid         workgroups of the forward
+ *   [5] lds_bytes    dynamic LDS of the forward
+ *   [6] split        partial products of d_fc1_w in the backward (1: written directly)
+ *   [7] k_per        rows per partial product
+ * ZT_ERR_ARG for NULL out or N < 0, ZT_ERR_UNSUPPORTED for the width. */
+#define ZT_DECODER_PLAN_FIELDS 8
+int zt_node_decoder_plan(int64_t N, int32_t H, int32_t training, int64_t *out);
+int zt_node_decoder(const float *x_dev, int64_t N, int32_t H, const zt_decoder_weights *weights,
+                    float *logit_dev, float *prob_dev, void *stream);
+int zt_node_decoder_train_forward(const float *x_dev, int64_t N, int32_t H,
+                                  const zt_decoder_weights *weights, float p, uint64_t seed,
+                                  float *logit_dev, float *h1_dev, float *h2_dev, void *stream);
+int64_t zt_node_decoder_train_workspace_bytes(int64_t max_N, int32_t H);
+int zt_node_decoder_train_backward(const float *x_dev, int64_t N, int32_t H,
+                                   const zt_decoder_weights *weights, const float *h1_dev,
+                                   const float *h2_dev, const float *dlogit_dev, float p, uint64_t seed,
+                                   float *d_x_dev, float *d_fc1_w_dev, float *d_fc1_b_dev,
+                                   float *d_fc2_w_dev, float *d_fc2_b_dev, float *d_fc3_w_dev,
+                                   float *d_fc3_b_dev, void *workspace_dev, int64_t ws_max_N,
+                                   void *stream);
+
 /* The tail of a TRAINING step (csrc/train_tail.hip): the loss of train.py:212-213 and the optimizer step of train.py:215.
  *
  * Pair loss.  prob_dev [2B] holds B positive probabilities, then B negative ones (what zt_affinity_train_forward writes):
@@ -952,6 +1010,14 @@ int zt_pipeline_metrics(zt_pipeline *p, void *stream, int64_t *n_out);
  * call. */
 int zt_link_bce_forward(const float *prob_dev, int64_t B, float *loss_dev, float *dprob_dev, void *stream);
 int zt_link_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int64_t B, float *d_prob_dev, void *stream);
+/* Label loss: torch.nn.BCELoss() (mean) of prob_dev [N] against a float label per row, label_dev [N]:
+ *   loss_dev[0] = mean_i -(y_i max(log x_i, -100) + (1 - y_i) max(log(1 - x_i), -100))
+ * and dprob_dev [N] = (x - y) / max((1 - x) x, 1e-12) / N, the gradient at grad_output = 1.  The pair loss's arithmetic and
+ * launches: float64 logarithms, quotients and sums with a fixed association, rounded once; one launch each way, the backward
+ * d_prob_dev = grad_loss_dev[0] * dprob_dev.  N < 1 or a NULL pointer: ZT_ERR_ARG before any device call. */
+int zt_label_bce_forward(const float *prob_dev, const float *label_dev, int64_t N, float *loss_dev, float *dprob_dev,
+                         void *stream);
+int zt_label_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int64_t N, float *d_prob_dev, void *stream);
 /* Adam for a whole list of float32 tensors in one launch per ZT_ADAM_MAX_TENSORS non-empty tensors: torch.optim.Adam's
  * single-tensor update without weight decay, amsgrad or maximize, in torch's order,
  *   m = m + (g - m) (1 - beta1);  v = v beta2 + (1 - beta2) g g;  p = p - step_size (m / (sqrt(v) / bias2_sqrt + eps))

@@ -15,4 +15,10 @@ def __getattr__(name):
     if name == "link_bce_loss":
         from .losses import link_bce_loss
         return link_bce_loss
+    if name == "label_bce_loss":
+        from .losses import label_bce_loss
+        return label_bce_loss
+    if name == "MLP":
+        from .decoder import MLP
+        return MLP
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -37,6 +37,8 @@ SYMBOLS = [
     "zt_tppr_query", "zt_affinity_rank_workspace_bytes", "zt_affinity_rank", "zt_rank_metrics",
     "zt_affinity_topk_workspace_bytes", "zt_affinity_topk", "zt_affinity_topk_plan",
     "zt_affinity_topk_masked", "zt_csr_seen_ranges", "zt_exclude_mark",
+    "zt_node_decoder_plan", "zt_node_decoder", "zt_node_decoder_train_forward", "zt_node_decoder_train_workspace_bytes",
+    "zt_node_decoder_train_backward", "zt_label_bce_forward", "zt_label_bce_backward",
 ]
 
 
@@ -59,6 +61,10 @@ ADAM_CHUNK, ADAM_MAX_TENSORS = 4096, 64                         # zt_adam_plan /
 RANK_MIN_H, RANK_MAX_H = 4, 4352                                # zt_affinity_rank's hidden widths (H % 4 == 0)
 TOPK_MAX_K = 256                                                # zt_affinity_topk
 TOPK_FORM_LANE, TOPK_FORM_LANE4 = 1, 2                          # zt_affinity_topk_plan
+DECODER_H1, DECODER_H2 = 80, 10                                 # zt_node_decoder's hidden widths
+DECODER_MIN_H, DECODER_MAX_H = RANK_MIN_H, RANK_MAX_H           # ... and its input widths (H % 4 == 0)
+DECODER_ARR_ONE, DECODER_ARR_FIVE = 1, 5                        # zt_node_decoder_plan
+DECODER_PLAN_FIELDS = ("arrangement", "waves", "rows", "k_chunk", "grid", "lds_bytes", "split", "k_per")
 TOPK_PLAN_FIELDS = ("form", "wave_queries", "q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid_pairs", "grid_merge",
                     "lists_offset", "pc_offset", "min_bytes")
 
@@ -93,6 +99,10 @@ class AttnWeights(C.Structure):
 
 class AffinityWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class DecoderWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")]
 
 
 class GruWeights(C.Structure):
@@ -148,7 +158,8 @@ def lib():
             _lib.zt_pipeline_main_stream.restype = C.c_void_p
         _lib.zt_version.restype = C.c_char_p
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
-                     "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes"):
+                     "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes",
+                     "zt_node_decoder_train_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib
@@ -200,6 +211,14 @@ def topk_plan(Q, Nc, C_, H, K, indexed, workspace_bytes):
     check(lib().zt_affinity_topk_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H), C.c_int32(K),
                                       C.c_int32(1 if indexed else 0), C.c_int64(workspace_bytes), out), "zt_affinity_topk_plan")
     return {name: int(out[i]) for i, name in enumerate(TOPK_PLAN_FIELDS)}
+
+
+def decoder_plan(N, H, training=False):
+    """zt_node_decoder_plan: the arrangement, rows per workgroup, K-chunk and grid of the decoder's forward over N rows of width
+    H, and the split of the backward's d_fc1_w (host code only)."""
+    out = (C.c_int64 * len(DECODER_PLAN_FIELDS))()
+    check(lib().zt_node_decoder_plan(C.c_int64(N), C.c_int32(H), C.c_int32(1 if training else 0), out), "zt_node_decoder_plan")
+    return {name: int(out[i]) for i, name in enumerate(DECODER_PLAN_FIELDS)}
 
 
 def adam_plan(numel):

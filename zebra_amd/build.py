@@ -38,6 +38,7 @@ SOURCES = {
     "rank_topk.hip": [],
     "seen.hip": [],
     "train_tail.hip": [],
+    "decoder.hip": [],
     "exchange.hip": [],
     "pipeline.hip": [],
 }

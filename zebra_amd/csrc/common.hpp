@@ -33,6 +33,18 @@ inline unsigned drop_threshold(float p)
     return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
 
+// The node decoder's launch (decoder.hip: zt::decoder_plan is the one place that picks it; zt_node_decoder_plan publishes it).
+// pin: 0 = the plan's pick, 1 / 5 = that arrangement (the test hook zt_test_decoder_arrangement sets g_decoder_arrangement).
+struct DecoderPlan {
+    int arrangement;        // 0 refused; 1: one wave owns the five N-tiles of 16 rows; 5: five waves own one N-tile each
+    int waves, threads, rows, k_chunk;
+    long long grid, lds_bytes;
+    int split;              // partial products of d_fc1_w in the backward
+    long long k_per;        // rows per partial product
+};
+DecoderPlan decoder_plan(int64_t N, int H, bool training, int pin);
+extern int g_decoder_arrangement;
+
 // Optional HIP-event timing of individual kernels (zt_profile_* in the ABI):
 // an event pair is recorded on the launch stream around the kernel; elapsed
 // times are summed per kernel name when the profile is read.

@@ -65,6 +65,9 @@ int zt_test_step_plan(int32_t streaming, int32_t masked, int32_t release, int64_
 /* Test hook: a launch group's release and size limit (zt::pipeline_group_plan).  want: zt_pipeline_set_group; n_more: batches
  * in sight behind the first.  out[2] = released by member (before "and more than one member"), batches it may take. */
 int zt_test_group_plan(int32_t streaming, int32_t release, int32_t want, int32_t n_more, int64_t *out);
+/* Test hook: pin the node decoder's arrangement process-wide (zt::decoder_plan: 0 = the plan's pick, 1 = one wave per 16 rows,
+ * 5 = five waves per 16 rows); zt_node_decoder_plan answers under the pin.  ZT_ERR_ARG for any other value. */
+int zt_test_decoder_arrangement(int32_t value);
 
 #ifdef __cplusplus
 }

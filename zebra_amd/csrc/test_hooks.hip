@@ -188,3 +188,10 @@ extern "C" int zt_test_group_plan(int32_t streaming, int32_t release, int32_t wa
     out[1] = gp.limit;
     return ZT_OK;
 }
+
+extern "C" int zt_test_decoder_arrangement(int32_t value)
+{
+    if (value != 0 && value != 1 && value != 5) return ZT_ERR_ARG;
+    g_decoder_arrangement = value;
+    return ZT_OK;
+}

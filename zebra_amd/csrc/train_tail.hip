@@ -72,6 +72,34 @@ __global__ __launch_bounds__(256) void k_link_bce_bwd(const float *__restrict__ 
     if (i < n) d_prob[i] = grad_loss[0] * dprob[i];
 }
 
+// Label loss (k_label_bce_fwd): torch.nn.BCELoss() (mean) of prob [N] against a float label per row,
+//   loss = mean_i -(y_i max(log x_i, -100) + (1 - y_i) max(log(1 - x_i), -100)),  dprob = (x - y) / max((1 - x) x, 1e-12) / N
+// with k_link_bce_fwd's arithmetic: float64 logarithms, quotient and sums, one rounding, the same fixed order.
+__global__ __launch_bounds__(BCE_THREADS) void k_label_bce_fwd(const float *__restrict__ prob, const float *__restrict__ label, long long N,
+                                                               float *__restrict__ loss, float *__restrict__ dprob)
+{
+    __shared__ double part[BCE_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double s = 0.0;
+    for (long long i = tid; i < N; i += BCE_THREADS) {
+        const double x = (double)prob[i], y = (double)label[i];
+        double l1 = log(x), l0 = log(1.0 - x), q = (1.0 - x) * x;
+        l1 = l1 < -100.0 ? -100.0 : l1;                                  // (a NaN stays one, as in torch)
+        l0 = l0 < -100.0 ? -100.0 : l0;
+        q = q < 1e-12 ? 1e-12 : q;
+        s -= y * l1 + (1.0 - y) * l0;
+        dprob[i] = (float)((x - y) / q / (double)N);
+    }
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d);             // a fixed tree over the lanes
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int w = 0; w < BCE_WAVES; ++w) t += part[w];                // ... and the waves in order
+        loss[0] = (float)(t / (double)N);
+    }
+}
+
 // (a kernel argument: keep the layout.  3096 bytes of the 4 KB a launch may carry)
 struct AdamArgs {
     float *param[ADAM_MAX_TENSORS];
@@ -244,6 +272,36 @@ extern "C" int zt_link_bce_backward(const float *dprob_dev, const float *grad_lo
     hipStream_t s = (hipStream_t)stream;
     ZT_PROF_BEGIN(s, P_LINK_BCE);
     k_link_bce_bwd<<<(unsigned)grid, 256, 0, s>>>(dprob_dev, grad_loss_dev, n, d_prob_dev);
+    ZT_PROF_END(s, P_LINK_BCE);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_label_bce_forward(const float *prob_dev, const float *label_dev, int64_t N, float *loss_dev, float *dprob_dev,
+                                    void *stream)
+{
+    if (N < 1 || !prob_dev || !label_dev || !loss_dev || !dprob_dev) {
+        set_error("zt_label_bce_forward: bad argument (N >= 1 and four device pointers expected)");
+        return ZT_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ZT_PROF_BEGIN(s, P_LINK_BCE);
+    k_label_bce_fwd<<<1, BCE_THREADS, 0, s>>>(prob_dev, label_dev, (long long)N, loss_dev, dprob_dev);
+    ZT_PROF_END(s, P_LINK_BCE);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_label_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int64_t N, float *d_prob_dev, void *stream)
+{
+    const long long grid = N < 1 ? 0 : (N - 1) / 256 + 1;
+    if (N < 1 || grid > 0x7fffffffll || !dprob_dev || !grad_loss_dev || !d_prob_dev) {
+        set_error("zt_label_bce_backward: bad argument (1 <= N within one launch and three device pointers expected)");
+        return ZT_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ZT_PROF_BEGIN(s, P_LINK_BCE);
+    k_link_bce_bwd<<<(unsigned)grid, 256, 0, s>>>(dprob_dev, grad_loss_dev, (long long)N, d_prob_dev);
     ZT_PROF_END(s, P_LINK_BCE);
     ZT_LAUNCH_CHECK();
     return ZT_OK;

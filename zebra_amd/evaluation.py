@@ -152,6 +152,54 @@ def _eval_edge_prediction_native(model, negative_edge_sampler, data, batch_size)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Node classification (evaluation/evaluation.py:51-79)
+# ---------------------------------------------------------------------------------------------------------------------
+def node_auc(prob, labels):
+    """sklearn.metrics.roc_auc_score(labels, prob) for binary labels (1 / 0) as a float64 scalar tensor on the scores' device:
+    ``roc_auc`` above on prob[labels == 1] and prob[labels == 0].  ValueError when only one class is present, as scikit-learn
+    raises (that check reads two counts from the device)."""
+    prob = torch.as_tensor(prob).reshape(-1)
+    labels = torch.as_tensor(labels).reshape(-1).to(prob.device)
+    if labels.numel() != prob.numel():
+        raise ValueError("node_auc takes one label per score")
+    is_pos = labels == 1
+    pos, neg = prob[is_pos], prob[labels == 0]
+    if pos.numel() + neg.numel() != prob.numel():
+        raise ValueError("node_auc takes binary labels (0 / 1)")
+    if pos.numel() == 0 or neg.numel() == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    return roc_auc(pos, neg)
+
+
+@torch.no_grad()
+def eval_node_classification(tgn, decoder, data, batch_size, n_neighbors):
+    """evaluation/evaluation.py:51-79 with the same protocol and return value (ROC-AUC of the decoder's probabilities on the
+    source embeddings over the whole split): the TGN is stepped in eval mode with each batch's destinations as negatives, the
+    probabilities of every batch are written into one device vector, the AUC is computed there (``roc_auc``, float64: a split can
+    exceed what zt_link_metrics sorts, and labels are not paired) and the host reads it once."""
+    decoder.eval()
+    tgn.eval()
+    n = len(data.sources)
+    nb = math.ceil(n / batch_size)
+    # the labels are host data: the two classes' positions are found there, so the device is read once, for the result
+    lab = np.asarray(data.labels[:n])
+    pos_i, neg_i = np.nonzero(lab == 1)[0], np.nonzero(lab == 0)[0]
+    if len(pos_i) + len(neg_i) != n:
+        raise ValueError("eval_node_classification takes binary labels (0 / 1)")
+    if len(pos_i) == 0 or len(neg_i) == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    prob = torch.empty(n, dtype=torch.float32, device=tgn.device)
+    for b in range(nb):
+        s, e = b * batch_size, min(n, (b + 1) * batch_size)
+        src_emb, _, _ = tgn.compute_temporal_embeddings(data.sources[s:e], data.destinations[s:e], data.destinations[s:e],
+                                                        data.timestamps[s:e], data.edge_idxs[s:e], n_neighbors, train=False)
+        prob[s:e] = decoder.predict(src_emb)
+    from ._capi import to_device
+    pos_d, neg_d = to_device(tgn.device, [pos_i.astype(np.int64), neg_i.astype(np.int64)])
+    return float(roc_auc(prob.index_select(0, pos_d), prob.index_select(0, neg_d)).item())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Evaluation by rank: one positive against many negatives (MRR, Hits@k)
 # ---------------------------------------------------------------------------------------------------------------------
 def rank_metrics(prob, cand_idx=None, out=None, ranks=False):

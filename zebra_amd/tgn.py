@@ -197,6 +197,13 @@ class TGN(torch.nn.Module):
         return em.embed_device(self.memory.memory, nodes_d, on, oe, od, ow, check_status=check_status, memory_obj=self.memory)
 
     @torch.no_grad()
+    def classify_nodes(self, decoder, nodes, timestamps, check_status=True):
+        """Probabilities [N] (CUDA) of ``decoder`` (zebra_amd.decoder.MLP) on the embeddings of ``nodes`` at ``timestamps``
+        from the model's current state: ``embed_nodes``, then ``decoder.predict``.  Read-only; it refuses what ``embed_nodes``
+        refuses."""
+        return decoder.predict(self.embed_nodes(nodes, timestamps, check_status=check_status))
+
+    @torch.no_grad()
     def rank_scores(self, emb_q, emb_c, cand_idx=None, check_status=True):
         """prob [Q, C] = sigmoid(affinity_score(emb_q[q], emb_c[cand_idx[q, c]])): one source against many candidates.
         ``cand_idx`` int32 [Q, C] names rows of ``emb_c`` (-1: absent, probability 0) or is None: every query takes all of
