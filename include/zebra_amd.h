@@ -807,6 +807,38 @@ int64_t zt_affinity_rank_workspace_bytes(int64_t Q, int64_t Nc, int32_t H);
 int zt_affinity_rank(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
                      const int32_t *cand_idx_dev, int64_t C, int32_t H, const zt_affinity_weights *w,
                      float *prob_dev, void *workspace_dev, void *stream);
+/* The same scorer for a RANKING training step, differentiable (csrc/rank_train.hip).  Inputs, widths (H % 4 == 0,
+ * 4 <= H <= 4352; ZT_ERR_UNSUPPORTED otherwise, before any launch), the C == Nc rule without an index and the status word
+ * (first int32 of the workspace, set to 0 by each call) are zt_affinity_rank's; emb_q_dev, emb_c_dev and fc1_w are 16-byte
+ * aligned.  Q = 0 or C = 0: ZT_OK, nothing touched; argument checks come before any device call; Q C must fit an int32.
+ *   forward:  logit_dev [Q][C] = b2 + sum_h w2[h] relu((P_q[q][h] + b1[h]) + P_c[row][h]) -- zt_affinity_rank's pair sum:
+ *             1 / (1 + expf(-logit)) has the bits zt_affinity_rank writes for the pair -- and -inf for an absent pair (index
+ *             -1, or out of range: ZT_ERR_RANGE in the status word).  pq_dev [Q][H] and pc_dev [Nc][H] (16-byte aligned)
+ *             receive the two projections; the caller keeps them for the backward.
+ *   backward: from dl_dev [Q][C] = d(loss)/d(logit) (ignored at absent pairs) and the forward's pq_dev / pc_dev:
+ *             d_emb_q_dev [Q][H], d_emb_c_dev [Nc][H] (a row no pair names: zeros), d_fc1_w_dev [H][2H], d_fc1_b_dev [H],
+ *             d_fc2_w_dev [H], d_fc2_b_dev [1], written, not accumulated; an output that is not needed is NULL and its work
+ *             is skipped.  The hidden layer is formed again from pq_dev and pc_dev: no array of Q C H elements exists.
+ *             With an index the caller passes its transpose: row_ptr_dev int64 [Nc + 1] and pairs_dev int32 [n_pairs], the
+ *             ids q C + c of the present pairs grouped by the row they name, ascending within a row.  A pair id outside
+ *             [0, Q C), a pair listed under a row it does not name or a row range outside [0, n_pairs] is left out and sets
+ *             ZT_ERR_RANGE in the status word; nothing is read or written out of bounds.  Two kernels, three zt_colsum_f32
+ *             and four zt_gemm_f32; every sum has one fixed association, no float atomics: two runs give the same bits.
+ * workspace_dev: zt_affinity_rank_train_workspace_bytes(Q, Nc, C, H) bytes (-1: H unsupported, or a negative size), 16-byte
+ * aligned; the forward uses its status word only, the backward also d(P_q), d(P_c) and the partial sums of d_fc2_w. */
+int64_t zt_affinity_rank_train_workspace_bytes(int64_t Q, int64_t Nc, int64_t C, int32_t H);
+int zt_affinity_rank_train_forward(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                                   const int32_t *cand_idx_dev, int64_t C, int32_t H,
+                                   const zt_affinity_weights *w, float *logit_dev, float *pq_dev,
+                                   float *pc_dev, void *workspace_dev, void *stream);
+int zt_affinity_rank_train_backward(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc,
+                                    const int32_t *cand_idx_dev, int64_t C, int32_t H,
+                                    const zt_affinity_weights *w, const float *pq_dev,
+                                    const float *pc_dev, const float *dl_dev, const int64_t *row_ptr_dev,
+                                    const int32_t *pairs_dev, int64_t n_pairs, float *d_emb_q_dev,
+                                    float *d_emb_c_dev, float *d_fc1_w_dev, float *d_fc1_b_dev,
+                                    float *d_fc2_w_dev, float *d_fc2_b_dev, void *workspace_dev,
+                                    void *stream);
 /* The K likeliest candidates of every query (csrc/rank_topk.hip) without prob[Q][C]: emb_q_dev, emb_c_dev, cand_idx_dev (NULL:
  * every query takes all Nc rows in order, C == Nc), the weights, the width bound and the status word (first int32 of the
  * workspace; ZT_ERR_RANGE for an index >= Nc or < -1, that pair counts as absent) are zt_affinity_rank's, and every pair's
@@ -1018,6 +1050,24 @@ int zt_link_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int
 int zt_label_bce_forward(const float *prob_dev, const float *label_dev, int64_t N, float *loss_dev, float *dprob_dev,
                          void *stream);
 int zt_label_bce_backward(const float *dprob_dev, const float *grad_loss_dev, int64_t N, float *d_prob_dev, void *stream);
+/* Listwise loss of a ranking step over logit_dev [Q][C] (what zt_affinity_rank_train_forward writes: -inf where a pair is
+ * absent).  target_dev [Q] (int32; NULL: column 0) names the positive's column; a query whose target is absent or outside
+ * [0, C) is skipped, n_live queries remain; with none the loss is 0 and dl is all zeros.
+ *   ZT_RANK_LOSS_SOFTMAX: loss = mean over live q of logsumexp over present c of logit[q][c] - logit[q][t_q],
+ *                         dl = (softmax - onehot) / n_live;
+ *   ZT_RANK_LOSS_BCE:     loss = mean over live q of -max(log sigma(logit[q][t_q]), -100) + mean over the n_neg present
+ *                         non-target pairs of live queries of -max(log(1 - sigma(logit)), -100); dl = (sigma - 1) / n_live at a
+ *                         target and sigma / n_neg elsewhere.  With C = 2 and nothing absent this is the pair loss of the same
+ *                         probabilities -- formed from the logits in float64, so equal to it within float32 rounding, not in bits.
+ * dl_dev [Q][C] is the gradient at grad_output = 1 (0 at absent pairs and skipped queries).  The pair loss's arithmetic:
+ * float64 exponentials, logarithms and sums with a fixed association, rounded to float32 once, one launch, no atomics.  The
+ * backward is one launch, d_logit_dev[i] = grad_loss_dev[0] * dl_dev[i] for n = Q C elements.  Q < 1, C < 1, an unknown mode
+ * or a NULL pointer (target_dev apart): ZT_ERR_ARG before any device call. */
+#define ZT_RANK_LOSS_SOFTMAX 0
+#define ZT_RANK_LOSS_BCE 1
+int zt_rank_loss_forward(const float *logit_dev, const int32_t *target_dev, int64_t Q, int64_t C, int32_t mode,
+                         float *loss_dev, float *dl_dev, void *stream);
+int zt_rank_loss_backward(const float *dl_dev, const float *grad_loss_dev, int64_t n, float *d_logit_dev, void *stream);
 /* Adam for a whole list of float32 tensors in one launch per ZT_ADAM_MAX_TENSORS non-empty tensors: torch.optim.Adam's
  * single-tensor update without weight decay, amsgrad or maximize, in torch's order,
  *   m = m + (g - m) (1 - beta1);  v = v beta2 + (1 - beta2) g g;  p = p - step_size (m / (sqrt(v) / bias2_sqrt + eps))

@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == "label_bce_loss":
         from .losses import label_bce_loss
         return label_bce_loss
+    if name == "listwise_loss":
+        from .losses import listwise_loss
+        return listwise_loss
     if name == "MLP":
         from .decoder import MLP
         return MLP

@@ -39,6 +39,8 @@ SYMBOLS = [
     "zt_affinity_topk_masked", "zt_csr_seen_ranges", "zt_exclude_mark",
     "zt_node_decoder_plan", "zt_node_decoder", "zt_node_decoder_train_forward", "zt_node_decoder_train_workspace_bytes",
     "zt_node_decoder_train_backward", "zt_label_bce_forward", "zt_label_bce_backward",
+    "zt_affinity_rank_train_workspace_bytes", "zt_affinity_rank_train_forward", "zt_affinity_rank_train_backward",
+    "zt_rank_loss_forward", "zt_rank_loss_backward",
 ]
 
 
@@ -59,6 +61,7 @@ METRICS_MAX_B = 16384
 MSG_ONE, MSG_TWO = 1, 2
 ADAM_CHUNK, ADAM_MAX_TENSORS = 4096, 64                         # zt_adam_plan / zt_adam_step
 RANK_MIN_H, RANK_MAX_H = 4, 4352                                # zt_affinity_rank's hidden widths (H % 4 == 0)
+RANK_LOSS_SOFTMAX, RANK_LOSS_BCE = 0, 1                         # zt_rank_loss_forward's modes
 TOPK_MAX_K = 256                                                # zt_affinity_topk
 TOPK_FORM_LANE, TOPK_FORM_LANE4 = 1, 2                          # zt_affinity_topk_plan
 DECODER_H1, DECODER_H2 = 80, 10                                 # zt_node_decoder's hidden widths
@@ -159,7 +162,7 @@ def lib():
         _lib.zt_version.restype = C.c_char_p
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
                      "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes",
-                     "zt_node_decoder_train_workspace_bytes"):
+                     "zt_node_decoder_train_workspace_bytes", "zt_affinity_rank_train_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib

@@ -36,6 +36,7 @@ SOURCES = {
     "scoring_train.hip": [],
     "rank.hip": [],
     "rank_topk.hip": [],
+    "rank_train.hip": [],
     "seen.hip": [],
     "train_tail.hip": [],
     "decoder.hip": [],

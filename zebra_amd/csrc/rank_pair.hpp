@@ -74,6 +74,18 @@ __device__ __forceinline__ float rk_fold16x8(const float (&acc)[RK_NC], int gl)
 
 __device__ __forceinline__ float rk_prob(float s, float bias2) { return 1.f / (1.f + expf(-(s + bias2))); }
 
+// the logit rk_prob takes the sigmoid of (rank_train.hip writes it): 1 / (1 + expf(-rk_logit(s, b))) has rk_prob(s, b)'s bits
+__device__ __forceinline__ float rk_logit(float s, float bias2) { return s + bias2; }
+
+// z of four columns of one pair, formed as rk_pair_step forms it: the backward's ReLU mask is the forward's
+__device__ __forceinline__ void rk_pair_z(const float4 pq, const float4 pc, float (&z)[4])
+{
+    z[0] = pq.x + pc.x;
+    z[1] = pq.y + pc.y;
+    z[2] = pq.z + pc.z;
+    z[3] = pq.w + pc.w;
+}
+
 #endif  // __HIPCC__
 
 }  // namespace zt

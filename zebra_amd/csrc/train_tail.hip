@@ -100,6 +100,117 @@ __global__ __launch_bounds__(BCE_THREADS) void k_label_bce_fwd(const float *__re
     }
 }
 
+// Listwise loss of a ranking step (k_rank_loss_fwd): logit [Q][C] from the one-vs-many scorer (rank_train.hip), -inf where a
+// pair is absent; target[q] (NULL: column 0) is the positive's column.  A query whose target is absent (or outside [0, C)) is
+// skipped; n_live queries remain.
+//   softmax: loss = mean over live q of (logsumexp over present c of logit[q][c]) - logit[q][t_q],  dl = (softmax - onehot) / n_live
+//   bce:     loss = mean over live q of -max(log sigma(logit[q][t_q]), -100)
+//                 + mean over the n_neg present non-target pairs of live q of -max(log(1 - sigma(logit)), -100),
+//            dl = (sigma - 1) / n_live at a target, sigma / n_neg elsewhere (as BCELoss's backward: not cut off where the log is)
+// Absent pairs and skipped queries get dl = 0; with no live query the loss is 0.  The bce terms are formed from the LOGIT in
+// float64 (log1p(exp(-|l|)) forms), not from a float32 probability: 1 - p of a rounded p would lose log(1 - sigma) its digits
+// for l > 10.  The arithmetic rules are k_link_bce_fwd's: float64 exponentials, logarithms and sums, rounded to float32 once.
+// A wave owns a query: its lanes add their columns in ascending order and meet in a fixed tree; lane 0 adds the wave's queries
+// in ascending order and the waves are added first to last.  The counts n_live and n_neg are integers.
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    return __shfl(v, 0);
+}
+
+__global__ __launch_bounds__(BCE_THREADS) void k_rank_loss_fwd(const float *__restrict__ logit, const int *__restrict__ target, long long Q,
+                                                               long long C, int mode, float *__restrict__ loss, float *__restrict__ dl)
+{
+    __shared__ double part[2][BCE_WAVES];
+    __shared__ long long cnt[2][BCE_WAVES];
+    __shared__ long long total[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float NEG_INF = -INFINITY;
+    // the counts
+    long long nl = 0, nn = 0;
+    for (long long q = wave; q < Q; q += BCE_WAVES) {
+        const long long t = target != nullptr ? (long long)target[q] : 0;
+        if (t < 0 || t >= C || logit[q * C + t] == NEG_INF) continue;       // (wave-uniform)
+        ++nl;
+        for (long long cb = 0; cb < C; cb += WAVE) {
+            const long long c = cb + lane;
+            nn += __popcll(__ballot(c < C && c != t && logit[q * C + c] != NEG_INF));
+        }
+    }
+    if (lane == 0) { cnt[0][wave] = nl; cnt[1][wave] = nn; }
+    __syncthreads();
+    if (tid == 0) {
+        long long a = 0, b = 0;
+        for (int w = 0; w < BCE_WAVES; ++w) { a += cnt[0][w]; b += cnt[1][w]; }
+        total[0] = a;
+        total[1] = b;
+    }
+    __syncthreads();
+    const double n_live = (double)total[0], n_neg = (double)total[1];
+    double s0 = 0.0, s1 = 0.0;                                               // softmax: s0; bce: targets in s0, the others in s1
+    for (long long q = wave; q < Q; q += BCE_WAVES) {
+        const float *row = logit + q * C;
+        float *drow = dl + q * C;
+        const long long t = target != nullptr ? (long long)target[q] : 0;
+        const bool live = t >= 0 && t < C && row[t] != NEG_INF;
+        if (!live) {
+            for (long long c = lane; c < C; c += WAVE) drow[c] = 0.f;
+            continue;
+        }
+        if (mode == ZT_RANK_LOSS_SOFTMAX) {
+            float m = NEG_INF;
+            for (long long c = lane; c < C; c += WAVE) m = fmaxf(m, row[c]);
+            for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+            const double md = (double)m;                                     // finite: the target is present
+            double e = 0.0;
+            for (long long c = lane; c < C; c += WAVE) {
+                const float v = row[c];
+                if (v != NEG_INF) e += exp((double)v - md);
+            }
+            e = wave_sum(e);
+            const double lse = md + log(e);
+            s0 += lse - (double)row[t];
+            for (long long c = lane; c < C; c += WAVE) {
+                const float v = row[c];
+                double g = 0.0;
+                if (v != NEG_INF) g = (exp((double)v - lse) - (c == t ? 1.0 : 0.0)) / n_live;
+                drow[c] = (float)g;
+            }
+        } else {
+            double a = 0.0;
+            for (long long c = lane; c < C; c += WAVE) {
+                const float v = row[c];
+                if (v == NEG_INF) { drow[c] = 0.f; continue; }
+                const double l = (double)v, ea = exp(-fabs(l)), lp = log1p(ea);
+                const double sig = l >= 0.0 ? 1.0 / (1.0 + ea) : ea / (1.0 + ea);
+                if (c == t) {                                                // (its term of the loss: below, by every lane)
+                    drow[c] = (float)((sig - 1.0) / n_live);
+                } else {
+                    double lg = -(l >= 0.0 ? lp + l : lp);                   // log(1 - sigma(l))
+                    lg = lg < -100.0 ? -100.0 : lg;
+                    a -= lg;
+                    drow[c] = (float)(sig / n_neg);
+                }
+            }
+            s1 += wave_sum(a);
+            const double l = (double)row[t], lp = log1p(exp(-fabs(l)));
+            double lg = -(l >= 0.0 ? lp : lp - l);                           // log sigma(l)
+            lg = lg < -100.0 ? -100.0 : lg;
+            s0 -= lg;
+        }
+    }
+    if (lane == 0) { part[0][wave] = s0; part[1][wave] = s1; }
+    __syncthreads();
+    if (tid == 0) {
+        double t0 = 0.0, t1 = 0.0;
+        for (int w = 0; w < BCE_WAVES; ++w) { t0 += part[0][w]; t1 += part[1][w]; }    // the waves in order
+        double out = 0.0;
+        if (total[0] > 0) out = t0 / n_live;
+        if (mode != ZT_RANK_LOSS_SOFTMAX && total[1] > 0) out += t1 / n_neg;
+        loss[0] = (float)out;
+    }
+}
+
 // (a kernel argument: keep the layout.  3096 bytes of the 4 KB a launch may carry)
 struct AdamArgs {
     float *param[ADAM_MAX_TENSORS];
@@ -302,6 +413,40 @@ extern "C" int zt_label_bce_backward(const float *dprob_dev, const float *grad_l
     hipStream_t s = (hipStream_t)stream;
     ZT_PROF_BEGIN(s, P_LINK_BCE);
     k_link_bce_bwd<<<(unsigned)grid, 256, 0, s>>>(dprob_dev, grad_loss_dev, (long long)N, d_prob_dev);
+    ZT_PROF_END(s, P_LINK_BCE);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_rank_loss_forward(const float *logit_dev, const int32_t *target_dev, int64_t Q, int64_t C, int32_t mode, float *loss_dev,
+                                    float *dl_dev, void *stream)
+{
+    if (Q < 1 || C < 1 || C > INT64_MAX / Q || !logit_dev || !loss_dev || !dl_dev) {
+        set_error("zt_rank_loss_forward: bad argument (Q >= 1, C >= 1 and three device pointers expected)");
+        return ZT_ERR_ARG;
+    }
+    if (mode != ZT_RANK_LOSS_SOFTMAX && mode != ZT_RANK_LOSS_BCE) {
+        set_error("zt_rank_loss_forward: mode %d unknown (ZT_RANK_LOSS_SOFTMAX or ZT_RANK_LOSS_BCE)", mode);
+        return ZT_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ZT_PROF_BEGIN(s, P_LINK_BCE);
+    k_rank_loss_fwd<<<1, BCE_THREADS, 0, s>>>(logit_dev, target_dev, (long long)Q, (long long)C, mode, loss_dev, dl_dev);
+    ZT_PROF_END(s, P_LINK_BCE);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_rank_loss_backward(const float *dl_dev, const float *grad_loss_dev, int64_t n, float *d_logit_dev, void *stream)
+{
+    const long long grid = n < 1 ? 0 : (n - 1) / 256 + 1;
+    if (n < 1 || grid > 0x7fffffffll || !dl_dev || !grad_loss_dev || !d_logit_dev) {
+        set_error("zt_rank_loss_backward: bad argument (1 <= n within one launch and three device pointers expected)");
+        return ZT_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ZT_PROF_BEGIN(s, P_LINK_BCE);
+    k_link_bce_bwd<<<(unsigned)grid, 256, 0, s>>>(dl_dev, grad_loss_dev, (long long)n, d_logit_dev);
     ZT_PROF_END(s, P_LINK_BCE);
     ZT_LAUNCH_CHECK();
     return ZT_OK;

@@ -337,6 +337,95 @@ class _HipLinkScore(torch.autograd.Function):
         return tuple(outs)
 
 
+def rank_transpose(cand_idx, Nc):
+    """The transpose of an index matrix [Q, C] (int32, -1: absent) that zt_affinity_rank_train_backward walks:
+    (row_ptr int64 [Nc + 1], pairs int32 [n_present]) -- pairs[row_ptr[r]:row_ptr[r + 1]] are the ids q * C + c of the present
+    pairs that name row r, ascending (a stable sort of the pair ids by row).  Indices outside [0, Nc) count as absent."""
+    flat = cand_idx.reshape(-1)
+    ids = torch.nonzero((flat >= 0) & (flat < Nc)).squeeze(1)
+    rows = flat[ids]
+    order = torch.sort(rows, stable=True)[1]
+    pairs = ids[order].to(torch.int32)
+    row_ptr = torch.zeros(Nc + 1, dtype=torch.int64, device=cand_idx.device)
+    if Nc:
+        row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=Nc), 0)
+    return row_ptr, pairs
+
+
+class _HipRankScore(torch.autograd.Function):
+    """logit [Q, C] = MergeLayer(emb_q[q], emb_c[cand_idx[q, c]]) before the sigmoid, one query against many candidates, with
+    forward and backward on the HIP kernels of csrc/rank_train.hip (zt_affinity_rank_train_forward / _backward): the scorer of
+    a ranking training step.  ``cand_idx`` int32 [Q, C] names rows of ``emb_c`` (-1: absent, the logit is -inf and takes no
+    gradient) or is None: every query takes all of ``emb_c``.  sigmoid(logit), computed as 1 / (1 + exp(-logit)) in float32,
+    has the bits TGN.rank_scores returns.  Saved for the backward: the two projections P_q [Q, H] and P_c [Nc, H] and the
+    index's transpose (rank_transpose) -- never anything of Q C H elements.  IndexError when an index is >= Nc or < -1 (one
+    host read of the forward's status word per call; the backward walks the transpose built here and its status word is not
+    read).  H % 4 == 0, 4 <= H <= 4352 (tgn.rank_score_plan); no double backward."""
+
+    @staticmethod
+    def forward(ctx, emb_q, emb_c, cand_idx, fc1_w, fc1_b, fc2_w, fc2_b):
+        emb_q, emb_c = emb_q.contiguous(), emb_c.contiguous()
+        (Q, H), Nc = emb_q.shape, emb_c.shape[0]
+        if emb_c.dim() != 2 or emb_c.shape[1] != H or tuple(fc1_w.shape) != (H, 2 * H):
+            raise ValueError("_HipRankScore: emb_q [Q, H], emb_c [Nc, H] and fc1.weight [H, 2H] expected")
+        dev = emb_q.device
+        ix = None
+        if cand_idx is not None:
+            ix = cand_idx.to(dev, torch.int32).contiguous()
+            if ix.dim() != 2 or ix.shape[0] != Q:
+                raise ValueError("_HipRankScore: cand_idx [Q, C] expected")
+        C_ = Nc if ix is None else ix.shape[1]
+        par = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b)]
+        logit = torch.empty((Q, C_), dtype=torch.float32, device=dev)
+        pq = torch.empty((Q, H), dtype=torch.float32, device=dev)
+        pc = torch.empty((Nc, H), dtype=torch.float32, device=dev)
+        ctx.shapes = tuple(tuple(t.shape) for t in (emb_q, emb_c, fc1_w, fc1_b, fc2_w, fc2_b))
+        ctx.has_index = ix is not None
+        row_ptr = pairs = None
+        if Q and C_:
+            need = int(lib().zt_affinity_rank_train_workspace_bytes(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H)))
+            if need < 0:
+                raise ValueError("_HipRankScore: H=%d unsupported (H %% 4 == 0, 4 <= H <= 4352)" % H)
+            head = torch.empty(256, dtype=torch.uint8, device=dev)     # (the forward touches the status word only)
+            wt = _capi.AffinityWeights(*[ptr(t) for t in par])
+            check(lib().zt_affinity_rank_train_forward(ptr(emb_q), C.c_int64(Q), ptr(emb_c), C.c_int64(Nc), ptr(ix), C.c_int64(C_),
+                                                       C.c_int32(H), C.byref(wt), ptr(logit), ptr(pq), ptr(pc), ptr(head),
+                                                       stream_ptr()), "zt_affinity_rank_train_forward")
+            if ix is not None:
+                st = int(head[:4].view(torch.int32).item())
+                if st != 0:
+                    raise IndexError("zt_affinity_rank_train_forward: candidate index out of range (status %d)" % st)
+                if any(ctx.needs_input_grad):
+                    row_ptr, pairs = rank_transpose(ix, Nc)
+        saved = [emb_q, emb_c, pq, pc] + par + ([ix, row_ptr, pairs] if row_ptr is not None else [])
+        ctx.save_for_backward(*saved)
+        return logit
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dl):
+        emb_q, emb_c, pq, pc, w1, b1, w2, b2 = ctx.saved_tensors[:8]
+        ix, row_ptr, pairs = ctx.saved_tensors[8:] if len(ctx.saved_tensors) > 8 else (None, None, None)
+        (Q, H), Nc = emb_q.shape, emb_c.shape[0]
+        C_ = dl.shape[1]
+        dev = emb_q.device
+        need_grad = [ctx.needs_input_grad[i] for i in (0, 1, 3, 4, 5, 6)]
+        run = bool(Q and C_) and (not ctx.has_index or ix is not None)
+        new = torch.empty if run else torch.zeros                      # (no pair: the kernels are not launched)
+        outs = [new(shape, dtype=torch.float32, device=dev) if need else None for shape, need in zip(ctx.shapes, need_grad)]
+        if run and any(o is not None for o in outs):
+            need = int(lib().zt_affinity_rank_train_workspace_bytes(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H)))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            wt = _capi.AffinityWeights(ptr(w1), ptr(b1), ptr(w2), ptr(b2))
+            n_pairs = 0 if pairs is None else int(pairs.numel())
+            check(lib().zt_affinity_rank_train_backward(ptr(emb_q), C.c_int64(Q), ptr(emb_c), C.c_int64(Nc), ptr(ix), C.c_int64(C_),
+                                                        C.c_int32(H), C.byref(wt), ptr(pq), ptr(pc), ptr(dl.to(torch.float32).contiguous()),
+                                                        ptr(row_ptr), ptr(pairs if n_pairs else None), C.c_int64(n_pairs),
+                                                        *[ptr(o) for o in outs], ptr(ws), stream_ptr()),
+                  "zt_affinity_rank_train_backward")
+        return (outs[0], outs[1], None) + tuple(outs[2:])
+
+
 def _cell_rows_forward(ctx, fwd, saved_cols, w_ih, w_hh, b_ih, b_hh, messages, memory_t, ids32):
     U, D, msg = int(ids32.numel()), memory_t.shape[1], messages.shape[1]
     dev = memory_t.device
@@ -730,11 +819,14 @@ class GraphDiffusionEmbedding(nn.Module):
         return out
 
     def compute_embedding_tppr_ensemble(self, memory, source_nodes, timestamps, edge_idxs, memory_updater, train,
-                                        row_sel=None, on_device=None):
+                                        row_sel=None, on_device=None, extra=None):
         """modules/embedding_module.py:217-278.  ``memory`` is the Memory object
         in train mode and the raw memory tensor in eval mode, as in the reference.
         ``row_sel`` (train mode, optional): LongTensor of the rows to embed -- a data-parallel rank embeds (and
-        back-propagates through) its share of the batch only; the T-PPR update always covers the whole batch."""
+        back-propagates through) its share of the batch only; the T-PPR update always covers the whole batch.
+        ``extra`` (train mode, optional) = (nodes_d int32 [M], ts_d float64 [M]): M further rows to embed after the batch's
+        own -- the negatives of a ranking step (TGN.compute_rank_loss).  Their T-PPR rows are READ (``query_device``) from
+        the state BEFORE this batch's update and never write it; the batch itself then streams with the roles it has."""
         d = self.device
         if on_device is not None:                  # (the caller has the three arrays on the device already: TGN's training step)
             nodes_d, ts_d, eidx_d = on_device
@@ -743,12 +835,21 @@ class GraphDiffusionEmbedding(nn.Module):
                                                         np.ascontiguousarray(timestamps, np.float64),
                                                         np.ascontiguousarray(edge_idxs, np.int64)])
         t = time.time()
+        if extra is not None:
+            if not train or row_sel is not None:
+                raise ValueError("extra rows are embedded in a whole-batch training step only")
+            extra_rows = self.query_device(extra[0], extra[1]) if extra[0].numel() else None      # before the update
         on, oe, od, ow = self.topk_device(nodes_d, ts_d, eidx_d)
         if self.sync_timers:
             torch.cuda.synchronize()
         self.t_tppr += time.time() - t
         n_edge = ow.shape[1] // 3
         self._avg_topk_t = ow[0, : 2 * n_edge].sum(dim=1).mean()
+        if extra is not None:
+            self._avg_topk_t = ow[0].sum(dim=1).mean()             # (the batch streamed as [src | dst]: every row is a positive's)
+            if extra_rows is not None:
+                nodes_d = torch.cat([nodes_d, extra[0]])
+                on, oe, od, ow = [torch.cat([a, b], dim=1) for a, b in zip((on, oe, od, ow), extra_rows)]
         if not train:
             with torch.no_grad():
                 return self.embed_device(memory, nodes_d, on, oe, od, ow)

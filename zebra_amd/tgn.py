@@ -15,8 +15,8 @@ import torch
 
 from . import _capi
 from ._capi import check, lib, ptr, stream_ptr
-from .losses import _HipLinkBCE, link_bce_loss
-from .modules import Memory, MergeLayer, TimeEncode, _HipLinkScore, get_embedding_module, get_memory_updater
+from .losses import _HipLinkBCE, link_bce_loss, listwise_loss
+from .modules import Memory, MergeLayer, TimeEncode, _HipLinkScore, _HipRankScore, get_embedding_module, get_memory_updater
 
 
 def link_score_plan(device_type, dtype, H, fused_scoring=True):
@@ -26,6 +26,15 @@ def link_score_plan(device_type, dtype, H, fused_scoring=True):
     if not fused_scoring or device_type != "cuda" or dtype != torch.float32:
         return "torch"
     return "hip" if (H % 4 == 0 and 4 <= H <= 768) else "torch"
+
+
+def rank_score_plan(device_type, dtype, H, fused_scoring=True):
+    """Which one-vs-many scorer a ranking training step runs (pure host code, as link_score_plan): "hip" -- _HipRankScore --
+    when ``fused_scoring`` is on, the embeddings are float32 on the GPU and the hidden width is one zt_affinity_rank_train_*
+    takes (H % 4 == 0, 4 <= H <= 4352: zt_affinity_rank's widths); else "torch", MergeLayer's composition."""
+    if not fused_scoring or device_type != "cuda" or dtype != torch.float32:
+        return "torch"
+    return "hip" if (H % 4 == 0 and _capi.RANK_MIN_H <= H <= _capi.RANK_MAX_H) else "torch"
 
 
 def absent_columns(absent, n_cols):
@@ -560,6 +569,39 @@ class TGN(torch.nn.Module):
             return prob[:B].unsqueeze(1), prob[B:].unsqueeze(1)
         return self._score_pairs(emb[:B], emb[B:2 * B], emb[2 * B:])
 
+    def score_many_train(self, emb_q, emb_c, cand_idx=None):
+        """logits [Q, C] = affinity_score(emb_q[q], emb_c[cand_idx[q, c]]) before the sigmoid, differentiable: one source
+        against many candidates in a TRAINING step.  ``cand_idx`` int32 [Q, C] names rows of ``emb_c`` (-1: absent, the logit
+        is -inf and takes no gradient; IndexError for anything else outside [0, Nc)) or is None: every query takes all of
+        ``emb_c``.  csrc/rank_train.hip through _HipRankScore where rank_score_plan says so -- no [Q, C, H] tensor exists,
+        forward or backward -- else torch's composition under autograd, a chunk of queries at a time as in rank_scores."""
+        a = self.affinity_score
+        Q, H = emb_q.shape
+        Nc = emb_c.shape[0]
+        C_ = Nc if cand_idx is None else cand_idx.shape[1]
+        if (rank_score_plan(emb_q.device.type, emb_q.dtype, H, getattr(self, "fused_scoring", True)) == "hip"
+                and emb_c.is_cuda and emb_c.dtype == torch.float32):
+            with torch.cuda.device(emb_q.device):
+                return _HipRankScore.apply(emb_q, emb_c, cand_idx, a.fc1.weight, a.fc1.bias, a.fc2.weight, a.fc2.bias)
+        if Q == 0 or C_ == 0:
+            return torch.zeros((Q, C_), dtype=emb_q.dtype, device=emb_q.device)
+        ix = None
+        if cand_idx is not None:
+            ix = cand_idx.to(emb_q.device).long()
+            if int(ix.max()) >= Nc or int(ix.min()) < -1:
+                raise IndexError("score_many_train: candidate index out of range")
+        out = []
+        step = max(1, (1 << 24) // max(1, C_ * 2 * H))
+        for s in range(0, Q, step):
+            q = emb_q[s:s + step]
+            ec = emb_c.unsqueeze(0).expand(q.shape[0], Nc, H) if ix is None else emb_c[ix[s:s + step].clamp(min=0)]
+            x = torch.cat([q.unsqueeze(1).expand(-1, C_, -1), ec], dim=2)
+            lg = a.fc2(a.act(a.fc1(x))).squeeze(2)
+            if ix is not None:
+                lg = lg.masked_fill(ix[s:s + step] < 0, float("-inf"))
+            out.append(lg)
+        return torch.cat(out)
+
     def enable_scoring(self, on=True):
         """With the native pipeline: every whole-batch step also scores its 2B pairs behind its aggregation
         (zt_pipeline_set_scoring); ``last_prob()`` returns the last step's probabilities.  ValueError where the hidden width
@@ -1088,7 +1130,8 @@ class TGN(torch.nn.Module):
         and BCELoss of the positive pairs against ones plus BCELoss of the negative pairs against zeros.  Where link_score_plan
         says "hip" the [2B] vector of _HipLinkScore goes straight into _HipLinkBCE (csrc/train_tail.hip): no slice, squeeze or
         cat node enters the graph; otherwise the probabilities' composition with losses.link_bce_loss.  pos_prob and neg_prob
-        are detached [B, 1] views for the caller's metrics."""
+        are detached [B, 1] views for the caller's metrics.  The single negative's T-PPR row is emitted by the stream in batch
+        order (role 3 of its edge); compute_rank_loss, with many negatives, reads theirs from the state before the batch."""
         n_samples = len(source_nodes)
         s, dd, n = self.compute_temporal_embeddings(source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs,
                                                     n_neighbors, True)
@@ -1103,6 +1146,59 @@ class TGN(torch.nn.Module):
             return loss, prob[:n_samples].unsqueeze(1), prob[n_samples:].unsqueeze(1)
         pos, neg = self._score_pairs(s, dd, n)
         return link_bce_loss(pos, neg), pos.detach(), neg.detach()
+
+    def compute_rank_loss(self, source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs, n_neighbors,
+                          mode="softmax", edge_sel=None):
+        """(loss, logits) of ONE training step that ranks every edge's destination against K negatives: ``negative_nodes`` is
+        [B, K], K >= 1, -1 = absent (a filtered sampler drops a source's true partners this way); ``mode`` is listwise_loss's
+        ("softmax": cross-entropy of column 0 over the present columns; "bce": compute_edge_loss's loss with the negatives'
+        term averaged over all present negatives).  logits [B, 1 + K] (column 0: the destination; -inf: absent) is detached,
+        for the caller's metrics.
+        The negatives' convention is eval_edge_ranking's, NOT compute_edge_loss's: the T-PPR rows of the present negatives are
+        read (``query_device``), each at its edge's timestamp, from the state BEFORE the batch, where compute_edge_loss's
+        single negative is emitted by the stream in batch order -- a negative that is an endpoint of an earlier edge of
+        the batch sees that edge there and not here.  A negative that is no endpoint of the batch reads the same row either
+        way.  Then the step is compute_temporal_embeddings(train=True)'s: the T-PPR stream runs over [src | dst] (negatives
+        never write state), GraphDiffusionEmbedding._train_forward embeds the 2B + n_present rows at once, the memory update
+        and the message store follow, score_many_train scores the sources against [destinations | negatives] and
+        listwise_loss finishes.  ValueError for negatives that are not [B, K >= 1] or for ``edge_sel`` (data-parallel shares
+        are not covered); RuntimeError with the native pipeline (and so an exchange) enabled."""
+        if edge_sel is not None:
+            raise ValueError("compute_rank_loss does not cover data-parallel shares (edge_sel)")
+        neg = np.asarray(negative_nodes)
+        B = len(source_nodes)
+        if neg.ndim != 2 or neg.shape[0] != B or neg.shape[1] < 1:
+            raise ValueError("compute_rank_loss takes negative_nodes [B, K] with K >= 1 (-1: absent)")
+        if getattr(self, "_pipe", None) is not None or getattr(self, "_xchg", None) is not None:
+            raise RuntimeError("compute_rank_loss does not cover the native pipeline or its exchange: call "
+                               "enable_pipeline(False) first")
+        K = neg.shape[1]
+        self.batch_counter += 1
+        positives = np.concatenate([source_nodes, destination_nodes])
+        self.n_update_memory += len(positives)
+        self.test_mode = False
+        # the index of the scorer and the negatives' (node, time) list, on the host: nothing of it waits for the device
+        present = neg >= 0
+        n_present = int(present.sum())
+        cand_idx = np.full((B, 1 + K), -1, np.int32)
+        cand_idx[:, 0] = np.arange(B, dtype=np.int32)                    # emb_c = [destinations | present negatives]
+        cand_idx[:, 1:][present] = B + np.arange(n_present, dtype=np.int32)
+        neg_ts = np.broadcast_to(np.asarray(edge_times, np.float64).reshape(B, 1), (B, K))[present]
+        src_d, dst_d, ts_d, eidx_d, upos_d, negn_d, negts_d, cand_d = _capi.to_device(self.device, [
+            np.ascontiguousarray(source_nodes, np.int32), np.ascontiguousarray(destination_nodes, np.int32),
+            np.ascontiguousarray(edge_times, np.float64), np.ascontiguousarray(edge_idxs, np.int64),
+            np.ascontiguousarray(np.unique(positives), np.int32), np.ascontiguousarray(neg[present], np.int32),
+            np.ascontiguousarray(neg_ts, np.float64), cand_idx])
+        emb = self.embedding_module.compute_embedding_tppr_ensemble(
+            memory=self.memory, source_nodes=positives, timestamps=None, edge_idxs=edge_idxs, memory_updater=self.memory_updater,
+            train=True, on_device=(torch.cat([src_d, dst_d]), ts_d.repeat(2), eidx_d), extra=(negn_d, negts_d))
+        # update memory without gradients, THEN collect raw messages (:155-168), as compute_temporal_embeddings(train=True)
+        with torch.no_grad():
+            self.memory_updater.update_device(self.memory, upos_d, upos_d.numel())
+            self.store_messages_device(src_d, dst_d, ts_d, eidx_d)
+        self._last_node_embedding = self._last_node_block = None
+        logits = self.score_many_train(emb[:B], emb[B:], cand_d)
+        return listwise_loss(logits, None, mode), logits.detach()
 
     def update_memory(self, memory, positives):
         with torch.no_grad():
