@@ -928,6 +928,55 @@ int zt_csr_seen_ranges(const zt_csr *c, const int32_t *q_nodes_dev, const double
 int zt_exclude_mark(const zt_csr *c, const int32_t *ids_dev, const int64_t *begin_dev, const int64_t *len_dev, int64_t Q,
                     int64_t id_lo, const int32_t *cand_sorted_dev, const int32_t *cand_col_dev, int64_t cand_stride,
                     int64_t C, uint32_t *absent_dev, int64_t absent_words, void *stream);
+/* Negative sampling on the device (csrc/neg_sample.hip): up to K negatives for each of Q edges (src_dev[q], dst_dev[q]),
+ * drawn reproducibly from the edge's own id list and from the destination pool pool_dev [n_pool], with the exclusions
+ * applied while drawing.
+ * THE ROW'S LIST.  For row q the list is ids[begin_dev[q] .. begin_dev[q] + len_dev[q]); ids is ids_dev, or the handle's
+ * neighbour array when ids_dev is NULL: zt_exclude_mark's convention -- a negative begin or len gives an empty list, a range
+ * of the handle's array is clipped to it (`len` below is the clipped length), duplicates and negative ids may occur.  c,
+ * ids_dev, begin_dev and len_dev all NULL (or begin_dev and len_dev NULL) means every list is empty.
+ * THE RULE.  Slots j < K_hist are HISTORICAL slots and the others are POOL slots.  All slots start empty.  In round
+ * r = 0 .. rounds - 1, every slot that is still empty draws one id:
+ *   - x is word 0 of Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *     (row & 0xffffffff, row >> 32, j, r), row = row_base + q;
+ *   - a historical slot with r < hist_rounds and len > 0 draws id = ids[begin + ((x * len) >> 32)]  (a LIST draw);
+ *   - every other slot draws id = pool[(x * n_pool) >> 32]  (a POOL draw);
+ *   - both products are 64-bit; len and n_pool are below 2^31.
+ * The draw PASSES unless one of these holds:
+ *   - id < 0;
+ *   - id == dst[q];
+ *   - ZT_NEG_EXCLUDE_SOURCE is set and id == src[q];
+ *   - ZT_NEG_FILTER is set, it is a pool draw, and id occurs in the row's list;
+ *   - ZT_NEG_DISTINCT is set and a slot filled in an earlier round holds id.
+ * A passing draw is ACCEPTED unless ZT_NEG_DISTINCT is set and a lower-numbered slot's draw of the same round passed with
+ * the same id.  Accepted draws fill their slots.  After the last round, empty slots read -1.
+ * Every element of neg_dev [Q][K] is written; count_dev[q] (where not NULL) is (slots filled from the list, slots filled from
+ * the pool).  The result is a function of the arguments alone -- not of the grid, not of the batch a row arrives in: a pass
+ * over a split numbers its rows by row_base.  One workgroup per row, no global atomics, no row waits for another; under
+ * ZT_NEG_FILTER a round that still has pool draws pending reads the row's list once.
+ * zt_neg_sample_plan (host code only): out[0] = the form (0: K outside 1 .. ZT_NEG_MAX_K, refused -- still ZT_OK;
+ * 1: one wave, K <= 128; 2: a workgroup of several waves), out[1] = threads of the workgroup, out[2] = the sort width (the
+ * power of two >= max(K, 64)), out[3] = dynamic LDS bytes.  NULL out: ZT_ERR_ARG.
+ * ZT_ERR_ARG before any device call: NULL d, src_dev, dst_dev, pool_dev or neg_dev; Q < 0; n_pool <= 0 with Q > 0; K outside
+ * 1 .. ZT_NEG_MAX_K; K_hist outside 0 .. K; rounds outside 1 .. ZT_NEG_MAX_ROUNDS; hist_rounds outside 0 .. rounds; unknown
+ * flag bits; begin_dev without len_dev or the reverse; lists with neither c nor ids_dev.  n_pool >= 2^31, a handle of 2^31
+ * entries or more, or Q beyond one launch's workgroups: ZT_ERR_UNSUPPORTED (a list of the caller's ids_dev is read up to
+ * 2^31 - 1 entries).  Q = 0: ZT_OK, nothing touched. */
+#define ZT_NEG_MAX_K 4096
+#define ZT_NEG_MAX_ROUNDS 8
+#define ZT_NEG_FILTER 1         /* a pool draw that is in the row's list is rejected */
+#define ZT_NEG_DISTINCT 2       /* no id twice in a row */
+#define ZT_NEG_EXCLUDE_SOURCE 4 /* the row's source is rejected */
+typedef struct zt_neg_desc {
+    uint64_t seed;
+    int64_t row_base;
+    int32_t K, K_hist, rounds, hist_rounds, flags;
+} zt_neg_desc;
+int zt_neg_sample_plan(int32_t K, int64_t *out);
+int zt_neg_sample(const zt_neg_desc *d, const int32_t *src_dev, const int32_t *dst_dev, int64_t Q,
+                  const int32_t *pool_dev, int64_t n_pool,
+                  const zt_csr *c, const int32_t *ids_dev, const int64_t *begin_dev, const int64_t *len_dev,
+                  int32_t *neg_dev, int32_t *count_dev, void *stream);
 /* Ranks, MRR and Hits@k of prob_dev [Q][C] (cand_idx_dev as above, may be NULL: every entry present).  Column 0 is the
  * positive:  rank = 1 + #{c >= 1 present : p_c > p_0} + 0.5 #{c >= 1 present : p_c == p_0}, the mean of the optimistic and
  * the pessimistic rank.  A query whose column 0 is absent is skipped and not counted.  rank_dev [Q] (or NULL) receives the

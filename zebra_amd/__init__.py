@@ -24,4 +24,7 @@ def __getattr__(name):
     if name == "MLP":
         from .decoder import MLP
         return MLP
+    if name == "NegativeSampler":
+        from .sampling import NegativeSampler
+        return NegativeSampler
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

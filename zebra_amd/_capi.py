@@ -41,6 +41,7 @@ SYMBOLS = [
     "zt_node_decoder_train_backward", "zt_label_bce_forward", "zt_label_bce_backward",
     "zt_affinity_rank_train_workspace_bytes", "zt_affinity_rank_train_forward", "zt_affinity_rank_train_backward",
     "zt_rank_loss_forward", "zt_rank_loss_backward",
+    "zt_neg_sample_plan", "zt_neg_sample",
 ]
 
 
@@ -68,6 +69,9 @@ DECODER_H1, DECODER_H2 = 80, 10                                 # zt_node_decode
 DECODER_MIN_H, DECODER_MAX_H = RANK_MIN_H, RANK_MAX_H           # ... and its input widths (H % 4 == 0)
 DECODER_ARR_ONE, DECODER_ARR_FIVE = 1, 5                        # zt_node_decoder_plan
 DECODER_PLAN_FIELDS = ("arrangement", "waves", "rows", "k_chunk", "grid", "lds_bytes", "split", "k_per")
+NEG_MAX_K, NEG_MAX_ROUNDS = 4096, 8                             # zt_neg_sample
+NEG_FILTER, NEG_DISTINCT, NEG_EXCLUDE_SOURCE = 1, 2, 4
+NEG_FORM_REFUSED, NEG_FORM_WAVE, NEG_FORM_WORKGROUP = 0, 1, 2   # zt_neg_sample_plan
 TOPK_PLAN_FIELDS = ("form", "wave_queries", "q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid_pairs", "grid_merge",
                     "lists_offset", "pc_offset", "min_bytes")
 
@@ -137,6 +141,11 @@ class ExchangeDesc(C.Structure):
 class AdamTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("numel", C.c_int64), ("step_size", C.c_float), ("bias2_sqrt", C.c_float)]
+
+
+class NegDesc(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("row_base", C.c_int64), ("K", C.c_int32), ("K_hist", C.c_int32),
+                ("rounds", C.c_int32), ("hist_rounds", C.c_int32), ("flags", C.c_int32)]
 
 
 class Batch(C.Structure):
@@ -214,6 +223,14 @@ def topk_plan(Q, Nc, C_, H, K, indexed, workspace_bytes):
     check(lib().zt_affinity_topk_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H), C.c_int32(K),
                                       C.c_int32(1 if indexed else 0), C.c_int64(workspace_bytes), out), "zt_affinity_topk_plan")
     return {name: int(out[i]) for i, name in enumerate(TOPK_PLAN_FIELDS)}
+
+
+def neg_sample_plan(K):
+    """zt_neg_sample_plan: the form (0: K is refused), the workgroup's threads, the sort width and the LDS bytes of the
+    negative sampler's kernel for K slots per row (host code only)."""
+    out = (C.c_int64 * 4)()
+    check(lib().zt_neg_sample_plan(C.c_int32(K), out), "zt_neg_sample_plan")
+    return dict(form=int(out[0]), threads=int(out[1]), n2=int(out[2]), lds_bytes=int(out[3]))
 
 
 def decoder_plan(N, H, training=False):

@@ -38,6 +38,7 @@ SOURCES = {
     "rank_topk.hip": [],
     "rank_train.hip": [],
     "seen.hip": [],
+    "neg_sample.hip": [],
     "train_tail.hip": [],
     "decoder.hip": [],
     "exchange.hip": [],

@@ -234,7 +234,10 @@ def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_siz
     ``filtered=True`` is the filtered protocol: a negative does not count where it is one of the source's true partners --
     a partner strictly before the edge's timestamp in ``finder`` (None: ``model.neighbor_finder``; ValueError if there is
     none), or the edge's own destination.  The positive, column 0, always counts.  The absent columns are marked on the device
-    (TGN.absent_bits) and reach zt_rank_metrics as cand_idx = -1; still one host read at the end."""
+    (TGN.absent_bits) and reach zt_rank_metrics as cand_idx = -1; still one host read at the end.
+    A sampler that has ``sample_for`` (zebra_amd.sampling.NegativeSampler) draws per edge on the device instead: it is called
+    with the batch's sources, destinations and timestamps and ``row_base`` = the batch's position in the split, and its rows
+    [B, n_negatives] are used as they are -- a -1 is an absent column, never ranked against; ``filtered`` ORs its masks on top."""
     assert negative_edge_sampler.seed is not None
     if filtered and finder is None and model.neighbor_finder is None:
         raise ValueError("eval_edge_ranking(filtered=True) needs a finder: the model has no neighbor_finder")
@@ -245,8 +248,31 @@ def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_siz
         model.test_mode = True
     n = data.n_interactions
     acc = torch.zeros(5, dtype=torch.float64, device=model.device)
+    on_device = hasattr(negative_edge_sampler, "sample_for")      # zebra_amd.sampling.NegativeSampler
     for s in range(0, n, batch_size):
         e = min(n, s + batch_size)
+        if on_device:
+            # per-edge negatives drawn on the device, row s + b of the split: the rows are used as they are, a -1 is an absent
+            # column for rank_candidates and for zt_rank_metrics; the eval step's single negative is the first column, or
+            # the edge's destination where that is -1 (its one read-back per batch, beside the step's own status read)
+            neg_d, _ = negative_edge_sampler.sample_for(data.sources[s:e], data.destinations[s:e], data.timestamps[s:e],
+                                                        n_negatives, row_base=s)
+            neg_d = neg_d.to(model.device)
+            dst_d = torch.from_numpy(np.ascontiguousarray(data.destinations[s:e], np.int32)).to(model.device)
+            cand_d = torch.cat([dst_d.reshape(-1, 1), neg_d], dim=1).contiguous()
+            prob = model.rank_candidates(data.sources[s:e], data.timestamps[s:e], cand_d)
+            gone = cand_d < 0
+            if filtered:
+                from .tgn import absent_columns
+                bits = model.absent_bits(data.sources[s:e], data.timestamps[s:e], finder if finder is not None else "seen",
+                                         candidates=cand_d)
+                gone = gone | absent_columns(bits, cand_d.shape[1]) | (cand_d == cand_d[:, :1])
+                gone[:, 0] = False                                   # the positive is never filtered
+            rank_metrics(prob.float(), -gone.to(torch.int32), out=acc)
+            first = torch.where(neg_d[:, 0] >= 0, neg_d[:, 0], dst_d).cpu().numpy()
+            model.compute_temporal_embeddings(data.sources[s:e], data.destinations[s:e], first, data.timestamps[s:e],
+                                              data.edge_idxs[s:e], n_neighbors, False)
+            continue
         _, negatives = negative_edge_sampler.sample((e - s) * n_negatives)
         negatives = np.asarray(negatives).reshape(e - s, n_negatives)
         cands = np.concatenate([np.asarray(data.destinations[s:e]).reshape(-1, 1), negatives], axis=1)

@@ -1150,7 +1150,8 @@ class TGN(torch.nn.Module):
     def compute_rank_loss(self, source_nodes, destination_nodes, negative_nodes, edge_times, edge_idxs, n_neighbors,
                           mode="softmax", edge_sel=None):
         """(loss, logits) of ONE training step that ranks every edge's destination against K negatives: ``negative_nodes`` is
-        [B, K], K >= 1, -1 = absent (a filtered sampler drops a source's true partners this way); ``mode`` is listwise_loss's
+        [B, K], K >= 1, -1 = absent (a filtered sampler drops a source's true partners this way) -- a numpy array, or an int32
+        tensor such as zebra_amd.sampling.NegativeSampler.sample_for returns, which is read back once; ``mode`` is listwise_loss's
         ("softmax": cross-entropy of column 0 over the present columns; "bce": compute_edge_loss's loss with the negatives'
         term averaged over all present negatives).  logits [B, 1 + K] (column 0: the destination; -inf: absent) is detached,
         for the caller's metrics.
@@ -1165,6 +1166,8 @@ class TGN(torch.nn.Module):
         are not covered); RuntimeError with the native pipeline (and so an exchange) enabled."""
         if edge_sel is not None:
             raise ValueError("compute_rank_loss does not cover data-parallel shares (edge_sel)")
+        if torch.is_tensor(negative_nodes):                              # NegativeSampler.sample_for's rows: read back once --
+            negative_nodes = negative_nodes.detach().cpu().numpy()       # the index below is built on the host
         neg = np.asarray(negative_nodes)
         B = len(source_nodes)
         if neg.ndim != 2 or neg.shape[0] != B or neg.shape[1] < 1:
