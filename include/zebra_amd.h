@@ -905,6 +905,52 @@ int zt_affinity_topk_masked(const float *emb_q_dev, int64_t Q, const float *emb_
                             int32_t *top_idx_dev, float *top_prob_dev,
                             void *workspace_dev, int64_t workspace_bytes,
                             const uint32_t *absent_dev, int64_t absent_words, void *stream);
+/* Where a probability stands in a shared pool (csrc/rank_count.hip) without prob[Q][C]: for every query the number of present
+ * candidates whose probability is ABOVE thr_dev[q] and the number EQUAL to it -- what a full-pool rank needs.  emb_q_dev,
+ * emb_c_dev, the weights and the width bound (H % 4 == 0, 4 <= H <= 4352; ZT_ERR_UNSUPPORTED otherwise, before any launch) are
+ * zt_affinity_rank's, and every pair's probability has the bits zt_affinity_rank writes for it (csrc/rank_pair.hpp).  The
+ * shared pool only: every query takes all Nc rows in order, C == Nc (a per-query table goes through zt_affinity_rank and
+ * zt_rank_metrics).
+ *   Present: the shared form of zt_affinity_topk_masked's rule -- the candidate's projected row is not NaN, nor the
+ *   probability; the global column idx_base + c differs from every one of skip_dev[q][0 .. n_skip) (int32 [Q][n_skip],
+ *   0 <= n_skip <= ZT_COUNT_MAX_SKIP, -1: none; skip_dev may be NULL when n_skip == 0); and bit c & 31 of word c >> 5 of row q
+ *   of absent_dev [Q][absent_words] is clear, c the LOCAL column (ABSENT BITS, above; absent_dev == NULL: no bits).
+ *   above_dev[q] = #{present c : p > thr[q]}, equal_dev[q] = #{present c : p == thr[q]} (int32 [Q]): IEEE float compares, so a
+ *   NaN threshold counts nothing and -0.0 equals +0.0.  accumulate != 0: the counts are ADDED to what the outputs hold; a pool
+ *   given in pieces, in any order, each with its idx_base and its own local bits, gives the numbers of one call.  Integer
+ *   sums: the result is a function of the inputs alone, whatever the workspace, slabs, spans or grid.
+ * Q = 0: ZT_OK, nothing touched.  Nc = 0: ZT_OK, zeros written, or the outputs left alone under accumulate.  ZT_ERR_ARG before
+ * any device call: a NULL emb_q_dev, emb_c_dev, w, thr_dev, above_dev, equal_dev or workspace_dev; a negative Q, Nc or
+ * idx_base; n_skip outside 0 .. ZT_COUNT_MAX_SKIP, or n_skip > 0 with skip_dev NULL; a non-NULL absent_dev with
+ * absent_words < ceil(Nc / 32); idx_base + Nc > INT32_MAX; a workspace below the minimum.
+ * workspace_dev, 16-byte aligned, of workspace_bytes bytes as the caller states them: a head of 256 bytes, P_q, and P_c of ONE
+ * SLAB of candidate rows -- per slab the f32 MFMA GEMM and one launch of the pair kernel over spans of candidate columns,
+ * whose workgroups add their counts into the outputs with integer atomics (no partial counts in the workspace, no reduce
+ * launch).  zt_affinity_count_workspace_bytes(Q, Nc, H) is the recommended size (-1: H unsupported, or a negative size); it
+ * stops growing once Nc exceeds the slab cap (128 MiB of P_c, or 2^18 rows).  Its value for Nc = 32 is the smallest size
+ * accepted.  zt_affinity_count_plan is where the slab rows, the spans and the grid are decided (host code only).  No float
+ * atomics, no workgroup waits for another. */
+#define ZT_COUNT_MAX_SKIP 4
+#define ZT_COUNT_PLAN_FIELDS 9
+/* plan_out[ZT_COUNT_PLAN_FIELDS], all int64:
+ *   [0] q_tiles      tiles of 4 queries
+ *   [1] slab_rows    rows of P_c the workspace holds (a multiple of 32)
+ *   [2] n_slabs      slabs the pool is walked in: n_slabs * slab_rows >= Nc
+ *   [3] span_cols    candidate columns of a slab per span (a multiple of 128, a workgroup's step)
+ *   [4] n_spans      spans per slab
+ *   [5] grid         workgroups of the pair kernel, per slab: q_tiles * n_spans
+ *   [6] h_chunks     chunks of 1024 columns the hidden width runs in
+ *   [7] pc_offset    byte offset of the slab's P_c in the workspace
+ *   [8] min_bytes    the smallest workspace accepted
+ * ZT_ERR_ARG for NULL plan_out, a negative size or a workspace below min_bytes; H as above. */
+int64_t zt_affinity_count_workspace_bytes(int64_t Q, int64_t Nc, int32_t H);
+int zt_affinity_count(const float *emb_q_dev, int64_t Q, const float *emb_c_dev, int64_t Nc, int32_t H,
+                      const zt_affinity_weights *w, const float *thr_dev,
+                      const int32_t *skip_dev, int32_t n_skip, int64_t idx_base, int32_t accumulate,
+                      int32_t *above_dev, int32_t *equal_dev,
+                      void *workspace_dev, int64_t workspace_bytes,
+                      const uint32_t *absent_dev, int64_t absent_words, void *stream);
+int zt_affinity_count_plan(int64_t Q, int64_t Nc, int32_t H, int64_t workspace_bytes, int64_t *plan_out);
 /* Exclusion lists from the adjacency (csrc/seen.hip).  For query (v, t) = (q_nodes_dev[q], q_ts_dev[q]): begin_dev[q] =
  * indptr[v], len_dev[q] = the number of v's entries with a timestamp strictly below t -- the prefix zt_csr_find_before
  * returns, so an entry AT t is not seen.  The partners themselves are entries [begin, begin + len) of the handle's neighbour
@@ -987,6 +1033,15 @@ int zt_neg_sample(const zt_neg_desc *d, const int32_t *src_dev, const int32_t *d
  * call. */
 int zt_rank_metrics(const float *prob_dev, const int32_t *cand_idx_dev, int64_t Q, int64_t C, float *rank_dev,
                     double *acc_dev, void *stream);
+/* The same sums from counts (zt_affinity_count's above_dev / equal_dev, with the thresholds they were taken at):
+ * rank = 1 + above + 0.5 equal in FLOAT64 -- a pool of ten million ids does not fit a float32 rank.  A query whose threshold
+ * is NaN is skipped and not counted; its rank is 0.  rank_dev [Q] (float64, or NULL) receives the ranks.  acc_dev [5] is ADDED
+ * to in zt_rank_metrics's layout and order (sum of 1 / rank, Hits@1, Hits@3, Hits@10, queries counted), one lane adding first
+ * to last: where every rank is below 2^23 the sums have the bits zt_rank_metrics gives for the same ranks in the same order.
+ * Q = 0: ZT_OK, nothing touched; NULL thr_dev / above_dev / equal_dev / acc_dev or Q < 0: ZT_ERR_ARG before any device
+ * call. */
+int zt_rank_metrics_counts(const float *thr_dev, const int32_t *above_dev, const int32_t *equal_dev, int64_t Q,
+                           double *rank_dev, double *acc_dev, void *stream);
 #define ZT_METRICS_FORM_REFUSED 0
 #define ZT_METRICS_FORM_SINGLE 1 /* one bitonic sort of 2B 64-bit (key | label) words */
 #define ZT_METRICS_FORM_SPLIT 2  /* positives and negatives sorted as two runs of 32-bit keys */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "zt_affinity_rank_train_workspace_bytes", "zt_affinity_rank_train_forward", "zt_affinity_rank_train_backward",
     "zt_rank_loss_forward", "zt_rank_loss_backward",
     "zt_neg_sample_plan", "zt_neg_sample",
+    "zt_affinity_count_workspace_bytes", "zt_affinity_count", "zt_affinity_count_plan", "zt_rank_metrics_counts",
 ]
 
 
@@ -72,6 +73,8 @@ DECODER_PLAN_FIELDS = ("arrangement", "waves", "rows", "k_chunk", "grid", "lds_b
 NEG_MAX_K, NEG_MAX_ROUNDS = 4096, 8                             # zt_neg_sample
 NEG_FILTER, NEG_DISTINCT, NEG_EXCLUDE_SOURCE = 1, 2, 4
 NEG_FORM_REFUSED, NEG_FORM_WAVE, NEG_FORM_WORKGROUP = 0, 1, 2   # zt_neg_sample_plan
+COUNT_MAX_SKIP = 4                                              # zt_affinity_count
+COUNT_PLAN_FIELDS = ("q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid", "h_chunks", "pc_offset", "min_bytes")
 TOPK_PLAN_FIELDS = ("form", "wave_queries", "q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid_pairs", "grid_merge",
                     "lists_offset", "pc_offset", "min_bytes")
 
@@ -171,7 +174,8 @@ def lib():
         _lib.zt_version.restype = C.c_char_p
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
                      "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes",
-                     "zt_node_decoder_train_workspace_bytes", "zt_affinity_rank_train_workspace_bytes"):
+                     "zt_node_decoder_train_workspace_bytes", "zt_affinity_rank_train_workspace_bytes",
+                     "zt_affinity_count_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib
@@ -223,6 +227,15 @@ def topk_plan(Q, Nc, C_, H, K, indexed, workspace_bytes):
     check(lib().zt_affinity_topk_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int64(C_), C.c_int32(H), C.c_int32(K),
                                       C.c_int32(1 if indexed else 0), C.c_int64(workspace_bytes), out), "zt_affinity_topk_plan")
     return {name: int(out[i]) for i, name in enumerate(TOPK_PLAN_FIELDS)}
+
+
+def count_plan(Q, Nc, H, workspace_bytes):
+    """zt_affinity_count_plan: the slab rows, spans and grid of one zt_affinity_count call over a pool of Nc rows (host code
+    only)."""
+    out = (C.c_int64 * len(COUNT_PLAN_FIELDS))()
+    check(lib().zt_affinity_count_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int32(H), C.c_int64(workspace_bytes), out),
+          "zt_affinity_count_plan")
+    return {name: int(out[i]) for i, name in enumerate(COUNT_PLAN_FIELDS)}
 
 
 def neg_sample_plan(K):

@@ -36,6 +36,7 @@ SOURCES = {
     "scoring_train.hip": [],
     "rank.hip": [],
     "rank_topk.hip": [],
+    "rank_count.hip": [],
     "rank_train.hip": [],
     "seen.hip": [],
     "neg_sample.hip": [],

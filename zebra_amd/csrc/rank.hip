@@ -6,6 +6,7 @@
 //                          s = b2 + sum_h w2[h] relu((P_q[q][h] + b1[h]) + P_c[idx][h]),
 //                      which is no GEMM (the relu sits inside the sum over h): k_rank_pairs.
 //   zt_rank_metrics    rank of column 0 among the present candidates of each query, and MRR / Hits@1,3,10 sums.
+//   zt_rank_metrics_counts  the same sums from counts taken elsewhere (rank_count.hip: above and equal over a whole pool).
 #include "common.hpp"
 #include "rank_pair.hpp"
 
@@ -140,6 +141,43 @@ __global__ __launch_bounds__(WAVE * RM_WAVES) void k_rank_metrics(const float *_
         for (int i = 0; i < 5; ++i) acc[i] = sum[i];
 }
 
+// k_rank_metrics' sums from counts: rank = 1 + above + 0.5 equal in float64 (a pool of ten million ids does not fit a float32
+// rank; below 2^23 the rank, its reciprocal and the compares are the ones k_rank_metrics forms from its float32 rank), 0 for
+// a query whose threshold is NaN.  One workgroup, a query per thread and chunk; ONE lane adds first to last.
+__global__ __launch_bounds__(RM_CHUNK) void k_rank_metrics_counts(const float *__restrict__ thr, const int *__restrict__ above,
+                                                                  const int *__restrict__ equal, long long Q,
+                                                                  double *__restrict__ rank_out, double *__restrict__ acc)
+{
+    __shared__ double s_rank[RM_CHUNK];         // 0: the query is skipped
+    double sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 5; ++i) sum[i] = acc[i];
+    for (long long qc = 0; qc < Q; qc += RM_CHUNK) {
+        const int nq = (int)min((long long)RM_CHUNK, Q - qc);
+        if ((int)threadIdx.x < nq) {
+            const long long q = qc + threadIdx.x;
+            const float t = thr[q];
+            const double rank = t == t ? 1.0 + (double)above[q] + 0.5 * (double)equal[q] : 0.0;
+            s_rank[threadIdx.x] = rank;
+            if (rank_out != nullptr) rank_out[q] = rank;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int qi = 0; qi < nq; ++qi) {
+                const double r = s_rank[qi];
+                if (r == 0.0) continue;
+                sum[0] += 1.0 / r;
+                sum[1] += r <= 1.0 ? 1.0 : 0.0;
+                sum[2] += r <= 3.0 ? 1.0 : 0.0;
+                sum[3] += r <= 10.0 ? 1.0 : 0.0;
+                sum[4] += 1.0;
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 5; ++i) acc[i] = sum[i];
+}
+
 }  // namespace
 
 extern "C" int64_t zt_affinity_rank_workspace_bytes(int64_t Q, int64_t Nc, int32_t H)
@@ -202,6 +240,19 @@ extern "C" int zt_rank_metrics(const float *prob_dev, const int32_t *cand_idx_de
     }
     if (Q == 0 || C == 0) return ZT_OK;
     k_rank_metrics<<<1, WAVE * RM_WAVES, 0, (hipStream_t)stream>>>(prob_dev, cand_idx_dev, Q, C, rank_dev, acc_dev);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+}
+
+extern "C" int zt_rank_metrics_counts(const float *thr_dev, const int32_t *above_dev, const int32_t *equal_dev, int64_t Q,
+                                      double *rank_dev, double *acc_dev, void *stream)
+{
+    if (!thr_dev || !above_dev || !equal_dev || !acc_dev || Q < 0) {
+        set_error("zt_rank_metrics_counts: bad argument");
+        return ZT_ERR_ARG;
+    }
+    if (Q == 0) return ZT_OK;
+    k_rank_metrics_counts<<<1, RM_CHUNK, 0, (hipStream_t)stream>>>(thr_dev, above_dev, equal_dev, Q, rank_dev, acc_dev);
     ZT_LAUNCH_CHECK();
     return ZT_OK;
 }

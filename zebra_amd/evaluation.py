@@ -223,6 +223,72 @@ def rank_metrics(prob, cand_idx=None, out=None, ranks=False):
     return (acc, rk) if ranks else acc
 
 
+def rank_metrics_counts(thr, above, equal, out=None, ranks=False):
+    """zt_rank_metrics_counts: ``rank_metrics`` from counts taken over a whole pool (TGN.count_scores / rank_of(counts=True)) --
+    ``thr`` float32 [Q] the thresholds they were taken at, ``above`` / ``equal`` int32 [Q], all CUDA.  rank = 1 + above +
+    0.5 equal in float64; a query whose threshold is NaN is skipped.  ADDS (sum of 1 / rank, Hits@1, Hits@3, Hits@10, queries
+    counted) to the float64 [5] tensor ``out`` (None: a fresh one of zeros) and returns it -- with ``ranks=True`` (out, rank [Q]
+    float64; 0 for a skipped query).  No host synchronisation."""
+    import ctypes as C
+    from ._capi import check, lib, ptr, stream_ptr
+    if not (torch.is_tensor(thr) and thr.is_cuda and thr.dtype == torch.float32 and thr.dim() == 1):
+        raise ValueError("rank_metrics_counts takes float32 CUDA thresholds [Q]")
+    Q = thr.numel()
+    for t in (above, equal):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.shape == (Q,)):
+            raise ValueError("rank_metrics_counts takes int32 CUDA counts above [Q] and equal [Q]")
+    if out is not None and not (out.is_cuda and out.dtype == torch.float64 and out.shape == (5,) and out.is_contiguous()):
+        raise ValueError("rank_metrics_counts: out is a contiguous float64 CUDA tensor [5]")
+    acc = out if out is not None else torch.zeros(5, dtype=torch.float64, device=thr.device)
+    rk = torch.zeros(Q, dtype=torch.float64, device=thr.device) if ranks else None
+    if Q == 0:
+        return (acc, rk) if ranks else acc
+    check(lib().zt_rank_metrics_counts(ptr(thr.contiguous()), ptr(above.contiguous()), ptr(equal.contiguous()), C.c_int64(Q),
+                                       ptr(rk), ptr(acc), stream_ptr()), "zt_rank_metrics_counts")
+    return (acc, rk) if ranks else acc
+
+
+@torch.no_grad()
+def eval_edge_ranking_full(model, data, n_neighbors, batch_size=200, filtered=False, finder=None, candidates=None,
+                           pool_chunk=65536):
+    """Link prediction by rank against the WHOLE pool: what ``TGN.recommend`` would have answered, measured.  Per batch, t0 is
+    the batch's first timestamp; every source ranks its true destination among all node ids but its own (``candidates``: a 1-D
+    list instead) read-only from the state BEFORE the batch -- ``TGN.rank_of(sources, t0, destinations, counts=True)``: the
+    fused count kernel, prob[B, pool] never exists --, zt_rank_metrics_counts accumulates on the device; then the state advances
+    with the ordinary eval step, whose single negative is the destination.  Returns dict(mrr, hits1, hits3, hits10) from one
+    host read at the end.  The model runs without the native pipeline.
+    THE PROTOCOL: this evaluates ``recommend`` as it answers -- everyone, sources and candidates, is embedded at t0, not at
+    each edge's own time, and no edge of the batch is known to the state.  ``batch_size=1`` is the per-edge protocol, at the
+    price of one embedding of the pool per edge.
+    ``filtered=True``: a candidate does not count where it is a partner of the source strictly before the EDGE'S OWN timestamp
+    in ``finder`` (None: ``model.neighbor_finder``; ValueError if there is none) -- embedded at t0, filtered at each edge's
+    time.  The destination itself always has its rank."""
+    if filtered and finder is None and model.neighbor_finder is None:
+        raise ValueError("eval_edge_ranking_full(filtered=True) needs a finder: the model has no neighbor_finder")
+    if int(batch_size) <= 0:
+        raise ValueError("eval_edge_ranking_full takes batch_size > 0")
+    model = model.eval()
+    if not model.test_mode:                                      # (as the eval step begins)
+        model.update_memory_in_test(model.memory)
+        model.test_mode = True
+    n = data.n_interactions
+    acc = torch.zeros(5, dtype=torch.float64, device=model.device)
+    exclude = None if not filtered else (finder if finder is not None else "seen")
+    for s in range(0, n, batch_size):
+        e = min(n, s + batch_size)
+        above, equal, prob = model.rank_of(data.sources[s:e], float(data.timestamps[s]), data.destinations[s:e],
+                                           candidates=candidates, pool_chunk=pool_chunk, exclude=exclude,
+                                           exclude_timestamps=data.timestamps[s:e], counts=True)
+        dst_d = torch.from_numpy(np.ascontiguousarray(data.destinations[s:e], np.int32)).to(model.device)
+        thr = torch.where(dst_d >= 0, prob, torch.full_like(prob, float("nan")))
+        rank_metrics_counts(thr, above, equal, out=acc)
+        model.compute_temporal_embeddings(data.sources[s:e], data.destinations[s:e], data.destinations[s:e],
+                                          data.timestamps[s:e], data.edge_idxs[s:e], n_neighbors, False)
+    a = acc.cpu().numpy()                                        # (the one host read of the pass)
+    q = a[4] if a[4] > 0 else float("nan")
+    return dict(mrr=float(a[0] / q), hits1=float(a[1] / q), hits3=float(a[2] / q), hits10=float(a[3] / q))
+
+
 @torch.no_grad()
 def eval_edge_ranking(model, negative_edge_sampler, data, n_neighbors, batch_size=200, n_negatives=100, filtered=False,
                       finder=None):

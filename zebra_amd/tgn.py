@@ -552,6 +552,188 @@ class TGN(torch.nn.Module):
             nodes = torch.where(idx >= 0, cand[idx.clamp(min=0).long()], torch.full_like(idx, -1))
         return nodes, prob
 
+    @torch.no_grad()
+    def count_scores(self, emb_q, emb_c, thr, skip=None, idx_base=0, out=None, absent=None, workspace_bytes=None):
+        """(above [Q] int32, equal [Q] int32): for every query the number of present candidates of ``rank_scores(emb_q, emb_c)``
+        whose probability is above ``thr[q]`` (float32 [Q]) and the number equal to it -- IEEE compares: a NaN threshold counts
+        nothing.  Present: ``topk_scores``' rule for a shared pool -- the probability is not NaN, nor any element of the
+        candidate's embedding; ``idx_base`` + column differs from every entry of ``skip`` (int32 [Q] or [Q, n], n <= 4, -1:
+        none); the column's bit of ``absent`` (int32 or uint32 [Q, W >= ceil(C / 32)], ``absent_bits``) is clear.
+        ``out=(above, equal)``: the counts are ADDED to what is there -- a pool given in pieces, in any order, with ``idx_base``
+        and local bits per piece, gives the numbers of one call.  Where ``rank_scores`` would call zt_affinity_rank this is
+        zt_affinity_count (csrc/rank_count.hip): prob[Q, C] is never written and the workspace does not grow with the pool
+        (``workspace_bytes``: its size, zt_affinity_count_workspace_bytes by default).  Anything else computes ``rank_scores`` a
+        chunk of queries at a time and counts under the same rule."""
+        a = self.affinity_score
+        Q, H = emb_q.shape
+        Nc = emb_c.shape[0]
+        dev = emb_q.device
+        if idx_base < 0 or idx_base + Nc > 0x7fffffff:
+            raise ValueError("count_scores: idx_base + C exceeds int32 columns")
+        if thr.dim() != 1 or thr.numel() != Q:
+            raise ValueError("count_scores: thr holds one threshold per query")
+        thr = thr.to(dev, torch.float32).contiguous()
+        if out is not None:
+            above, equal = out
+            for t in (above, equal):
+                if t.shape != (Q,) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+                    raise ValueError("count_scores: out is (above [Q] int32, equal [Q] int32), contiguous, on the embeddings' device")
+        if skip is not None:
+            skip = skip.to(dev, torch.int32)
+            if skip.dim() == 1:
+                skip = skip.unsqueeze(1)
+            if skip.dim() != 2 or skip.shape[0] != Q or skip.shape[1] > _capi.COUNT_MAX_SKIP:
+                raise ValueError("count_scores: skip is [Q] or [Q, n] with n <= %d" % _capi.COUNT_MAX_SKIP)
+            skip = None if skip.shape[1] == 0 else skip.contiguous()
+        if absent is not None:
+            if absent.dtype != torch.int32:
+                if absent.dtype != getattr(torch, "uint32", None):
+                    raise ValueError("count_scores: absent is int32 or uint32 [Q, W]")
+                absent = absent.view(torch.int32)
+            if absent.dim() != 2 or absent.shape[0] != Q or absent.shape[1] < (Nc + 31) // 32:
+                raise ValueError("count_scores: absent is [Q, W] with W >= ceil(C / 32)")
+            absent = absent.to(dev).contiguous()
+        if out is None:
+            above = torch.zeros(Q, dtype=torch.int32, device=dev)
+            equal = torch.zeros(Q, dtype=torch.int32, device=dev)
+        hip = (emb_q.is_cuda and emb_c.is_cuda and emb_q.dtype == torch.float32 and emb_c.dtype == torch.float32
+               and H % 4 == 0 and _capi.RANK_MIN_H <= H <= _capi.RANK_MAX_H)
+        if Q == 0 or Nc == 0:
+            return above, equal
+        if not hip:
+            col = torch.arange(Nc, device=dev, dtype=torch.int64) + int(idx_base)
+            nan_row = torch.isnan(emb_c).any(dim=1)              # (the kernels' relu drops a NaN: such a row is a NaN candidate)
+            step = max(1, (1 << 24) // max(1, Nc))
+            for s in range(0, Q, step):
+                p = self.rank_scores(emb_q[s:s + step], emb_c).to(torch.float32)
+                live = ~torch.isnan(p) & ~nan_row.unsqueeze(0)
+                if skip is not None:
+                    for j in range(skip.shape[1]):
+                        live &= col.unsqueeze(0) != skip[s:s + step, j].to(torch.int64).unsqueeze(1)
+                if absent is not None:
+                    live &= ~absent_columns(absent[s:s + step], Nc)
+                t = thr[s:s + step].unsqueeze(1)
+                above[s:s + step] += (live & (p > t)).sum(dim=1).to(torch.int32)
+                equal[s:s + step] += (live & (p == t)).sum(dim=1).to(torch.int32)
+            return above, equal
+        need = int(lib().zt_affinity_count_workspace_bytes(C.c_int64(Q), C.c_int64(Nc), C.c_int32(H)))
+        if workspace_bytes is not None:
+            need = int(workspace_bytes)
+        ws = getattr(self, "_count_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._count_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        w = _capi.AffinityWeights()
+        w.fc1_w, w.fc1_b, w.fc2_w, w.fc2_b = (a.fc1.weight.data_ptr(), a.fc1.bias.data_ptr(), a.fc2.weight.data_ptr(),
+                                              a.fc2.bias.data_ptr())
+        n_skip = 0 if skip is None else skip.shape[1]
+        if out is None:                                              # (a fresh call: the library zeroes what it adds to)
+            above = torch.empty(Q, dtype=torch.int32, device=self.device)
+            equal = torch.empty(Q, dtype=torch.int32, device=self.device)
+        check(lib().zt_affinity_count(ptr(emb_q.contiguous()), C.c_int64(Q), ptr(emb_c.contiguous()), C.c_int64(Nc), C.c_int32(H),
+                                      C.byref(w), ptr(thr), ptr(skip), C.c_int32(n_skip), C.c_int64(int(idx_base)),
+                                      C.c_int32(0 if out is None else 1), ptr(above), ptr(equal), ptr(ws), C.c_int64(need),
+                                      ptr(absent),
+                                      C.c_int64(0 if absent is None else absent.shape[1]), stream_ptr()), "zt_affinity_count")
+        return above, equal
+
+    @staticmethod
+    def _pack_absent(gone):
+        """int32 [Q, ceil(C / 32)] absent bits of a bool [Q, C] (bit c & 31 of word c >> 5: ``absent_columns``' inverse)"""
+        Q, C_ = gone.shape
+        W = (C_ + 31) // 32
+        padded = torch.zeros((Q, W * 32), dtype=torch.int64, device=gone.device)
+        padded[:, :C_] = gone
+        words = (padded.view(Q, W, 32) << torch.arange(32, dtype=torch.int64, device=gone.device)).sum(dim=2)
+        return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+    @torch.no_grad()
+    def rank_of(self, sources, timestamps, targets, candidates=None, exclude_self=True, pool_chunk=65536, exclude=None,
+                exclude_timestamps=None, counts=False):
+        """(rank [Q] float64, prob [Q] float32): where ``targets[q]`` stands among the candidates ``recommend`` would rank for
+        ``sources[q]`` at ``timestamps[q]`` -- rank = 1 + (present candidates with a larger probability) + 0.5 (present
+        candidates with an equal one), the mean of the optimistic and the pessimistic rank; ``prob`` is the target's own
+        probability, ``rank_scores`` of (source, target) both embedded at the query time.  ``counts=True`` returns (above
+        [Q] int32, equal [Q] int32, prob) instead.  The target is never counted against itself; a target < 0 gives rank 0
+        (counts 0, probability 0).  Read-only; raises where ``embed_nodes`` raises.
+        ``candidates=None`` (every node id 1 .. n_nodes - 1, without the source's own id under ``exclude_self``) or a 1-D list
+        (-1: absent; duplicates allowed): ``recommend``'s shared-pool walk -- the pool is embedded ``pool_chunk`` rows at a time
+        and every chunk goes through ``count_scores`` with accumulate, so prob[Q, pool] never exists and memory does not depend
+        on the pool; ``timestamps`` is then a scalar or all equal (``recommend``'s ValueError otherwise).  ``candidates``
+        [Q, C] (-1: absent) takes per-query times: ``rank_candidates`` on [target | C], then ``evaluation.rank_metrics``.
+        ``exclude``: as ``recommend`` takes it -- "seen", a NeighborFinder or (ptr [Q + 1], ids) -- with the "seen" lists cut at
+        ``exclude_timestamps`` [Q] (default: the query times).  An excluded id that is the target still is the target: it has
+        its rank among the others."""
+        src_d = self._as_device(sources, torch.int32).reshape(-1)
+        Q = src_d.numel()
+        ts_d = self._as_device(timestamps, torch.float64).reshape(-1)
+        if ts_d.numel() == 1 and Q != 1:
+            ts_d = ts_d.expand(Q).contiguous()
+        tgt_d = self._as_device(targets, torch.int32).reshape(-1)
+        if ts_d.numel() != Q or tgt_d.numel() != Q or int(pool_chunk) <= 0:
+            raise ValueError("rank_of takes sources [Q], timestamps [Q] or a scalar, targets [Q] and pool_chunk > 0")
+        ets_d = ts_d
+        if exclude_timestamps is not None:
+            ets_d = self._as_device(exclude_timestamps, torch.float64).reshape(-1)
+            if ets_d.numel() != Q:
+                raise ValueError("rank_of takes exclude_timestamps [Q]")
+        cand = None if candidates is None else self._as_device(candidates, torch.int32)
+        if cand is not None and (cand.dim() not in (1, 2) or (cand.dim() == 2 and cand.shape[0] != Q)):
+            raise ValueError("rank_of takes candidates [Q, C] or [C]")
+        self.embed_nodes(src_d[:0], ts_d[:0])                        # (refuses where embed_nodes does, before any device work)
+        lists = None if exclude is None else self._exclude_lists(src_d, ets_d, exclude)
+        has = tgt_d >= 0
+        if cand is not None and cand.dim() == 2:
+            from .evaluation import rank_metrics
+            gone = (cand == tgt_d.unsqueeze(1)) | (cand < 0)
+            if lists is not None:
+                gone |= absent_columns(self._mark_absent(lists, Q, candidates=cand.contiguous()), cand.shape[1])
+            table = torch.cat([tgt_d.unsqueeze(1), torch.where(gone, torch.full_like(cand, -1), cand)], dim=1).contiguous()
+            p = self.rank_candidates(src_d, ts_d, table).float()
+            prob = p[:, 0].contiguous()
+            if counts:
+                live = (table[:, 1:] >= 0) & has.unsqueeze(1)
+                above = (live & (p[:, 1:] > p[:, :1])).sum(dim=1).to(torch.int32)
+                equal = (live & (p[:, 1:] == p[:, :1])).sum(dim=1).to(torch.int32)
+                return above, equal, prob
+            return rank_metrics(p, table, ranks=True)[1].to(torch.float64), prob
+        if Q > 0 and bool((ts_d != ts_d[0]).any()):
+            raise ValueError("recommend: a shared pool needs one query time (a scalar, or all timestamps equal): a candidate's "
+                             "embedding depends on it; give candidates [Q, C] for per-query times")
+        emb_q = self.embed_nodes(src_d, ts_d)
+        # the thresholds: rank_scores of (source, target), the target embedded at the query time, through cand_idx [Q, 1]
+        prob = torch.zeros(Q, dtype=torch.float32, device=self.device)
+        if bool(has.any()):
+            uniq, inv = torch.unique(tgt_d[has], return_inverse=True)
+            emb_t = self.embed_nodes(uniq, ts_d[:1].expand(uniq.numel()).contiguous())
+            tix = torch.full((Q, 1), -1, dtype=torch.int32, device=self.device)
+            tix[has, 0] = inv.to(torch.int32)
+            prob = self.rank_scores(emb_q, emb_t, tix).float()[:, 0].contiguous()
+        thr = torch.where(has, prob, torch.full_like(prob, float("nan")))
+        above = torch.zeros(Q, dtype=torch.int32, device=self.device)
+        equal = torch.zeros(Q, dtype=torch.int32, device=self.device)
+        n_pool = self.n_nodes - 1 if cand is None else cand.numel()
+        skip = None
+        if cand is None:                                             # node id v is column v - 1 of the pool 1 .. n - 1
+            skip = torch.stack([torch.where(has, tgt_d - 1, torch.full_like(tgt_d, -1)),
+                                (src_d - 1) if exclude_self else torch.full_like(src_d, -1)], dim=1).contiguous()
+        for s in range(0, max(n_pool, 0) if Q > 0 else 0, int(pool_chunk)):
+            e = min(n_pool, s + int(pool_chunk))
+            ids = torch.arange(s + 1, e + 1, dtype=torch.int32, device=self.device) if cand is None else cand[s:e]
+            emb_c = self.embed_nodes(ids.clamp(min=0), ts_d[:1].expand(e - s).contiguous())
+            absent = None
+            if cand is not None:                                     # the target's columns and the list's -1 entries: bits
+                absent = self._pack_absent((ids.unsqueeze(0) == tgt_d.unsqueeze(1)) | (ids < 0).unsqueeze(0))
+            if lists is not None:
+                bits = (self._mark_absent(lists, Q, id_lo=s + 1, n_cols=e - s) if cand is None
+                        else self._mark_absent(lists, Q, candidates=ids.contiguous()))
+                absent = bits if absent is None else absent | bits
+            self.count_scores(emb_q, emb_c, thr, skip=skip, idx_base=s, out=(above, equal), absent=absent)
+        if counts:
+            return above, equal, prob
+        rank = torch.where(has & ~torch.isnan(prob), 1.0 + above.to(torch.float64) + 0.5 * equal.to(torch.float64),
+                           torch.zeros(Q, dtype=torch.float64, device=self.device))
+        return rank, prob
+
     def _score_pairs(self, s, dd, n):
         """The scorer as torch composes it (tgn_model.py:185-188): (pos [B, 1], neg [B, 1]) under autograd."""
         n_samples = s.shape[0]
