@@ -67,7 +67,8 @@ int zt_stream_destroy(void *stream);
  * oracle, on the same inputs.  A pinned kernel that cannot take a shape falls back to the library's pick.  Not a
  * tuning interface: every kernel of a selector computes the same function. */
 #define ZT_CHOICE_AGGREGATE 0   /* neighbour aggregation (zt_embed): ZT_AGG_GENERIC */
-#define ZT_CHOICE_EMBED_OUT 1   /* output layers (zt_embed): ZT_OUT_TILED, ZT_OUT_LATENCY, ZT_OUT_PERSIST */
+#define ZT_CHOICE_EMBED_OUT 1   /* output layers (zt_embed): ZT_OUT_TILED, ZT_OUT_LATENCY, ZT_OUT_PERSIST; zt_pipeline_*: also
+                                 * ZT_OUT_NBR_GRU, ZT_OUT_WHOLE */
 #define ZT_CHOICE_GRU 2         /* zt_gru_update: ZT_GRU_TILE, ZT_GRU_SPLIT */
 #define ZT_CHOICE_MESSAGES 3    /* zt_store_messages: ZT_MSG_ONE, ZT_MSG_TWO (batch positions per wavefront) */
 #define ZT_CHOICE_TPPR_CHAIN 4  /* hub chains of zt_tppr_stream: ZT_CHAIN_SINGLE (one position per critical section: the
@@ -90,6 +91,11 @@ int zt_stream_destroy(void *stream);
 #define ZT_OUT_TILED 1
 #define ZT_OUT_LATENCY 2
 #define ZT_OUT_PERSIST 3
+#define ZT_OUT_NBR_GRU 4   /* the persistent form, and in the pipeline its neighbour paths run in the GRU update's grid (k_nbr_gru)
+                            * behind a source-only launch, at any batch size: what the library picks by itself from 8 192 rows
+                            * on.  (ZT_OUT_PERSIST: the persistent form whole, k_embed_out3, in the pipeline too) */
+#define ZT_OUT_WHOLE 5     /* the library's pick by shape, but the output layers are never divided between two launches: the
+                            * persistent form runs whole (k_embed_out3) in front of the GRU update */
 #define ZT_GRU_TILE 1
 #define ZT_GRU_SPLIT 2
 #define ZT_CHAIN_SINGLE 1

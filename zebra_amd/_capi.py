@@ -56,6 +56,7 @@ PREPASS_LAUNCHES, PREPASS_COOP = 1, 2                          # PREPASS_COOP: r
 CHAIN_SINGLE, CHAIN_PAIRED, CHAIN_SPINE, CHAIN_DUO = 1, 2, 3, 4   # PAIRED / SPINE / DUO: removed; see DESIGN.md section 5
 AGG_GENERIC = 1
 OUT_TILED, OUT_LATENCY, OUT_PERSIST = 1, 2, 3
+OUT_NBR_GRU, OUT_WHOLE = 4, 5                                   # the pipeline: k_nbr_gru at any batch size / never
 GRU_TILE, GRU_SPLIT = 1, 2
 CELL_GRU, CELL_RNN = 0, 1                                       # zt_pipeline_set_cell
 METRICS_FORM_REFUSED, METRICS_FORM_SINGLE, METRICS_FORM_SPLIT = 0, 1, 2   # zt_link_metrics_plan

@@ -811,208 +811,30 @@ __global__ __launch_bounds__(AGG_THREADS, 1) void k_fc1_agg_reg(
 
 
 // ---------------------------------------------------------------------------
-// k_embed_out3 (round 5): the same three layers, PERSISTENT, for batches beyond k_embed_out2's reach.  k_embed_out's time
-// at 3 000-12 000 rows was rounds of dependent weight-fragment fetches from L2 per 32-row workgroup (35-40 us for 1 GFLOP
-// at C5's batch).  Here the weights live in LDS for the launch, in the order the MFMAs consume them (fragment (N-tile b,
-// k-chunk c) = 64 lanes x 4 floats, one conflict-free ds_read_b128 per four MFMAs), one workgroup per CU of the stream,
-// and every WAVE strides over (16 rows x ALL seven N-tiles) units by itself: the A operand comes straight from memory
-// into the MFMA lanes (float4 at columns 16 c + 4 g, as in k_embed_out2), the next unit's rows are requested before the
-// current unit's MFMAs, a row is read once.  Workgroups [0, n_src) take the source path (fc1s and fc2s resident: 98 KB, the
-// hidden rows through 7 KB of the wave's own LDS), the others fc2 of the M models (49 KB).  Same accumulation order as
-// the other two kernels (k-chunks first to last), so the three agree to the bit.  D = 100 (Dp = 112).
+// k_embed_out3: the persistent output layers (embed_out_body.hpp: eo3_src_body, eo3_nbr_body) in one grid -- workgroups
+// [0, n_src) take the source path, the others fc2 of the M models.  k_embed_src3 / k_embed_nbr3: one path each, for a caller
+// that holds the neighbour paths back for the GRU update's launch (embed_ex: `defer`; k_nbr_gru, memory_update.hip) -- the
+// neighbour-only launch is what such a caller falls back to where no GRU kernel takes them along.
 // ---------------------------------------------------------------------------
-constexpr int EO3_NT = 7, EO3_KC = 7, EO3_DP = 112, EO3_LDY = 116;
-constexpr int EO3_FRAG = EO3_NT * EO3_KC * 256;      // floats of one weight matrix in fragment order
-
-__device__ __forceinline__ void eo3_fill(float *Wl, const float *__restrict__ Wp, int tid)
-{
-    constexpr int PER = (EO3_NT * EO3_KC * 64 + 255) / 256;             // fragments-lanes per thread: all in flight, then stored
-    f32x4 v[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int idx = tid + q * 256, frag = idx >> 6, ln = idx & 63;
-        const int b = frag / EO3_KC, c = frag - b * EO3_KC;
-        v[q] = idx < EO3_NT * EO3_KC * 64
-                   ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)(16 * b + (ln & 15)) * EO3_DP + 16 * c + 4 * (ln >> 4))
-                   : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int idx = tid + q * 256;
-        if (idx < EO3_NT * EO3_KC * 64) reinterpret_cast<f32x4 *>(Wl)[idx] = v[q];
-    }
-}
-
 template <int HG>
-__global__ __launch_bounds__(AGG_THREADS, 1) void k_embed_out3(
-    const float *__restrict__ memory, long long num_nodes, const int *__restrict__ nodes, long long N, int D, int M,
-    const float *__restrict__ H, const float *__restrict__ S, const float *__restrict__ fc2_p,
-    const float *__restrict__ fc2_b, const float *__restrict__ fc1s_p, const float *__restrict__ fc1s_b,
-    const float *__restrict__ fc2s_p, const float *__restrict__ fc2s_b, float *__restrict__ out, int *status, int n_src)
+__global__ __launch_bounds__(AGG_THREADS, 1) void k_embed_out3(EmbedOutArgs E, int n_src)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *W0 = reinterpret_cast<float *>(smem);                         // fc2 (neighbour role) / fc1s (source role)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g4 = lane >> 4;
-    const int OW = D * (M + 1);
-    const long long tiles = (N + 15) / 16;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    bool cin[EO3_KC];                                                    // this lane's float4 of chunk c lies inside the row
-#pragma unroll
-    for (int c = 0; c < EO3_KC; ++c) cin[c] = 16 * c + 4 * g4 < D;
-    const f32x4 *Wf0 = reinterpret_cast<const f32x4 *>(W0) + lane;
+    if ((int)blockIdx.x < n_src) eo3_src_body(E, smem, blockIdx.x, n_src);
+    else eo3_nbr_body<HG, AGG_WAVES, EO3_NT>(E, smem, (int)blockIdx.x - n_src, (int)gridDim.x - n_src);
+}
 
-    if ((int)blockIdx.x < n_src) {
-        // ---------------- source path: memory[nodes] -> fc1s -> relu -> fc2s ----------------
-        float *W1 = W0 + EO3_FRAG;                                       // fc2s
-        float *Y = W1 + EO3_FRAG + wave * 16 * EO3_LDY;                  // this wave's hidden rows
-        eo3_fill(W0, fc1s_p, tid);
-        eo3_fill(W1, fc2s_p, tid);
-        float b1v[EO3_NT], b2v[EO3_NT];
-#pragma unroll
-        for (int b = 0; b < EO3_NT; ++b) {
-            b1v[b] = 16 * b + r16 < D ? fc1s_b[16 * b + r16] : 0.f;
-            b2v[b] = 16 * b + r16 < D ? fc2s_b[16 * b + r16] : 0.f;
-        }
-        const f32x4 *Wf1 = reinterpret_cast<const f32x4 *>(W1) + lane;
-        const long long stride = (long long)n_src * AGG_WAVES;
-        long long t = (long long)blockIdx.x * AGG_WAVES + wave;
-        // ids two units ahead, rows one unit ahead
-        auto node_of = [&](long long tt) -> int { return (tt < tiles && tt * 16 + r16 < N) ? nodes[tt * 16 + r16] : -1; };
-        auto rows_of = [&](int nd, f32x4 (&a)[EO3_KC]) {
-            const bool ok = nd >= 0 && nd < num_nodes;
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c)
-                a[c] = (ok && cin[c]) ? *reinterpret_cast<const f32x4 *>(memory + (size_t)nd * D + 16 * c + 4 * g4) : zero4;
-        };
-        int nd_cur = node_of(t), nd_nxt = node_of(t + stride);
-        f32x4 a[EO3_KC], an[EO3_KC];
-        if (t < tiles) rows_of(nd_cur, a);
-        __syncthreads();                                                 // both weight images are in LDS
-        for (; t < tiles; t += stride) {
-            const long long r0 = t * 16;
-            if (r0 + r16 < N && (nd_cur < 0 || nd_cur >= num_nodes)) atomicExch(status, ZT_ERR_RANGE);
-            rows_of(nd_nxt, an);                                         // the next unit's rows, under this unit's MFMAs
-            nd_cur = nd_nxt;
-            nd_nxt = node_of(t + 2 * stride);
-            f32x4 acc1[EO3_NT];
-#pragma unroll
-            for (int b = 0; b < EO3_NT; ++b) acc1[b] = zero4;
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c) {
-                f32x4 w[EO3_NT];
-#pragma unroll
-                for (int b = 0; b < EO3_NT; ++b) w[b] = Wf0[(b * EO3_KC + c) * 64];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)                                  // consecutive MFMAs on different accumulators
-#pragma unroll
-                    for (int b = 0; b < EO3_NT; ++b) acc1[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], w[b][j], acc1[b], 0, 0, 0);
-            }
-#pragma unroll
-            for (int b = 0; b < EO3_NT; ++b)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = acc1[b][j] + b1v[b];
-                    Y[(4 * g4 + j) * EO3_LDY + 16 * b + r16] = (16 * b + r16 < D && v > 0.f) ? v : 0.f;
-                }
-            wave_sync();
-            f32x4 acc[EO3_NT];
-#pragma unroll
-            for (int b = 0; b < EO3_NT; ++b) acc[b] = zero4;
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c) {
-                const f32x4 y = *reinterpret_cast<const f32x4 *>(Y + r16 * EO3_LDY + 16 * c + 4 * g4);
-                f32x4 w[EO3_NT];
-#pragma unroll
-                for (int b = 0; b < EO3_NT; ++b) w[b] = Wf1[(b * EO3_KC + c) * 64];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int b = 0; b < EO3_NT; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(y[j], w[b][j], acc[b], 0, 0, 0);
-            }
-#pragma unroll
-            for (int b = 0; b < EO3_NT; ++b) {
-                const int col = 16 * b + r16;
-                if (col < D) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (r0 + 4 * g4 + j < N) out[(size_t)(r0 + 4 * g4 + j) * OW + col] = acc[b][j] + b2v[b];
-                }
-            }
-            wave_sync();                                                 // Y is free for the next unit
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c) a[c] = an[c];
-        }
-        return;
-    }
-    // ---------------- neighbour paths: fc2 on the reduced rows of model m ----------------
-    eo3_fill(W0, fc2_p, tid);
-    float b2v[EO3_NT];
-#pragma unroll
-    for (int b = 0; b < EO3_NT; ++b) b2v[b] = 16 * b + r16 < D ? fc2_b[16 * b + r16] : 0.f;
-    const long long units = tiles * M;
-    const long long stride = (long long)((int)gridDim.x - n_src) * AGG_WAVES;
-    long long u = (long long)((int)blockIdx.x - n_src) * AGG_WAVES + wave;
-    // a unit's A operand: a query row's HG partial-sum groups (k_fc1_agg_wide), added first to last.  HG = 1: the next
-    // unit's rows are requested under this unit's MFMAs; HG > 1 (F = 172: at most a few units per wave at those batch
-    // sizes): groups [q0, q0 + GQ) at a time, at the top of the unit
-    constexpr int GQ = HG == 1 ? 1 : 5;
-    auto rows_of = [&](long long uu, int q0, f32x4 (&g)[GQ][EO3_KC]) {
-        const long long m = uu / tiles, r = (uu - m * tiles) * 16 + r16;
-        const bool rin = uu < units && r < N;
-        const float *hp = H + (((size_t)m * N + (rin ? r : 0)) * HG + q0) * D + 4 * g4;
-#pragma unroll
-        for (int q = 0; q < GQ; ++q)
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c) g[q][c] = (rin && cin[c]) ? *reinterpret_cast<const f32x4 *>(hp + (size_t)q * D + 16 * c) : zero4;
-    };
-    f32x4 gn[GQ][EO3_KC];
-    if (HG == 1) rows_of(u, 0, gn);
-    __syncthreads();                                                     // the weight image is in LDS
-    for (; u < units; u += stride) {
-        const long long m = u / tiles, r0 = (u - m * tiles) * 16;
-        f32x4 a[EO3_KC];
-        if (HG == 1) {
-#pragma unroll
-            for (int c = 0; c < EO3_KC; ++c) a[c] = gn[0][c];
-        } else {
-#pragma nounroll
-            for (int q0 = 0; q0 < HG; q0 += GQ) {
-                rows_of(u, q0, gn);
-#pragma unroll
-                for (int c = 0; c < EO3_KC; ++c) {
-                    if (q0 == 0) a[c] = gn[0][c]; else a[c] += gn[0][c];
-#pragma unroll
-                    for (int q = 1; q < GQ; ++q) a[c] += gn[q][c];
-                }
-            }
-        }
-        float sv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sv[j] = r0 + 4 * g4 + j < N ? S[(size_t)m * N + r0 + 4 * g4 + j] : 0.f;
-        if (HG == 1) rows_of(u + stride, 0, gn);                         // the next unit's rows, under this unit's MFMAs
-        f32x4 acc[EO3_NT];
-#pragma unroll
-        for (int b = 0; b < EO3_NT; ++b) acc[b] = zero4;
-#pragma unroll
-        for (int c = 0; c < EO3_KC; ++c) {
-            f32x4 w[EO3_NT];
-#pragma unroll
-            for (int b = 0; b < EO3_NT; ++b) w[b] = Wf0[(b * EO3_KC + c) * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int b = 0; b < EO3_NT; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], w[b][j], acc[b], 0, 0, 0);
-        }
-#pragma unroll
-        for (int b = 0; b < EO3_NT; ++b) {
-            const int col = 16 * b + r16;
-            if (col < D) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (r0 + 4 * g4 + j < N) out[(size_t)(r0 + 4 * g4 + j) * OW + (size_t)D * (m + 1) + col] = acc[b][j] + b2v[b] * sv[j];
-            }
-        }
-    }
+__global__ __launch_bounds__(AGG_THREADS, 1) void k_embed_src3(EmbedOutArgs E)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    eo3_src_body(E, smem, blockIdx.x, gridDim.x);
+}
+
+// (plain rows only: the neighbour paths are never held back where H holds partial-sum groups, KernelPlan::nbr_later)
+__global__ __launch_bounds__(AGG_THREADS, 1) void k_embed_nbr3(EmbedOutArgs E)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    eo3_nbr_body<1, AGG_WAVES, EO3_NT>(E, smem, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1135,7 +957,7 @@ bool make_plan(int64_t N, int D, int F, int T, int M, int k, EmbedPlan &p)
 KernelPlan plan_kernels(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
                         int out_choice, EmbedPlan &p)
 {
-    KernelPlan kp{AggKernel::unsupported, OutForm::tiled, Refusal::shape, 0, 0, 0, 0, 1};
+    KernelPlan kp{AggKernel::unsupported, OutForm::tiled, Refusal::shape, 0, 0, 0, 0, 1, false};
     static_assert(16 * NTW * AGG_WAVES == 128 && 16 * NTW_WIDE * AGG_WAVES == MAX_D, "the N-tiles cover D <= 128 / D <= 256");
     if (!make_plan(N, D, F, T, M, k, p)) return kp;
     const bool big = k > MAX_MT * 16;
@@ -1174,10 +996,17 @@ KernelPlan plan_kernels(int64_t N, int D, int F, int T, int M, int k, bool have_
     //  In the pipeline the persistent workgroups (130 KB of LDS, a whole register file per wave) do not fit beside another
     //  stream's kernels: C4 (3 000 rows, no CU masks, k_pruned_topk running beside) 36 us against the tiled kernel's 20; C5
     //  (12 288 rows, the main stream's CUs to itself) 29 against 38.  So: from 8 192 rows on.
-    if (D % 4 == 0 && (p.Dp == 112 || p.Dp == 128) && (out_choice == ZT_OUT_LATENCY || (out_choice == 0 && N <= 1024)))
+    // (ZT_OUT_WHOLE: the library's pick; ZT_OUT_NBR_GRU: the persistent form wherever it exists)
+    const bool by_shape = out_choice == 0 || out_choice == ZT_OUT_WHOLE;
+    if (D % 4 == 0 && (p.Dp == 112 || p.Dp == 128) && (out_choice == ZT_OUT_LATENCY || (by_shape && N <= 1024)))
         kp.out = OutForm::latency;
-    else if (D % 4 == 0 && p.Dp == EO3_DP && (out_choice == ZT_OUT_PERSIST || (out_choice == 0 && N >= 8192)))
+    else if (D % 4 == 0 && p.Dp == EO3_DP && (out_choice == ZT_OUT_PERSIST || out_choice == ZT_OUT_NBR_GRU || (by_shape && N >= 8192)))
         kp.out = OutForm::persist;
+    // The persistent form's two halves share nothing, and only the source path reads the memory table: where the caller can
+    // hold output layers back (the pipeline), the neighbour paths leave the chain aggregation -> output layers -> GRU update
+    // and run in the GRU update's grid (k_nbr_gru, memory_update.hip).  Plain rows only (no partial-sum groups); a pinned
+    // ZT_OUT_PERSIST stays what it was, k_embed_out3 whole.
+    kp.nbr_later = kp.out == OutForm::persist && kp.hg == 1 && (out_choice == 0 || out_choice == ZT_OUT_NBR_GRU);
     return kp;
 }
 
@@ -1405,12 +1234,26 @@ static int embed_impl(const float *memory_dev, const float *efeat_dev, int64_t n
                          reinterpret_cast<const float *>(ws + p.off_fc1st), wt->fc1s_b,
                          reinterpret_cast<const float *>(ws + p.off_fc2st), wt->fc2s_b, out_dev, status_dev};
     const long long tiles = (N + 15) / 16;
-    const zt::embed_out_deferred od{true, E, kp.hg, kp.out, kp.out == OutForm::latency ? (int)(tiles < 256 ? tiles : 256) : 0, nullptr};
-    if (defer != nullptr && kp.out != OutForm::persist) {
+    zt::embed_out_deferred od{true, E, kp.hg, kp.out, kp.out == OutForm::latency ? (int)(tiles < 256 ? tiles : 256) : 0, nullptr};
+    if (defer != nullptr && kp.out == OutForm::persist && kp.nbr_later) {
+        // the source path by itself, here: it reads the memory rows the GRU update rewrites, and nothing of the aggregation's.
+        // One persistent workgroup per compute unit of the stream, as many as there are four-wave loads of 16-row tiles.
+        long long wgs = zt::stream_cu_count(s);
+        if (defer->max_wgs > 0 && wgs > defer->max_wgs) wgs = defer->max_wgs;
+        if (wgs > (tiles + AGG_WAVES - 1) / AGG_WAVES) wgs = (tiles + AGG_WAVES - 1) / AGG_WAVES;
+        ZT_PROF_BEGIN(s, P_EMBED_OUT);
+        ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_src3), EO3_SRC_LDS));
+        k_embed_src3<<<(unsigned)wgs, AGG_THREADS, EO3_SRC_LDS, s>>>(E);
+        ZT_PROF_END(s, P_EMBED_OUT);
+        od.form = OutForm::persist_nbr;          // what is left: handed on below
+    }
+    if (defer != nullptr && od.form != OutForm::persist) {
         // held back: the caller launches them beside the GRU update (gru_update_ex) -- or by embed_out_launch
         int *latch = defer->latch;
+        const int max_wgs = defer->max_wgs;
         *defer = od;
         defer->latch = latch;
+        defer->max_wgs = max_wgs;
         ZT_LAUNCH_CHECK();
         return ZT_OK;
     }
@@ -1454,12 +1297,21 @@ int zt::embed_out_launch(const zt::embed_out_deferred &d, void *stream)
         int n_src = (int)((2 * wgs + (E.M + 2) / 2) / (E.M + 2));
         if (n_src < 1) n_src = 1;
         if (n_src > wgs - 1) n_src = (int)wgs - 1;
-        const size_t lds3 = (size_t)(2 * EO3_FRAG + AGG_WAVES * 16 * EO3_LDY) * 4;
         rc = dispatch<1, 5, 10>(d.hg, [&](auto HGV) {
-            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_out3<HGV>), lds3));
-            k_embed_out3<HGV><<<(unsigned)wgs, AGG_THREADS, lds3, s>>>(E.memory, E.num_nodes, E.nodes, E.N, E.D, E.M, E.H, E.S, E.fc2_p,
-                                                                      E.fc2_b, E.fc1s_p, E.fc1s_b, E.fc2s_p, E.fc2s_b, E.out, E.status,
-                                                                      n_src);
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_out3<HGV>), EO3_SRC_LDS));
+            k_embed_out3<HGV><<<(unsigned)wgs, AGG_THREADS, EO3_SRC_LDS, s>>>(E, n_src);
+            return ZT_OK;
+        });
+    } else if (d.form == OutForm::persist_nbr) {
+        // the neighbour paths alone (their source path ran in embed_ex; no GRU kernel took them along): (16 rows, model) units
+        // over the waves of at most one workgroup per CU
+        const long long units = (E.N + 15) / 16 * E.M;
+        long long wgs = zt::stream_cu_count(s);
+        if (d.max_wgs > 0 && wgs > d.max_wgs) wgs = d.max_wgs;
+        if (wgs > (units + AGG_WAVES - 1) / AGG_WAVES) wgs = (units + AGG_WAVES - 1) / AGG_WAVES;
+        rc = dispatch<1>(d.hg, [&](auto) {
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_embed_nbr3), EO3_NBR_LDS));
+            k_embed_nbr3<<<(unsigned)wgs, AGG_THREADS, EO3_NBR_LDS, s>>>(E);
             return ZT_OK;
         });
     } else {

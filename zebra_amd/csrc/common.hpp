@@ -81,8 +81,10 @@ struct EmbedOutArgs {
 // (80 < k); reg = k_fc1_agg_reg, wide = k_fc1_agg_wide (aggregate_wide.hip), d100 = k_fc1_agg_d100, split = k_fc1_agg_split
 // (aggregate_split.hip).  Every kernel of a family gives the same bits; the choice is speed only (tests/test_launch_plan_cpu.py).
 enum class AggKernel { unsupported, reg, wide, d100, tiled_table, tiled_full, tiled_table_big, tiled_full_big, split };
-// the output layers: k_embed_out (tiled), k_embed_out2 (latency: small batches), k_embed_out3 (persist: large ones)
-enum class OutForm { tiled, latency, persist };
+// the output layers: k_embed_out (tiled), k_embed_out2 (latency: small batches), k_embed_out3 (persist: large ones);
+// persist_nbr: the neighbour paths of the persistent form alone -- what embed_ex holds back after it has launched the source
+// path by itself (KernelPlan::nbr_later); never a plan's own answer
+enum class OutForm { tiled, latency, persist, persist_nbr };
 // why a shape is refused: no kernel or workspace for it / no tile holds a query row and no chunk of one fits (zt_embed: it needs
 // the projected table) / partial-sum groups the output layers have no instantiation for
 enum class Refusal { none, shape, no_split, groups };
@@ -93,6 +95,11 @@ struct KernelPlan {
     size_t lds;            // dynamic LDS of the tiled and d100 launches (the other launchers size their own)
     int rq, mt, lda;       // their tile: query rows, 16-row M-tiles, leading dimension
     int hg;                // partial-sum groups per query row in H (k_fc1_agg_wide: k / 4; else 1)
+    // out == persist, for a caller that can hold output layers back (embed_ex: `defer`): the source path is launched by itself
+    // and the neighbour paths are handed on as OutForm::persist_nbr, for the GRU update's launch (k_nbr_gru).  A direct
+    // zt_embed runs k_embed_out3 whole either way.  ZT_OUT_NBR_GRU asks for it at any batch size; ZT_OUT_WHOLE (the pick by
+    // shape) and ZT_OUT_PERSIST forbid it.
+    bool nbr_later;
 };
 // Pure host code (no HIP calls).  training: zt_agg_train_forward's choice (no table; tiled_full or split)
 KernelPlan embed_kernel_plan(int64_t N, int D, int F, int T, int M, int k, bool have_table, bool training, int agg_choice,
@@ -100,10 +107,16 @@ KernelPlan embed_kernel_plan(int64_t N, int D, int F, int T, int M, int k, bool 
 // The memory update's kernels for one shape (memory_update.hip: memory_kernel_plan): the message build (k_build_messages, or
 // k_build_messages2: two batch positions per wave); the GRU / RNN update (none: no rows; tile = k_gru, split = k_gru_split);
 // output layers held back by embed_ex (launched in front of the GRU kernel -- or on the way out of a refused or empty update
-// --, fused with k_gru: k_out_gru, or with k_gru_split: k_out_gru2).  Every form gives the same bits; the choice is speed only.
+// --, fused with k_gru: k_out_gru, or with k_gru_split: k_out_gru2; fused_nbr: the neighbour paths of the persistent form behind
+// k_gru's tiles in one grid, k_nbr_gru -- no gate: they read nothing the update writes).  The choice is speed only: wherever
+// and in whichever form the output layers are launched they give the same bits, and so do the two message kernels; the two
+// GRU forms agree to rounding, not to the bit (the split's four waves divide K among them and add their partial gate sums
+// afterwards; tests/test_embed_gpu.py holds the two to 2e-6).  Held-back neighbour paths draw an update of <= 512 rows, the
+// split's by the library's pick, to the tile: that happens under ZT_OUT_NBR_GRU only (the pipeline's update has two thirds
+// as many rows as its output layers, which are divided from 8 192 rows on), and moves such an update's rows by that rounding.
 enum class MsgKernel { one, two };
 enum class GruForm { none, tile, split };
-enum class OutLaunch { none, front, fused_tile, fused_split };
+enum class OutLaunch { none, front, fused_tile, fused_split, fused_nbr };
 enum class MemRefusal { none, arg, d_large, msg_wide };      // bad argument / D > 128 / message width too large
 // the held-back output layers (embed_out_deferred) as far as the GRU launch needs them; same_memory: they read the table updated
 struct HeldOut {
@@ -121,6 +134,8 @@ struct MemoryPlan {
     size_t lds, lds2, lds_f;           // dynamic LDS of k_gru, k_gru_split and the fused kernel
     int gru_tiles, NTg;                // 16-row tiles, hidden N-tiles
     int n_src_wgs, n_nb_wgs, out_tiles;     // k_out_gru2's source- and neighbour-path workgroups; k_out_gru's row tiles
+                                            // (k_nbr_gru: n_nb_wgs = the neighbour workgroups asked for; the launch caps them at
+                                            //  one per compute unit of the stream)
     unsigned grid;                     // workgroups of the launch (k_gru_split: x dimension)
     unsigned target, participants;     // the fused kernels' SrcGate
 };
@@ -222,9 +237,12 @@ struct embed_out_deferred {
     bool valid;
     EmbedOutArgs args;
     int hg;
-    OutForm form;          // (latency: gx tiles' worth of waves per path and N-tile; persist is never held back)
+    OutForm form;          // (latency: gx tiles' worth of waves per path and N-tile; persist is never held back whole:
+                           //  persist_nbr is its neighbour half, the source half launched already)
     int gx;
     int *latch;            // host-mapped word a gate wait that gives up writes ZT_ERR_TIMEOUT to (or NULL); kept across embed_ex calls
+    int max_wgs = 0;       // the divided persistent form's launches (k_embed_src3, k_nbr_gru's neighbour half, k_embed_nbr3): at most
+                           // so many persistent workgroups each; 0 = one per compute unit of the stream.  The caller's, like latch
 };
 struct member_gate;                                                         // (below: the wait for one batch's T-PPR rows)
 int embed_out_launch(const embed_out_deferred &d, void *stream);           // aggregate.hip: the output layers as a kernel of their own

@@ -350,4 +350,248 @@ __global__ __launch_bounds__(64) void k_embed_out2(EmbedOutArgs E)
     embed_out2_body<NT, HG>(E, Y, threadIdx.x, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, nullptr);
 }
 
+// ---------------------------------------------------------------------------
+// k_embed_out3 (round 5): the same three layers, PERSISTENT, for batches beyond k_embed_out2's reach.  k_embed_out's time
+// at 3 000-12 000 rows was rounds of dependent weight-fragment fetches from L2 per 32-row workgroup (35-40 us for 1 GFLOP
+// at C5's batch).  Here the weights live in LDS for the launch, in the order the MFMAs consume them (fragment (N-tile b,
+// k-chunk c) = 64 lanes x 4 floats, one conflict-free ds_read_b128 per four MFMAs), one workgroup per CU of the stream,
+// and every WAVE strides over (16 rows x ALL seven N-tiles) units by itself: the A operand comes straight from memory
+// into the MFMA lanes (float4 at columns 16 c + 4 g, as in k_embed_out2), the next unit's rows are requested before the
+// current unit's MFMAs, a row is read once.  Same accumulation order as the other two kernels (k-chunks first to last),
+// so the three agree to the bit.  D = 100 (Dp = 112).
+// The two paths are device functions of their own (round 15): neither reads what the other writes, and only the source
+// path reads the memory table.  aggregate.hip builds k_embed_out3 from both (workgroups [0, n_src) the source path), a
+// source-only and a neighbour-only launch from one each; memory_update.hip runs the neighbour path behind the GRU tiles
+// of k_nbr_gru, in that kernel's eight-wave workgroups.
+// ---------------------------------------------------------------------------
+constexpr int EO3_NT = 7, EO3_KC = 7, EO3_DP = 112, EO3_LDY = 116;
+constexpr int EO3_FRAG = EO3_NT * EO3_KC * 256;      // floats of one weight matrix in fragment order
+constexpr size_t EO3_SRC_LDS = (size_t)(2 * EO3_FRAG + AGG_WAVES * 16 * EO3_LDY) * 4;     // fc1s, fc2s, the waves' hidden rows
+constexpr size_t EO3_NBR_LDS = (size_t)EO3_FRAG * 4;                                      // fc2
+
+template <int THREADS>
+__device__ __forceinline__ void eo3_fill(float *Wl, const float *__restrict__ Wp, int tid)
+{
+    constexpr int PER = (EO3_NT * EO3_KC * 64 + THREADS - 1) / THREADS;  // fragments-lanes per thread: all in flight, then stored
+    f32x4 v[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int idx = tid + q * THREADS, frag = idx >> 6, ln = idx & 63;
+        const int b = frag / EO3_KC, c = frag - b * EO3_KC;
+        v[q] = idx < EO3_NT * EO3_KC * 64
+                   ? *reinterpret_cast<const f32x4 *>(Wp + (size_t)(16 * b + (ln & 15)) * EO3_DP + 16 * c + 4 * (ln >> 4))
+                   : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int idx = tid + q * THREADS;
+        if (idx < EO3_NT * EO3_KC * 64) reinterpret_cast<f32x4 *>(Wl)[idx] = v[q];
+    }
+}
+
+// The source path: memory[nodes] -> fc1s -> relu -> fc2s.  Workgroup wg of n_wgs, four waves (AGG_THREADS); fc1s and fc2s
+// resident (98 KB), the hidden rows through 7 KB of the wave's own LDS: EO3_SRC_LDS bytes at smem.
+__device__ __forceinline__ void eo3_src_body(const EmbedOutArgs &E, char *smem, int wg, int n_wgs)
+{
+    const float *__restrict__ memory = E.memory;
+    const long long num_nodes = E.num_nodes, N = E.N;
+    const int *__restrict__ nodes = E.nodes;
+    const int D = E.D, M = E.M;
+    const float *__restrict__ fc1s_p = E.fc1s_p, *__restrict__ fc1s_b = E.fc1s_b, *__restrict__ fc2s_p = E.fc2s_p, *__restrict__ fc2s_b = E.fc2s_b;
+    float *__restrict__ out = E.out;
+    int *status = E.status;
+    float *W0 = reinterpret_cast<float *>(smem);                         // fc1s
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g4 = lane >> 4;
+    const int OW = D * (M + 1);
+    const long long tiles = (N + 15) / 16;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    bool cin[EO3_KC];                                                    // this lane's float4 of chunk c lies inside the row
+#pragma unroll
+    for (int c = 0; c < EO3_KC; ++c) cin[c] = 16 * c + 4 * g4 < D;
+    const f32x4 *Wf0 = reinterpret_cast<const f32x4 *>(W0) + lane;
+    float *W1 = W0 + EO3_FRAG;                                           // fc2s
+    float *Y = W1 + EO3_FRAG + wave * 16 * EO3_LDY;                      // this wave's hidden rows
+    eo3_fill<AGG_THREADS>(W0, fc1s_p, tid);
+    eo3_fill<AGG_THREADS>(W1, fc2s_p, tid);
+    float b1v[EO3_NT], b2v[EO3_NT];
+#pragma unroll
+    for (int b = 0; b < EO3_NT; ++b) {
+        b1v[b] = 16 * b + r16 < D ? fc1s_b[16 * b + r16] : 0.f;
+        b2v[b] = 16 * b + r16 < D ? fc2s_b[16 * b + r16] : 0.f;
+    }
+    const f32x4 *Wf1 = reinterpret_cast<const f32x4 *>(W1) + lane;
+    const long long stride = (long long)n_wgs * AGG_WAVES;
+    long long t = (long long)wg * AGG_WAVES + wave;
+    // ids two units ahead, rows one unit ahead
+    auto node_of = [&](long long tt) -> int { return (tt < tiles && tt * 16 + r16 < N) ? nodes[tt * 16 + r16] : -1; };
+    auto rows_of = [&](int nd, f32x4 (&a)[EO3_KC]) {
+        const bool ok = nd >= 0 && nd < num_nodes;
+#pragma unroll
+        for (int c = 0; c < EO3_KC; ++c)
+            a[c] = (ok && cin[c]) ? *reinterpret_cast<const f32x4 *>(memory + (size_t)nd * D + 16 * c + 4 * g4) : zero4;
+    };
+    int nd_cur = node_of(t), nd_nxt = node_of(t + stride);
+    f32x4 a[EO3_KC], an[EO3_KC];
+    if (t < tiles) rows_of(nd_cur, a);
+    __syncthreads();                                                     // both weight images are in LDS
+    for (; t < tiles; t += stride) {
+        const long long r0 = t * 16;
+        if (r0 + r16 < N && (nd_cur < 0 || nd_cur >= num_nodes)) atomicExch(status, ZT_ERR_RANGE);
+        rows_of(nd_nxt, an);                                             // the next unit's rows, under this unit's MFMAs
+        nd_cur = nd_nxt;
+        nd_nxt = node_of(t + 2 * stride);
+        f32x4 acc1[EO3_NT];
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) acc1[b] = zero4;
+#pragma unroll
+        for (int c = 0; c < EO3_KC; ++c) {
+            f32x4 w[EO3_NT];
+#pragma unroll
+            for (int b = 0; b < EO3_NT; ++b) w[b] = Wf0[(b * EO3_KC + c) * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)                                      // consecutive MFMAs on different accumulators
+#pragma unroll
+                for (int b = 0; b < EO3_NT; ++b) acc1[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], w[b][j], acc1[b], 0, 0, 0);
+        }
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = acc1[b][j] + b1v[b];
+                Y[(4 * g4 + j) * EO3_LDY + 16 * b + r16] = (16 * b + r16 < D && v > 0.f) ? v : 0.f;
+            }
+        wave_sync();
+        f32x4 acc[EO3_NT];
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) acc[b] = zero4;
+#pragma unroll
+        for (int c = 0; c < EO3_KC; ++c) {
+            const f32x4 y = *reinterpret_cast<const f32x4 *>(Y + r16 * EO3_LDY + 16 * c + 4 * g4);
+            f32x4 w[EO3_NT];
+#pragma unroll
+            for (int b = 0; b < EO3_NT; ++b) w[b] = Wf1[(b * EO3_KC + c) * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int b = 0; b < EO3_NT; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(y[j], w[b][j], acc[b], 0, 0, 0);
+        }
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) {
+            const int col = 16 * b + r16;
+            if (col < D) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (r0 + 4 * g4 + j < N) out[(size_t)(r0 + 4 * g4 + j) * OW + col] = acc[b][j] + b2v[b];
+            }
+        }
+        wave_sync();                                                     // Y is free for the next unit
+#pragma unroll
+        for (int c = 0; c < EO3_KC; ++c) a[c] = an[c];
+    }
+}
+
+// The neighbour paths: fc2 on the reduced rows H, S of the M models; reads nothing of the memory table.  Workgroup wg of
+// n_wgs, WAVES waves each (every thread of the workgroup comes here: one barrier); fc2 resident: EO3_NBR_LDS bytes at smem.
+// FB: N-tile fragments of a k-chunk held at once -- all seven where the kernel has the register file to itself
+// (k_embed_out3), fewer where the waves share it with another body's (k_nbr_gru: there the biases are fetched behind the
+// MFMAs too; plain rows only, HG = 1).  Each accumulator sees its k-chunks first to last whatever FB is.
+template <int HG, int WAVES, int FB>
+__device__ __forceinline__ void eo3_nbr_body(const EmbedOutArgs &E, char *smem, int wg, int n_wgs)
+{
+    const long long N = E.N;
+    const int D = E.D, M = E.M;
+    const float *__restrict__ H = E.H, *__restrict__ S = E.S, *__restrict__ fc2_p = E.fc2_p, *__restrict__ fc2_b = E.fc2_b;
+    float *__restrict__ out = E.out;
+    constexpr bool LEAN = FB < EO3_NT;
+    static_assert(HG == 1 || !LEAN, "partial-sum groups only with all seven fragments held (k_embed_out3)");
+    float *W0 = reinterpret_cast<float *>(smem);                         // fc2
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g4 = lane >> 4;
+    const int OW = D * (M + 1);
+    const long long tiles = (N + 15) / 16;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    bool cin[EO3_KC];                                                    // this lane's float4 of chunk c lies inside the row
+#pragma unroll
+    for (int c = 0; c < EO3_KC; ++c) cin[c] = 16 * c + 4 * g4 < D;
+    const f32x4 *Wf0 = reinterpret_cast<const f32x4 *>(W0) + lane;
+    eo3_fill<64 * WAVES>(W0, fc2_p, tid);
+    float b2v[LEAN ? 1 : EO3_NT];
+    if constexpr (!LEAN) {
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) b2v[b] = 16 * b + r16 < D ? fc2_b[16 * b + r16] : 0.f;
+    }
+    const long long units = tiles * M;
+    const long long stride = (long long)n_wgs * WAVES;
+    long long u = (long long)wg * WAVES + wave;
+    // a unit's A operand: a query row's HG partial-sum groups (k_fc1_agg_wide), added first to last.  HG = 1: the next
+    // unit's rows are requested under this unit's MFMAs; HG > 1 (F = 172: at most a few units per wave at those batch
+    // sizes): groups [q0, q0 + GQ) at a time, at the top of the unit
+    constexpr int GQ = HG == 1 ? 1 : 5;
+    auto rows_of = [&](long long uu, int q0, f32x4 (&g)[GQ][EO3_KC]) {
+        const long long m = uu / tiles, r = (uu - m * tiles) * 16 + r16;
+        const bool rin = uu < units && r < N;
+        const float *hp = H + (((size_t)m * N + (rin ? r : 0)) * HG + q0) * D + 4 * g4;
+#pragma unroll
+        for (int q = 0; q < GQ; ++q)
+#pragma unroll
+            for (int c = 0; c < EO3_KC; ++c) g[q][c] = (rin && cin[c]) ? *reinterpret_cast<const f32x4 *>(hp + (size_t)q * D + 16 * c) : zero4;
+    };
+    f32x4 gn[GQ][EO3_KC];
+    if (HG == 1) rows_of(u, 0, gn);
+    __syncthreads();                                                     // the weight image is in LDS
+    for (; u < units; u += stride) {
+        const long long m = u / tiles, r0 = (u - m * tiles) * 16;
+        f32x4 a[EO3_KC];
+        if (HG == 1) {
+#pragma unroll
+            for (int c = 0; c < EO3_KC; ++c) a[c] = gn[0][c];
+        } else {
+#pragma nounroll
+            for (int q0 = 0; q0 < HG; q0 += GQ) {
+                rows_of(u, q0, gn);
+#pragma unroll
+                for (int c = 0; c < EO3_KC; ++c) {
+                    if (q0 == 0) a[c] = gn[0][c]; else a[c] += gn[0][c];
+#pragma unroll
+                    for (int q = 1; q < GQ; ++q) a[c] += gn[q][c];
+                }
+            }
+        }
+        float sv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sv[j] = r0 + 4 * g4 + j < N ? S[(size_t)m * N + r0 + 4 * g4 + j] : 0.f;
+        if (HG == 1) rows_of(u + stride, 0, gn);                         // the next unit's rows, under this unit's MFMAs
+        // (LEAN: the fragments are read from LDS unit by unit -- left to itself the compiler lifts all 49 reads out of the unit
+        //  loop, 196 registers that this kernel does not have)
+        if constexpr (LEAN) asm volatile("" ::: "memory");
+        f32x4 acc[EO3_NT];
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) acc[b] = zero4;
+#pragma unroll
+        for (int c = 0; c < EO3_KC; ++c) {
+#pragma unroll
+            for (int b0 = 0; b0 < EO3_NT; b0 += FB) {
+                f32x4 w[FB];
+#pragma unroll
+                for (int b = 0; b < FB; ++b)
+                    if (b0 + b < EO3_NT) w[b] = Wf0[((b0 + b) * EO3_KC + c) * 64];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)                                  // consecutive MFMAs on different accumulators
+#pragma unroll
+                    for (int b = 0; b < FB; ++b)
+                        if (b0 + b < EO3_NT) acc[b0 + b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], w[b][j], acc[b0 + b], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < EO3_NT; ++b) {
+            const int col = 16 * b + r16;
+            if (col < D) {
+                const float bias = LEAN ? fc2_b[col] : b2v[LEAN ? 0 : b];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (r0 + 4 * g4 + j < N) out[(size_t)(r0 + 4 * g4 + j) * OW + (size_t)D * (m + 1) + col] = acc[b][j] + bias * sv[j];
+            }
+        }
+    }
+}
+
 }  // namespace

@@ -520,6 +520,31 @@ __global__ __launch_bounds__(64 * GRU_WAVES) void k_out_gru(EmbedOutArgs E, int 
     if (bid < out_tiles && threadIdx.x == 0) gate_leave(gate);   // (a source-path workgroup: thread 0 made its add to word[0])
 }
 
+// k_gru with the neighbour paths of the persistent output layers in its grid (round 15).  On large batches the output layers
+// are k_embed_out3's two halves; the source half reads the memory rows this update rewrites and runs in front, as a kernel of
+// its own (embed_ex).  The neighbour half reads H, S and the fc2 weights and writes `out`: nothing this update reads or
+// writes, and nothing k_gru reads -- so it needs no place in the chain aggregation -> output layers -> update, and no gate
+// here.  Workgroups [0, gru_wgs) are k_gru's tiles, exactly (gate == nullptr; workgroup 0 carries the tail gate): they are
+// the long pole and come FIRST.  The workgroups behind them are persistent and stride over the (16 rows, model) units, eight
+// waves each, with fc2 resident in LDS (EO3_NBR_LDS: the launch's dynamic LDS is the larger of the two needs).
+// Registers: the kernel is held to k_gru's four waves per SIMD (launch bounds), so the neighbour body keeps NBR_FB N-tile
+// fragments of a k-chunk at a time instead of seven (embed_out_body.hpp).
+constexpr int NBR_FB = 3;
+template <int CELL>
+__global__ __launch_bounds__(64 * GRU_WAVES, 4) void k_nbr_gru(EmbedOutArgs E, int gru_wgs, GruArgs G)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bid = blockIdx.x;
+    if (bid < gru_wgs) {
+        gru_body<CELL>(G, smem, bid, nullptr);
+        // (the tail gate: as in k_gru)
+        if (G.next_word != nullptr && bid == 0 && threadIdx.x == 0)
+            (void)member_gate_wait<4>(G.next_word, G.next_target, G.next_status, G.next_latch);
+        return;
+    }
+    eo3_nbr_body<1, GRU_WAVES, NBR_FB>(E, smem, bid - gru_wgs, (int)gridDim.x - gru_wgs);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // k_gru_split (round 4): the same update for SMALL row counts.  Phase stamps of k_gru at C2's batch (400 rows, 25
 // workgroups on 224 CUs; tools/exp/gru_phases.py): 66 000 cycles per workgroup, 49 000 of them in the two gate products
@@ -931,6 +956,8 @@ extern "C" int zt_rnn_update(float *memory_dev, float *last_update_dev, const fl
 //   tile (k_gru)        beyond: 16 rows per workgroup, the gate weights streamed from L2 per tile.
 // Output layers held back by embed_ex go into the same launch where both take their tiled forms (k_out_gru) or both their
 // latency-organised ones (k_out_gru2), otherwise in front of the GRU kernel: their source path reads the rows it rewrites.
+// The persistent output layers come divided: embed_ex has launched their source half, and the neighbour half (persist_nbr)
+// runs behind the tile's workgroups in one grid (k_nbr_gru).
 MemoryPlan zt::memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, int T, int gru_choice, int msg_choice,
                                   const HeldOut &held)
 {
@@ -951,7 +978,12 @@ MemoryPlan zt::memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, i
     mp.gru_tiles = (int)((max_rows + 15) / 16);
     mp.NTg = p.Hp / 16;
     mp.grid = (unsigned)mp.gru_tiles;
-    if (fits && (gru_choice == ZT_GRU_SPLIT || (gru_choice == 0 && max_rows <= 512))) {
+    // the neighbour half of the persistent output layers (embed_ex launched their source half): beside the tile's workgroups in
+    // one grid wherever the tile runs at D <= 128 -- and held-back neighbour paths draw the update to the tile at any row
+    // count, unless the split is pinned (then they go in front)
+    const bool nbr = held.present && held.form == OutForm::persist_nbr && held.hg == 1 && round_up(held.D, 16) == EO3_DP &&
+                     held.N > 0 && held.M > 0 && p.Hp <= 16 * GRU_NTW * GRU_WAVES;
+    if (fits && (gru_choice == ZT_GRU_SPLIT || (gru_choice == 0 && max_rows <= 512 && !nbr))) {
         mp.gru = GruForm::split;
         mp.lds2 = ((size_t)16 * p.lda + (size_t)GS_WAVES * 4 * 64 * 4) * 4 + 32 * 4;
         if (held.present && held.form == OutForm::latency && held.same_memory && (held.D + 15) / 16 == mp.NTg &&
@@ -975,6 +1007,14 @@ MemoryPlan zt::memory_kernel_plan(int64_t max_rows, int D, int msg_dim, int F, i
             mp.target = (unsigned)mp.out_tiles;
             mp.participants = (unsigned)mp.out_tiles + (unsigned)mp.gru_tiles;
             mp.grid = (unsigned)(mp.out_tiles * (held.M + 1)) + (unsigned)mp.gru_tiles;
+        } else if (nbr) {
+            // k_nbr_gru: two (16 rows, model) units to a wave -- a workgroup fills 49 KB of LDS before its first unit, and the
+            // fewer of them there are, the more compute units keep both their residency slots for GRU tiles
+            const long long units = (held.N + 15) / 16 * held.M;
+            mp.out = OutLaunch::fused_nbr;
+            mp.n_nb_wgs = (int)std::min<long long>((units + 2 * GRU_WAVES - 1) / (2 * GRU_WAVES), 1024);
+            mp.lds_f = std::max(EO3_NBR_LDS, mp.lds);
+            mp.grid = (unsigned)mp.gru_tiles + (unsigned)mp.n_nb_wgs;
         }
     }
     return mp;
@@ -1042,7 +1082,8 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
     if (mp.out == OutLaunch::front) { const int rc = pending.launch(); if (rc != ZT_OK) return rc; }
     GruArgs G{memory_dev, last_update_dev, messages_dev, msg_ts_dev, rows, cnt, D, msg_dim, p.Xp, p.Hp, p.lda,
               wih, whh, wt->b_ih, wt->b_hh, wm_p, proj_table, (int)max_rows, nullptr, 0, nullptr, nullptr};
-    // (the plain tiled kernel alone takes the tail gate along: the fused and the split forms are other steps' kernels)
+    // (the plain tiled kernel takes the tail gate along, by itself or with the neighbour paths behind it -- k_nbr_gru: the fused
+    //  and the split forms are other steps' kernels)
     if (mp.out != OutLaunch::fused_tile && mp.out != OutLaunch::fused_split && mp.gru == GruForm::tile && tail_gate != nullptr &&
         tail_gate->word != nullptr && tail_gate->status != nullptr && tail_carried != nullptr) {
         G.next_word = tail_gate->word; G.next_target = tail_gate->target; G.next_status = tail_gate->status; G.next_latch = tail_gate->latch;
@@ -1069,6 +1110,15 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
                     return ZT_OK;
                 });
             });
+        case OutLaunch::fused_nbr: {
+            // (persistent neighbour workgroups: at most one per compute unit of the stream)
+            int cus = zt::stream_cu_count(s);
+            if (fuse->max_wgs > 0 && cus > fuse->max_wgs) cus = fuse->max_wgs;
+            const unsigned n_nb = (unsigned)(mp.n_nb_wgs < cus ? mp.n_nb_wgs : cus);
+            ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_nbr_gru<CELL>), mp.lds_f));
+            k_nbr_gru<CELL><<<(unsigned)mp.gru_tiles + n_nb, 64 * GRU_WAVES, mp.lds_f, s>>>(fuse->args, mp.gru_tiles, G);
+            return ZT_OK;
+        }
         default:
             if (mp.gru == GruForm::split) {
                 ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_gru_split<CELL>), mp.lds2));
@@ -1083,7 +1133,7 @@ int zt::gru_update_ex(float *memory_dev, float *last_update_dev, const float *me
         }
     });
     if (rc_launch != ZT_OK) return rc_launch;
-    if (mp.out == OutLaunch::fused_tile || mp.out == OutLaunch::fused_split) fuse->valid = false;     // (launched)
+    if (mp.out == OutLaunch::fused_tile || mp.out == OutLaunch::fused_split || mp.out == OutLaunch::fused_nbr) fuse->valid = false;     // (launched)
     ZT_PROF_END(s, P_GRU);
     ZT_LAUNCH_CHECK();
     return ZT_OK;

@@ -756,7 +756,10 @@ struct Step {
     // ---- P2: aggregate.  The wait for the message build sits between the aggregation and the output layers -- the messages
     // are ready long before the aggregation ends -- so that the GRU follows the output layers without a packet in between.
     // The output layers are held back: gru_update_ex launches them in ONE kernel with the GRU update where both take their
-    // tiled forms (k_out_gru), otherwise in front of it. ----
+    // tiled forms (k_out_gru) or their latency-organised ones (k_out_gru2), otherwise in front of it.  The persistent form
+    // (large batches: C5) is divided: its source half, which reads the memory rows the update rewrites, is launched here,
+    // behind the wait for the messages, and only its neighbour half is held back -- it runs behind the GRU tiles in the
+    // update's grid (k_nbr_gru), off the chain aggregation -> source half -> update. ----
     int aggregate()
     {
         if (n_rows == 0) return ZT_OK;

@@ -34,9 +34,10 @@ int zt_test_tppr_plan_dump(zt_tppr *h, int32_t *wo, int32_t *pflag, int32_t *hv,
 int zt_test_embed_plan(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table, int32_t training,
                        int32_t agg_choice, int32_t out_choice, int32_t *agg_out, int32_t *out_out, int64_t *lds_out);
 /* Test hook: the memory update's kernel choice for one shape (zt::memory_kernel_plan, host code only).  The held-back output
- * layers: held (0 / 1), out_form (0 tiled, 1 latency, 2 persist), hg, out_D, out_M, gx, out_N, same_memory.  out[14] =
+ * layers: held (0 / 1), out_form (0 tiled, 1 latency, 2 persist, 3 the persistent form's neighbour half), hg, out_D, out_M, gx, out_N, same_memory.  out[14] =
  * refusal (0 none, 1 bad argument, 2 D > 128, 3 message width), message kernel (0 one, 1 two positions per wave), GRU form
- * (0 none, 1 tile, 2 split), output layers (0 none, 1 in front, 2 fused with the tile, 3 fused with the split), lds, lds2,
+ * (0 none, 1 tile, 2 split), output layers (0 none, 1 in front, 2 fused with the tile, 3 fused with the split, 4 the neighbour half behind the
+ * tile's workgroups), lds, lds2,
  * lds_f, gru_tiles, NTg, n_src_wgs, n_nb_wgs, out_tiles, target, participants. */
 int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim, int32_t F, int32_t T, int32_t gru_choice,
                         int32_t msg_choice, int32_t held, int32_t out_form, int32_t hg, int32_t out_D, int32_t out_M,
@@ -68,6 +69,25 @@ int zt_test_group_plan(int32_t streaming, int32_t release, int32_t want, int32_t
 /* Test hook: pin the node decoder's arrangement process-wide (zt::decoder_plan: 0 = the plan's pick, 1 = one wave per 16 rows,
  * 5 = five waves per 16 rows); zt_node_decoder_plan answers under the pin.  ZT_ERR_ARG for any other value. */
 int zt_test_decoder_arrangement(int32_t value);
+/* Test hook: whether a caller that can hold output layers back (the pipeline) gets the persistent form divided for this shape
+ * (zt::embed_kernel_plan's nbr_later, host code only): the source path launched by itself, the neighbour paths handed on to the
+ * GRU update's launch (k_nbr_gru).  out_choice: the ZT_CHOICE_EMBED_OUT selection.  *divided_out = 0 / 1. */
+int zt_test_embed_divided(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table,
+                          int32_t out_choice, int32_t *divided_out);
+/* Test hook: the two calls of a pipeline step without the pipeline -- zt_embed with its output layers held back (zt::embed_ex),
+ * then the memory update that takes them along (zt::gru_update_ex) -- under the process's ZT_CHOICE_EMBED_OUT / ZT_CHOICE_GRU.
+ * The first arguments are zt_embed's, the rest zt_gru_update's (cell: ZT_CELL_GRU / ZT_CELL_RNN), except that the rows to
+ * update are the caller's list: their count in gru_ws's first word, the ids at zt_gru_rows_offset, at most max_rows.
+ * max_wgs: the divided persistent form's launches take at most so many persistent workgroups each (0 = one per compute unit
+ * of the stream), so that a small grid's seams -- fewer units than striding waves, as many, one more -- sit at a test's sizes.
+ * *out_launch = what became of the held-back layers (zt_test_memory_plan's values; 4 = behind the GRU tiles, k_nbr_gru). */
+int zt_test_embed_gru(float *memory_dev, const float *efeat_dev, int64_t num_nodes, int64_t num_edges, int32_t D, int32_t F,
+                      int32_t T, const int32_t *nodes_dev, int64_t N, int32_t M, int32_t k, const int32_t *nbr_dev,
+                      const int32_t *eix_dev, const float *dt_dev, const float *w_dev, const zt_embed_weights *ew,
+                      float *out_dev, void *embed_ws, int32_t *status_dev, float *proj_table_dev, int32_t embed_ready,
+                      float *last_update_dev, const float *messages_dev, const float *msg_ts_dev, uint8_t *flags_dev,
+                      int32_t msg_dim, int64_t max_rows, const zt_gru_weights *gw, void *gru_ws, int32_t gru_ready,
+                      int32_t cell, int32_t max_wgs, int32_t *out_launch, void *stream);
 
 #ifdef __cplusplus
 }

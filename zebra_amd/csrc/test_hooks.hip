@@ -131,7 +131,7 @@ extern "C" int zt_test_memory_plan(int64_t max_rows, int32_t D, int32_t msg_dim,
                                    int32_t msg_choice, int32_t held, int32_t out_form, int32_t hg, int32_t out_D, int32_t out_M,
                                    int32_t gx, int64_t out_N, int32_t same_memory, int64_t *out)
 {
-    if (!out || out_form < 0 || out_form > 2) return ZT_ERR_ARG;
+    if (!out || out_form < 0 || out_form > 3) return ZT_ERR_ARG;
     const HeldOut h{held != 0, (OutForm)out_form, hg, out_D, out_M, gx, (long long)out_N, same_memory != 0};
     const MemoryPlan mp = memory_kernel_plan(max_rows, D, msg_dim, F, T, gru_choice, msg_choice, h);
     const int64_t v[14] = {(int64_t)mp.refusal, (int64_t)mp.msg, (int64_t)mp.gru, (int64_t)mp.out, (int64_t)mp.lds, (int64_t)mp.lds2,
@@ -187,6 +187,40 @@ extern "C" int zt_test_group_plan(int32_t streaming, int32_t release, int32_t wa
     out[0] = gp.by_member;
     out[1] = gp.limit;
     return ZT_OK;
+}
+
+extern "C" int zt_test_embed_divided(int64_t N, int32_t D, int32_t F, int32_t T, int32_t M, int32_t k, int32_t have_table,
+                                     int32_t out_choice, int32_t *divided_out)
+{
+    if (!divided_out) return ZT_ERR_ARG;
+    const KernelPlan kp = embed_kernel_plan(N, D, F, T, M, k, have_table != 0, false, 0, out_choice);
+    *divided_out = kp.nbr_later ? 1 : 0;
+    return ZT_OK;
+}
+
+// embed_ex with its output layers held back, then gru_update_ex with them: the two calls of a pipeline step, without the
+// pipeline.  The GRU rows are the caller's: gru_ws holds the count (first word) and the row list (zt_gru_rows_offset).
+extern "C" int zt_test_embed_gru(float *memory_dev, const float *efeat_dev, int64_t num_nodes, int64_t num_edges, int32_t D, int32_t F,
+                                 int32_t T, const int32_t *nodes_dev, int64_t N, int32_t M, int32_t k, const int32_t *nbr_dev,
+                                 const int32_t *eix_dev, const float *dt_dev, const float *w_dev, const zt_embed_weights *ew,
+                                 float *out_dev, void *embed_ws, int32_t *status_dev, float *proj_table_dev, int32_t embed_ready,
+                                 float *last_update_dev, const float *messages_dev, const float *msg_ts_dev, uint8_t *flags_dev,
+                                 int32_t msg_dim, int64_t max_rows, const zt_gru_weights *gw, void *gru_ws, int32_t gru_ready,
+                                 int32_t cell, int32_t max_wgs, int32_t *out_launch, void *stream)
+{
+    if (!out_launch || !nodes_dev || max_wgs < 0) return ZT_ERR_ARG;
+    embed_out_deferred held{};
+    held.max_wgs = max_wgs;
+    int rc = embed_ex(memory_dev, efeat_dev, num_nodes, num_edges, D, F, T, nodes_dev, N, M, k, nbr_dev, eix_dev, dt_dev, w_dev, ew,
+                      out_dev, embed_ws, status_dev, proj_table_dev, embed_ready, stream, nullptr, &held, nullptr);
+    if (rc != ZT_OK) return rc;
+    // what the GRU launch will make of them: 0 none (they ran in embed_ex), 1 in front, 2 / 3 fused, 4 behind the tiles (k_nbr_gru)
+    HeldOut h{};
+    if (held.valid) h = HeldOut{true, held.form, held.hg, held.args.D, held.args.M, held.gx, held.args.N, held.args.memory == memory_dev};
+    *out_launch = (int32_t)memory_kernel_plan(max_rows, D, msg_dim, 0, 0, kernel_choice(ZT_CHOICE_GRU), 0, h).out;
+    const float *wm_p = proj_table_dev ? embed_wm_ptr(embed_ws, N, D, F, T, M, k) : nullptr;
+    return gru_update_ex(memory_dev, last_update_dev, messages_dev, msg_ts_dev, flags_dev, num_nodes, D, msg_dim, nodes_dev, max_rows,
+                         nullptr, gw, gru_ws, gru_ready, wm_p, wm_p ? proj_table_dev : nullptr, stream, true, true, &held, cell);
 }
 
 extern "C" int zt_test_decoder_arrangement(int32_t value)
