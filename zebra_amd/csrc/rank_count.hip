@@ -1,8 +1,8 @@
 // Where a probability stands in a large candidate pool ("Read-only queries and ranking"):
 //   zt_affinity_count  for each query the number of present candidates of a shared pool whose probability -- zt_affinity_rank's,
 //                      bit for bit (rank_pair.hpp) -- is ABOVE the query's threshold and the number EQUAL to it, without ever
-//                      writing prob[Q][C]: the two integers a full-pool rank needs.  The walk is rank_topk.hip's: the pool goes
-//                      through the workspace in SLABS of P_c rows, per slab one launch of
+//                      writing prob[Q][C]: the two integers a full-pool rank needs.  The walk is rank_walk.hpp's, as
+//                      rank_topk.hip's is: the pool goes through the workspace in SLABS of P_c rows, per slab one launch of
 //     k_count_pairs    a workgroup takes RK_TQ queries and a SPAN of candidate columns; every wave scores its 32 candidates of a
 //                      step against the four query rows from LDS and keeps 2 x RK_TQ counters fed by ballots (wave-uniform
 //                      integers); at the end the four waves' counters are added through LDS and ONE integer atomicAdd per
@@ -13,7 +13,7 @@
 #include <algorithm>
 
 #include "common.hpp"
-#include "rank_pair.hpp"
+#include "rank_walk.hpp"
 
 using namespace zt;
 
@@ -21,8 +21,6 @@ namespace {
 
 constexpr int CN_WAVES = 4;                          // waves per workgroup
 constexpr int CN_MAX_SKIP = ZT_COUNT_MAX_SKIP;
-constexpr long long CN_SLAB_BYTES = 128ll << 20;     // P_c of one slab at most: half the Infinity Cache (rank_topk.hip's cap)
-constexpr long long CN_SLAB_ROWS = 1ll << 18;        // ... and its rows at most
 constexpr long long CN_TARGET_WGS = 2048;            // workgroups worth cutting spans for: 8 per compute unit
 constexpr int CN_MIN_STEPS = 4;                      // steps of a workgroup per span at least: a span pays one load of the query
                                                      // tile into LDS and 2 x RK_TQ atomics, no list warm-up as the top-K's
@@ -32,13 +30,11 @@ struct CountPlan {
     long long q_tiles, slab_rows, n_slabs, span_cols, n_spans, grid, h_chunks, off_pc, min_bytes;
 };
 
-inline long long round_up_ll(long long x, long long m) { return (x + m - 1) / m * m; }
-inline long long count_cap_rows(int H) { return std::max(32ll, std::min(CN_SLAB_ROWS, CN_SLAB_BYTES / ((long long)H * 4) / 32 * 32)); }
 // byte offset of the slab's P_c behind the status word and P_q
 inline void count_layout(long long Q, int H, CountPlan &p)
 {
     p.q_tiles = (Q + RK_TQ - 1) / RK_TQ;
-    p.off_pc = (long long)RK_HEAD + round_up_ll(Q * (long long)H * 4, 256);
+    p.off_pc = rank_layout_head(Q, H);
     p.min_bytes = p.off_pc + 32ll * H * 4;
     p.h_chunks = (H + RK_HC - 1) / RK_HC;
 }
@@ -49,50 +45,35 @@ bool count_plan(long long Q, long long Nc, int H, long long workspace_bytes, Cou
 {
     count_layout(Q, H, p);
     if (workspace_bytes < p.min_bytes) return false;
-    p.slab_rows = std::min(count_cap_rows(H), (workspace_bytes - p.off_pc) / ((long long)H * 4) / 32 * 32);
+    p.slab_rows = rank_slab_rows(H, workspace_bytes - p.off_pc);
     p.n_slabs = std::max(1ll, (Nc + p.slab_rows - 1) / p.slab_rows);
     const long long cols = std::min(p.slab_rows, std::max(Nc, 1ll));            // columns a launch walks: a slab's rows
-    const long long max_spans = std::max(1ll, (CN_TARGET_WGS + p.q_tiles - 1) / std::max(1ll, p.q_tiles));
-    const long long n = std::min(max_spans, std::max(1ll, cols / (CN_STEP_COLS * CN_MIN_STEPS)));
-    p.span_cols = round_up_ll((cols + n - 1) / n, CN_STEP_COLS);               // a multiple of the step: a wave's 32 columns of
-    p.n_spans = std::max(1ll, (cols + p.span_cols - 1) / p.span_cols);         // a step lie in one word of absent bits
+    rank_cut_spans(cols, CN_STEP_COLS, CN_MIN_STEPS, rank_max_spans(CN_TARGET_WGS, p.q_tiles), p.span_cols, p.n_spans);
     p.grid = p.q_tiles * p.n_spans;
     return true;
 }
 
-struct CountArgs {
-    const float *Pq, *Pc;             // [Q][H]; the slab's rows [r0, r0 + rows) of P_c
+struct CountArgs : RkWalkArgs {      // (cand_idx, Nc, C, status: the indexed form's, unset here)
     const float *thr;                 // [Q]
     const int *skip;                  // [Q][n_skip] or NULL
-    long long Q, r0, rows, idx_base;
-    long long n_spans, span_cols;
-    int H, n_skip;
-    const float *b1, *w2, *b2;
+    int n_skip;
     int *above, *equal;               // [Q], added to
-    const unsigned *absent;           // [Q][absent_words] or NULL: read by the MASKED instantiation alone
-    long long absent_words;
 };
 
-// One workgroup: RK_TQ queries against one span of the slab's columns, in steps of CN_STEP_COLS.  The pair sum, the NaN rule,
-// the skip and the absent bits are k_topk_pairs<RK_TQ, ., MASKED>'s (rank_topk.hip) -- here with up to CN_MAX_SKIP skipped
-// columns per query --; what happens to a present candidate's probability differs: two compares against the query's threshold
-// and two ballots.  Every lane of a wave takes every ballot (wave-uniform control flow), so the counters are wave-uniform.
+// One workgroup: RK_TQ queries against one span of the slab's columns -- rank_walk.hpp's span walk in its shared-pool form
+// (rk_span_walk<RK_TQ, MASKED, .>: the steps of CN_STEP_COLS, the NaN rule, the absent bits, the pair sum), here with up to
+// CN_MAX_SKIP skipped columns per query.  What happens to a present candidate's probability: two compares against the query's
+// threshold and two ballots.  Every lane of a wave takes every ballot (wave-uniform control flow), so the counters are
+// wave-uniform.
 template <bool MASKED>
 __global__ __launch_bounds__(WAVE * CN_WAVES) void k_count_pairs(const CountArgs a)
 {
-    __shared__ float4 s_q[RK_TQ][RK_HC / 4];
-    __shared__ float4 s_w[RK_HC / 4];
+    __shared__ RkTileLds s_t;
     __shared__ int s_cnt[CN_WAVES][2 * RK_TQ];
     __shared__ int s_skip[RK_TQ][CN_MAX_SKIP];                                  // the global columns query qi leaves out, or -1
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int grp = lane >> 4, gl = lane & 15;
     const long long qt = blockIdx.x / a.n_spans, span = blockIdx.x - qt * a.n_spans;
     const long long q0 = qt * RK_TQ;
-    const int H = a.H;
-    const long long lo = min(a.rows, span * a.span_cols), hi = min(a.rows, lo + a.span_cols);
-    const long long nsteps = (hi - lo + CN_STEP_COLS - 1) / CN_STEP_COLS;       // the same for the four waves (barriers below)
-    const int nchunks = (H + RK_HC - 1) / RK_HC;
-    const float bias2 = a.b2[0];
 
     float thr[RK_TQ];
     int n_above[RK_TQ], n_equal[RK_TQ];
@@ -101,91 +82,16 @@ __global__ __launch_bounds__(WAVE * CN_WAVES) void k_count_pairs(const CountArgs
         thr[qi] = q0 + qi < a.Q ? a.thr[q0 + qi] : 0.f;
         n_above[qi] = n_equal[qi] = 0;
     }
-    if (tid < RK_TQ * CN_MAX_SKIP) {                                            // (read after the barrier every path below has)
+    if (tid < RK_TQ * CN_MAX_SKIP) {                                            // (read after the barrier every path of the walk has)
         const int qi = tid / CN_MAX_SKIP, j = tid - qi * CN_MAX_SKIP;
         s_skip[qi][j] = (j < a.n_skip && q0 + qi < a.Q) ? a.skip[(q0 + qi) * a.n_skip + j] : -1;
     }
-
-    auto load_chunk = [&](int h0, int hn) {
-        for (int v = tid; v < (RK_TQ + 1) * (hn / 4); v += WAVE * CN_WAVES) {
-            const int r = v / (hn / 4), c4 = v - r * (hn / 4);
-            const float4 b = *reinterpret_cast<const float4 *>((r < RK_TQ ? a.b1 : a.w2) + h0 + 4 * c4);
-            if (r == RK_TQ) { s_w[c4] = b; continue; }
-            float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q0 + r < a.Q) p = *reinterpret_cast<const float4 *>(a.Pq + (q0 + r) * H + h0 + 4 * c4);
-            s_q[r][c4] = rk_query_bias(p, b);
-        }
-    };
-    if (nchunks == 1) {
-        load_chunk(0, H);
-        __syncthreads();
-    }
-
-    const int myj = rk_fold_pair(gl);                                   // the pair of its group whose sum this lane ends with
-    for (long long t = 0; t < nsteps; ++t) {
-        // this lane's own candidate: column of the slab = its local row (-1: nothing to read)
-        const long long mycol = lo + t * CN_STEP_COLS + wave * RK_TC + grp * RK_NC + myj;
-        const int myrow = mycol < hi ? (int)mycol : -1;
-        // a NaN anywhere in a candidate's embedding makes its whole projected row NaN; the pair sum's relu (fmaxf) would drop
-        // it: such a candidate is a NaN candidate, never counted (zt_affinity_topk's rule)
-        const bool nan_row = myrow >= 0 && a.Pc[(long long)myrow * H] != a.Pc[(long long)myrow * H];
-        // MASKED: the wave's RK_TC = 32 columns of this step lie in ONE word of a query's bits -- spans begin at multiples of
-        // the step and slabs at multiples of 32 rows (count_plan) --, so the word's address is the same in every lane
-        unsigned gone[RK_TQ];
-        if (MASKED) {
-            static_assert(RK_TC == 32, "one word of absent bits per wave and step");
-            const long long wcol = lo + t * CN_STEP_COLS + __builtin_amdgcn_readfirstlane(wave) * RK_TC;
-            const long long word = (a.r0 + wcol) >> 5;                  // < ceil(C / 32) wherever wcol < hi
+    rk_span_walk<RK_TQ, MASKED, CN_WAVES>(a, s_t, q0, span, [&](int qi, float p, bool present, long long gcol) {
 #pragma unroll
-            for (int qi = 0; qi < RK_TQ; ++qi)
-                gone[qi] = (wcol < hi && q0 + qi < a.Q) ? a.absent[(q0 + qi) * a.absent_words + word] : 0u;
-        }
-        int row[RK_NC];
-#pragma unroll
-        for (int j = 0; j < RK_NC; ++j)          // pair j's row from the lane of this group that owns it (bit 0 of gl clear)
-            row[j] = __shfl(myrow, (lane & 48) | ((j & 4) << 1) | ((j & 2) << 1) | ((j & 1) << 1), WAVE);
-
-        float acc[RK_TQ][RK_NC];
-#pragma unroll
-        for (int qi = 0; qi < RK_TQ; ++qi)
-#pragma unroll
-            for (int j = 0; j < RK_NC; ++j) acc[qi][j] = 0.f;
-
-        for (int h0 = 0; h0 < H; h0 += RK_HC) {
-            const int hn = min(RK_HC, H - h0);                 // a multiple of 4
-            if (nchunks > 1) {
-                __syncthreads();                               // the chunk before has been read
-                load_chunk(h0, hn);
-                __syncthreads();
-            }
-            for (int c4 = gl; c4 < hn / 4; c4 += RK_GROUP) {
-                float4 pc[RK_NC];
-#pragma unroll
-                for (int j = 0; j < RK_NC; ++j) {
-                    pc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (row[j] >= 0) pc[j] = *reinterpret_cast<const float4 *>(a.Pc + (long long)row[j] * H + h0 + 4 * c4);
-                }
-                const float4 w = s_w[c4];
-#pragma unroll
-                for (int qi = 0; qi < RK_TQ; ++qi) {
-                    const float4 pq = s_q[qi][c4];
-#pragma unroll
-                    for (int j = 0; j < RK_NC; ++j) acc[qi][j] = rk_pair_step(acc[qi][j], w, pq, pc[j]);
-                }
-            }
-        }
-        const long long gcol = a.r0 + mycol + a.idx_base;      // <= INT32_MAX wherever myrow >= 0 (the host checks idx_base + C)
-#pragma unroll
-        for (int qi = 0; qi < RK_TQ; ++qi) {
-            const float p = rk_prob(rk_fold16x8(acc[qi], gl), bias2);
-            bool present = myrow >= 0 && !nan_row && (gl & 1) == 0 && p == p && q0 + qi < a.Q;
-#pragma unroll
-            for (int j = 0; j < CN_MAX_SKIP; ++j) present = present && gcol != (long long)s_skip[qi][j];
-            if (MASKED) present = present && ((gone[qi] >> (mycol & 31)) & 1u) == 0u;
-            n_above[qi] += __popcll(__ballot(present && p > thr[qi]));          // IEEE compares: a NaN threshold counts nothing,
-            n_equal[qi] += __popcll(__ballot(present && p == thr[qi]));         // -0.0 equals +0.0
-        }
-    }
+        for (int j = 0; j < CN_MAX_SKIP; ++j) present = present && gcol != (long long)s_skip[qi][j];
+        n_above[qi] += __popcll(__ballot(present && p > thr[qi]));              // IEEE compares: a NaN threshold counts nothing,
+        n_equal[qi] += __popcll(__ballot(present && p == thr[qi]));             // -0.0 equals +0.0
+    });
 
     // the four waves' counters through LDS, then one atomicAdd per query and counter: integer sums, any order gives the number
     if (lane == 0) {
@@ -212,8 +118,7 @@ extern "C" int64_t zt_affinity_count_workspace_bytes(int64_t Q, int64_t Nc, int3
     if (Q < 0 || Nc < 0 || !rank_width_ok(H)) return -1;
     CountPlan p;
     count_layout(Q, H, p);
-    const long long rows = std::min(count_cap_rows(H), round_up_ll(std::max<long long>(Nc, 32), 32));
-    return p.off_pc + rows * (long long)H * 4;
+    return p.off_pc + rank_pool_rows(Nc, H) * (long long)H * 4;
 }
 
 extern "C" int zt_affinity_count_plan(int64_t Q, int64_t Nc, int32_t H, int64_t workspace_bytes, int64_t *plan_out)
@@ -222,10 +127,7 @@ extern "C" int zt_affinity_count_plan(int64_t Q, int64_t Nc, int32_t H, int64_t 
         set_error("zt_affinity_count_plan: bad argument");
         return ZT_ERR_ARG;
     }
-    if (!rank_width_ok(H)) {
-        set_error("zt_affinity_count_plan: H=%d unsupported (H %% 4 == 0 and %d <= H <= %d)", H, RANK_MIN_H, RANK_MAX_H);
-        return ZT_ERR_UNSUPPORTED;
-    }
+    if (!rank_width_ok(H)) return rank_width_refused("zt_affinity_count_plan", H);
     CountPlan p;
     if (!count_plan(Q, Nc, H, workspace_bytes, p)) {
         set_error("zt_affinity_count_plan: workspace of %lld bytes, at least %lld needed (zt_affinity_count_workspace_bytes for Nc = 32)",
@@ -257,10 +159,7 @@ extern "C" int zt_affinity_count(const float *emb_q_dev, int64_t Q, const float 
                   (long long)((Nc + 31) / 32));
         return ZT_ERR_ARG;
     }
-    if (!rank_width_ok(H)) {
-        set_error("zt_affinity_count: H=%d unsupported (H %% 4 == 0 and %d <= H <= %d)", H, RANK_MIN_H, RANK_MAX_H);
-        return ZT_ERR_UNSUPPORTED;
-    }
+    if (!rank_width_ok(H)) return rank_width_refused("zt_affinity_count", H);
     if (idx_base > 0x7fffffffll - Nc) {
         set_error("zt_affinity_count: idx_base=%lld + C=%lld exceeds int32 columns", (long long)idx_base, (long long)Nc);
         return ZT_ERR_ARG;
@@ -276,11 +175,7 @@ extern "C" int zt_affinity_count(const float *emb_q_dev, int64_t Q, const float 
         return ZT_ERR_UNSUPPORTED;
     }
     if (Q == 0) return ZT_OK;
-    if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || ((uintptr_t)workspace_dev & 15) || ((uintptr_t)w->fc1_b & 15) ||
-        ((uintptr_t)w->fc2_w & 15)) {
-        set_error("zt_affinity_count: NULL weight, or workspace / fc1 bias / fc2 weight not 16-byte aligned");
-        return ZT_ERR_ARG;
-    }
+    if (!rank_weights_ok("zt_affinity_count", w, workspace_dev)) return ZT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (!accumulate) {                         // the kernels add: a fresh call starts from zeros
         ZT_HIP(hipMemsetAsync(above_dev, 0, Q * sizeof(int32_t), s));
@@ -289,10 +184,9 @@ extern "C" int zt_affinity_count(const float *emb_q_dev, int64_t Q, const float 
     if (Nc == 0) return ZT_OK;
     char *ws = reinterpret_cast<char *>(workspace_dev);
     float *Pq = reinterpret_cast<float *>(ws + RK_HEAD), *Pc = reinterpret_cast<float *>(ws + p.off_pc);
-    // W_a = columns [0, H) of fc1.weight [H][2H], W_b = columns [H, 2H): the GEMM calls of zt_affinity_rank, P_c a slab at a time
-    int rc = zt_gemm_f32(emb_q_dev, w->fc1_w, Pq, Q, H, H, H, 2 * (int64_t)H, H, 0, 1, 0, stream);
+    int rc = rank_project(emb_q_dev, w, false, Pq, Q, H, stream);
     if (rc != ZT_OK) return rc;
-    CountArgs a;
+    CountArgs a = {};
     a.Pq = Pq; a.Pc = Pc; a.thr = thr_dev; a.skip = n_skip > 0 ? skip_dev : nullptr;
     a.Q = Q; a.idx_base = idx_base;
     a.n_spans = p.n_spans; a.span_cols = p.span_cols;
@@ -300,10 +194,10 @@ extern "C" int zt_affinity_count(const float *emb_q_dev, int64_t Q, const float 
     a.b1 = w->fc1_b; a.w2 = w->fc2_w; a.b2 = w->fc2_b;
     a.above = above_dev; a.equal = equal_dev;
     a.absent = absent_dev; a.absent_words = absent_words;
-    for (long long slab = 0; slab < p.n_slabs; ++slab) {
+    for (long long slab = 0; slab < p.n_slabs; ++slab) {       // P_c a slab at a time
         a.r0 = slab * p.slab_rows;
         a.rows = std::min<long long>(p.slab_rows, Nc - a.r0);
-        rc = zt_gemm_f32(emb_c_dev + a.r0 * H, w->fc1_w + H, Pc, a.rows, H, H, H, 2 * (int64_t)H, H, 0, 1, 0, stream);
+        rc = rank_project(emb_c_dev + a.r0 * H, w, true, Pc, a.rows, H, stream);
         if (rc != ZT_OK) return rc;
         ZT_PROF_BEGIN(s, P_SCORE);
         if (absent_dev != nullptr) k_count_pairs<true><<<(unsigned)p.grid, WAVE * CN_WAVES, 0, s>>>(a);

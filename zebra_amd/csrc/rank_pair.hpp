@@ -1,5 +1,5 @@
-// The pair sum of the one-vs-many scorers (rank.hip: k_rank_pairs; rank_topk.hip: k_topk_pairs), in ONE place so that both
-// give a pair the same bits:
+// The pair sum of the one-vs-many scorers, in ONE place so that all give a pair the same bits (the walks around it, and so its
+// two call sites, are rank_walk.hpp's: the tile body of rank.hip / rank_train.hip, the span walk of rank_topk.hip / rank_count.hip):
 //   s = b2 + sum_h w2[h] relu((P_q[q][h] + b1[h]) + P_c[row][h]),  prob = 1 / (1 + expf(-s)).
 // Sixteen lanes share a pair.  Lane l of the group adds columns 4l .. 4l + 3 of every 64 in ascending order into one
 // accumulator (rk_pair_step, one call per 64 columns), then the sixteen are folded by xor 8, 4, 2, 1 (rk_fold16, or rk_fold16x8

@@ -1,9 +1,10 @@
 // The one-vs-many scorer of a RANKING training step, forward and backward ("The scorer of a ranking step"):
 //   z[q][c][h]  = (P_q[q][h] + b1[h]) + P_c[row(q, c)][h],   P_q = emb_q W_a^T,  P_c = emb_c W_b^T   (rank.hip's factoring)
 //   logit[q][c] = b2 + sum_h w2[h] relu(z[q][c][h])
-// zt_affinity_rank_train_forward writes the logits -- rank_pair.hpp's pair sum, so sigmoid(logit) computed as rk_prob computes it
-// has the bits zt_affinity_rank writes -- and leaves P_q and P_c with the caller, who keeps them for the backward.  No buffer
-// of Q C H elements exists on either side: the backward forms z and the ReLU mask again from P_q and P_c.
+// zt_affinity_rank_train_forward writes the logits -- rank_walk.hpp's tile body (rk_tile_pairs) over rank_pair.hpp's pair sum,
+// k_rank_pairs' too, so sigmoid(logit) computed as rk_prob computes it has the bits zt_affinity_rank writes -- and leaves P_q
+// and P_c with the caller, who keeps them for the backward.  No buffer of Q C H elements exists on either side: the backward
+// forms z and the ReLU mask again from P_q and P_c.
 //
 // Backward, from dl = d(loss)/d(logit) [Q][C]:
 //   k_rank_bwd_q   one workgroup per RK_TQ queries and 64 columns of H: wave w owns query q0 + w, its four 16-lane groups take
@@ -21,7 +22,7 @@
 // d_fc1_w[:, :H] = dP_q^T emb_q, d_fc1_w[:, H:] = dP_c^T emb_c).  Every sum has one fixed association and there is no float
 // atomic: two runs give the same bits.
 #include "common.hpp"
-#include "rank_pair.hpp"
+#include "rank_walk.hpp"
 
 using namespace zt;
 
@@ -32,70 +33,16 @@ constexpr int RT_CROWS = 4;                  // rows of emb_c per workgroup of t
 constexpr int RT_CCOLS = 4 * WAVE;           // 256 columns of H per workgroup of the candidate pass
 constexpr int RT_CU = 8;                     // pairs of a row whose loads are in flight together
 
-// k_rank_pairs' tiling and arithmetic (rank.hip); what is written is the logit, -inf for an absent pair
+// rank_walk.hpp's tile body (rk_tile_pairs), k_rank_pairs' too (rank.hip); what is written is the logit, -inf for an absent pair
 __global__ __launch_bounds__(WAVE * RK_TQ) void k_rank_train_fwd(const float *__restrict__ Pq, const float *__restrict__ Pc,
                                                                  const int *__restrict__ cand_idx, long long Q, long long Nc,
                                                                  long long C, int H, long long ctiles,
                                                                  const float *__restrict__ b1, const float *__restrict__ w2,
                                                                  const float *__restrict__ b2, float *__restrict__ logit, int *status)
 {
-    __shared__ float4 s_q[RK_TQ][RK_HC / 4];
-    __shared__ float4 s_w[RK_HC / 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int grp = lane >> 4, gl = lane & 15;
-    const long long qt = blockIdx.x / ctiles, ct = blockIdx.x - qt * ctiles;
-    const long long q0 = qt * RK_TQ, q = q0 + wave;
-    const long long c0 = ct * RK_TC + grp * RK_NC;
-
-    long long row[RK_NC];           // row of P_c, or -1: nothing to read (absent, out of range, beyond C or Q)
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < RK_NC; ++j) {
-        const long long c = c0 + j;
-        long long r = -1;
-        if (q < Q && c < C) {
-            r = cand_idx != nullptr ? (long long)cand_idx[q * C + c] : c;
-            if (r < -1 || r >= Nc) { bad = true; r = -1; }
-        }
-        row[j] = r;
-    }
-    if (bad && gl == 0) atomicExch(status, (int)ZT_ERR_RANGE);
-
-    float acc[RK_NC];
-#pragma unroll
-    for (int j = 0; j < RK_NC; ++j) acc[j] = 0.f;
-
-    for (int h0 = 0; h0 < H; h0 += RK_HC) {
-        const int hn = min(RK_HC, H - h0);                     // a multiple of 4
-        if (h0 > 0) __syncthreads();                           // the chunk before has been read
-        for (int v = tid; v < (RK_TQ + 1) * (hn / 4); v += WAVE * RK_TQ) {
-            const int r = v / (hn / 4), c4 = v - r * (hn / 4);
-            const float4 b = *reinterpret_cast<const float4 *>((r < RK_TQ ? b1 : w2) + h0 + 4 * c4);
-            if (r == RK_TQ) { s_w[c4] = b; continue; }
-            float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q0 + r < Q) p = *reinterpret_cast<const float4 *>(Pq + (q0 + r) * H + h0 + 4 * c4);
-            s_q[r][c4] = rk_query_bias(p, b);
-        }
-        __syncthreads();
-        for (int c4 = gl; c4 < hn / 4; c4 += RK_GROUP) {
-            float4 pc[RK_NC];
-#pragma unroll
-            for (int j = 0; j < RK_NC; ++j) {
-                pc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row[j] >= 0) pc[j] = *reinterpret_cast<const float4 *>(Pc + row[j] * H + h0 + 4 * c4);
-            }
-            const float4 pq = s_q[wave][c4], w = s_w[c4];
-#pragma unroll
-            for (int j = 0; j < RK_NC; ++j) acc[j] = rk_pair_step(acc[j], w, pq, pc[j]);
-        }
-    }
-    const float bias2 = b2[0];
-#pragma unroll
-    for (int j = 0; j < RK_NC; ++j) {
-        const float s = rk_fold16(acc[j]);
-        const long long c = c0 + j;
-        if (gl == 0 && q < Q && c < C) logit[q * C + c] = row[j] >= 0 ? rk_logit(s, bias2) : -INFINITY;
-    }
+    __shared__ RkTileLds s_t;
+    rk_tile_pairs(s_t, Pq, Pc, cand_idx, Q, Nc, C, H, ctiles, b1, w2, b2, logit, status,
+                  [](bool present, float s, float bias2) { return present ? rk_logit(s, bias2) : -INFINITY; });
 }
 
 // the values of the wave's four lane groups at this lane's place in its group, added first to last: every lane receives the sum
@@ -281,10 +228,7 @@ int rt_check(const char *who, const float *emb_q, int64_t Q, const float *emb_c,
         set_error("%s: bad argument", who);
         return ZT_ERR_ARG;
     }
-    if (!rank_width_ok(H)) {
-        set_error("%s: H=%d unsupported (H %% 4 == 0 and %d <= H <= %d)", who, H, RANK_MIN_H, RANK_MAX_H);
-        return ZT_ERR_UNSUPPORTED;
-    }
+    if (!rank_width_ok(H)) return rank_width_refused(who, H);
     if (cand_idx == nullptr && C != Nc) {
         set_error("%s: without cand_idx every query takes all Nc=%lld candidates, C=%lld given", who, (long long)Nc, (long long)C);
         return ZT_ERR_ARG;
@@ -340,9 +284,8 @@ extern "C" int zt_affinity_rank_train_forward(const float *emb_q_dev, int64_t Q,
     hipStream_t s = (hipStream_t)stream;
     int *status = reinterpret_cast<int *>(workspace_dev);
     ZT_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
-    // W_a = columns [0, H) of fc1.weight [H][2H], W_b = columns [H, 2H): the same matrix, a pointer offset, ldb = 2H (rank.hip)
-    rc = zt_gemm_f32(emb_q_dev, w->fc1_w, pq_dev, Q, H, H, H, 2 * (int64_t)H, H, 0, 1, 0, stream);
-    if (rc == ZT_OK) rc = zt_gemm_f32(emb_c_dev, w->fc1_w + H, pc_dev, Nc, H, H, H, 2 * (int64_t)H, H, 0, 1, 0, stream);
+    rc = rank_project(emb_q_dev, w, false, pq_dev, Q, H, stream);
+    if (rc == ZT_OK) rc = rank_project(emb_c_dev, w, true, pc_dev, Nc, H, stream);
     if (rc != ZT_OK) return rc;
     ZT_PROF_BEGIN(s, P_SCORE);
     k_rank_train_fwd<<<(unsigned)(qtiles * ctiles), WAVE * RK_TQ, 0, s>>>(pq_dev, pc_dev, cand_idx_dev, Q, Nc, C, H, ctiles, w->fc1_b,
