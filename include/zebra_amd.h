@@ -785,6 +785,21 @@ int zt_affinity_train_backward(const float *emb_dev, int64_t B, int32_t H,
                                float *d_fc1_w_dev, float *d_fc1_b_dev, float *d_fc2_w_dev,
                                float *d_fc2_b_dev, void *workspace_dev, int64_t ws_max_B,
                                void *stream);
+/* zt_affinity_train_plan (host code only, the one place that decides; the backward launches from the same function): the
+ * launches of zt_affinity_train_backward over B edges with every output asked for, out[ZT_AFFINITY_TRAIN_PLAN_FIELDS], all
+ * int64:
+ *   [0] split        partial products of d_fc1_w over K = 2B pair rows (1: written directly)
+ *   [1] k_per        pair rows per partial product, whole 64-row steps
+ *   [2] max_split    the most partial products this width takes
+ *   [3] steps        64-row steps of K = 2B
+ *   [4] grid_dx      workgroups of k_score_bwd_dx (16 edges each)
+ *   [5..7] grid_dw   x, y, z of k_score_bwd_dw's grid (z = split)
+ *   [8] grid_fin     workgroups of k_score_bwd_fin: the column sums, then the sum of the partial products
+ *   [9] lds_dx       dynamic LDS of k_score_bwd_dx in bytes
+ * With d_fc1_w_dev = NULL the backward runs no k_score_bwd_dw and takes split = 1.
+ * ZT_ERR_ARG for NULL out or B < 0, ZT_ERR_UNSUPPORTED for the width. */
+#define ZT_AFFINITY_TRAIN_PLAN_FIELDS 10
+int zt_affinity_train_plan(int64_t B, int32_t H, int64_t *out);
 /* evaluation/evaluation.py:34-45 and train.py:218-227 without the host: out_dev[0..3) (float64) =
  * (average_precision_score, roc_auc_score, mean(pos >= neg)) of B positive and B negative scores, scikit-learn's
  * definitions (distinct thresholds, ties included); accumulate != 0 adds to out_dev.  One single-workgroup kernel in one of

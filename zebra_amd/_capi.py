@@ -31,7 +31,7 @@ SYMBOLS = [
     "zt_affinity_workspace_bytes", "zt_affinity", "zt_link_metrics", "zt_pipeline_set_scoring", "zt_pipeline_last_scores", "zt_pipeline_run",
     "zt_exchange_unique_id", "zt_exchange_create", "zt_exchange_set_tables", "zt_exchange_destroy", "zt_pipeline_set_exchange",
     "zt_rnn_update", "zt_rnn_train_forward", "zt_rnn_train_backward", "zt_pipeline_set_cell",
-    "zt_affinity_train_workspace_bytes", "zt_affinity_train_forward", "zt_affinity_train_backward",
+    "zt_affinity_train_workspace_bytes", "zt_affinity_train_forward", "zt_affinity_train_backward", "zt_affinity_train_plan",
     "zt_link_metrics_plan", "zt_pipeline_set_metrics", "zt_pipeline_metrics",
     "zt_link_bce_forward", "zt_link_bce_backward", "zt_adam_step", "zt_adam_plan",
     "zt_tppr_query", "zt_affinity_rank_workspace_bytes", "zt_affinity_rank", "zt_rank_metrics",
@@ -70,6 +70,7 @@ TOPK_FORM_LANE, TOPK_FORM_LANE4 = 1, 2                          # zt_affinity_to
 DECODER_H1, DECODER_H2 = 80, 10                                 # zt_node_decoder's hidden widths
 DECODER_MIN_H, DECODER_MAX_H = RANK_MIN_H, RANK_MAX_H           # ... and its input widths (H % 4 == 0)
 DECODER_ARR_ONE, DECODER_ARR_FIVE = 1, 5                        # zt_node_decoder_plan
+SCORE_TRAIN_PLAN_FIELDS = ("split", "k_per", "max_split", "steps", "grid_dx", "grid_dw_x", "grid_dw_y", "grid_dw_z", "grid_fin", "lds_dx")
 DECODER_PLAN_FIELDS = ("arrangement", "waves", "rows", "k_chunk", "grid", "lds_bytes", "split", "k_per")
 NEG_MAX_K, NEG_MAX_ROUNDS = 4096, 8                             # zt_neg_sample
 NEG_FILTER, NEG_DISTINCT, NEG_EXCLUDE_SOURCE = 1, 2, 4
@@ -245,6 +246,14 @@ def neg_sample_plan(K):
     out = (C.c_int64 * 4)()
     check(lib().zt_neg_sample_plan(C.c_int32(K), out), "zt_neg_sample_plan")
     return dict(form=int(out[0]), threads=int(out[1]), n2=int(out[2]), lds_bytes=int(out[3]))
+
+
+def score_train_plan(B, H):
+    """zt_affinity_train_plan: the split of d_fc1_w over K = 2B pair rows, the three grids and the dynamic LDS of
+    zt_affinity_train_backward over B edges of width H with every output asked for (host code only)."""
+    out = (C.c_int64 * len(SCORE_TRAIN_PLAN_FIELDS))()
+    check(lib().zt_affinity_train_plan(C.c_int64(B), C.c_int32(H), out), "zt_affinity_train_plan")
+    return {name: int(out[i]) for i, name in enumerate(SCORE_TRAIN_PLAN_FIELDS)}
 
 
 def decoder_plan(N, H, training=False):

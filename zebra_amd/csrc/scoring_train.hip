@@ -295,6 +295,40 @@ void st_plan(int64_t max_B, int H, ScoreTrainPlan &p)
     p.total = o;
 }
 
+// The one place that decides the backward's launches (host code only; zt_affinity_train_plan reports it and
+// zt_affinity_train_backward launches from it).  d_fc1_w: K = 2B in partial products of whole 64-row steps, at least two steps
+// each; the split is recomputed from the rounded part so that no part is empty (nine steps asked in four parts: three of 192
+// rows).  Without d_fc1_w no product is launched and split = 1.
+struct ScoreBwdPlan {
+    int split, max_split;
+    long long kper, steps;
+    unsigned grid_dx, grid_dw[3], grid_fin;
+    size_t lds_dx;
+};
+ScoreBwdPlan st_bwd_plan(int64_t B, int H, bool want_dw, bool want_sums)
+{
+    ScoreBwdPlan p = {};
+    p.max_split = st_max_split(H);
+    p.steps = (2 * B + GK - 1) / GK;
+    const long long want = p.steps / 2 < 1 ? 1 : p.steps / 2;
+    int split = (int)(want < p.max_split ? want : p.max_split);
+    p.kper = (p.steps + split - 1) / split * GK;
+    split = B > 0 ? (int)((2 * B + p.kper - 1) / p.kper) : 1;
+    p.split = want_dw ? split : 1;
+    p.grid_dx = (unsigned)((B + 15) / 16);
+    p.lds_dx = ((size_t)48 * (round_up16(H) + 4) + 32) * 4;
+    if (want_dw) {
+        p.grid_dw[0] = (unsigned)((2 * H + 63) / 64);
+        p.grid_dw[1] = (unsigned)((H + 63) / 64);
+        p.grid_dw[2] = (unsigned)p.split;
+    }
+    if (p.split > 1 || want_sums) {
+        const size_t n4 = (size_t)H * 2 * H / 4;
+        p.grid_fin = (unsigned)((H + 63) / 64) + (p.split > 1 ? (unsigned)((n4 + ST_THREADS - 1) / ST_THREADS) : 0u);
+    }
+    return p;
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int st_check_width(const char *who, int H)
@@ -312,6 +346,20 @@ extern "C" int64_t zt_affinity_train_workspace_bytes(int64_t max_B, int32_t H)
     ScoreTrainPlan p;
     st_plan(max_B, H, p);
     return (int64_t)p.total;
+}
+
+extern "C" int zt_affinity_train_plan(int64_t B, int32_t H, int64_t *out)
+{
+    if (!out || B < 0) {
+        set_error("zt_affinity_train_plan: bad argument");
+        return ZT_ERR_ARG;
+    }
+    const int rc = st_check_width("zt_affinity_train_plan", H);
+    if (rc != ZT_OK) return rc;
+    const ScoreBwdPlan p = st_bwd_plan(B, H, true, true);
+    out[0] = p.split; out[1] = p.kper; out[2] = p.max_split; out[3] = p.steps; out[4] = p.grid_dx;
+    out[5] = p.grid_dw[0]; out[6] = p.grid_dw[1]; out[7] = p.grid_dw[2]; out[8] = p.grid_fin; out[9] = (int64_t)p.lds_dx;
+    return ZT_OK;
 }
 
 extern "C" int zt_affinity_train_forward(const float *emb_dev, int64_t B, int32_t H, const zt_affinity_weights *wt, float *prob_dev,
@@ -353,27 +401,19 @@ extern "C" int zt_affinity_train_backward(const float *emb_dev, int64_t B, int32
     char *ws = reinterpret_cast<char *>(workspace_dev);
     float *dh = reinterpret_cast<float *>(ws + p.off_dh), *ds = reinterpret_cast<float *>(ws + p.off_ds);
     float *partial = reinterpret_cast<float *>(ws + p.off_part);
-    const size_t lds = ((size_t)48 * (round_up16(H) + 4) + 32) * 4;
-    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_score_bwd_dx), lds));
-    k_score_bwd_dx<<<(unsigned)((B + 15) / 16), ST_THREADS, lds, s>>>(B, H, wt->fc1_w, wt->fc2_w, prob_dev, hid_dev, dprob_dev, dh, ds,
-                                                                       d_emb_dev);
-    int split = 1;
+    const ScoreBwdPlan pl = st_bwd_plan(B, H, d_fc1_w_dev != nullptr,
+                                        d_fc1_b_dev != nullptr || d_fc2_w_dev != nullptr || d_fc2_b_dev != nullptr);
+    ZT_HIP(set_dynamic_lds(reinterpret_cast<const void *>(k_score_bwd_dx), pl.lds_dx));
+    k_score_bwd_dx<<<pl.grid_dx, ST_THREADS, pl.lds_dx, s>>>(B, H, wt->fc1_w, wt->fc2_w, prob_dev, hid_dev, dprob_dev, dh, ds, d_emb_dev);
+    const int split = pl.split;
     if (d_fc1_w_dev != nullptr) {
-        // K = 2B in partial products of whole 64-row steps, at least two steps each
-        const long long steps = (2 * B + GK - 1) / GK;
-        const long long want = steps / 2 < 1 ? 1 : steps / 2;
-        split = (int)(want < st_max_split(H) ? want : st_max_split(H));
-        const long long kper = (steps + split - 1) / split * GK;
-        split = (int)((2 * B + kper - 1) / kper);
-        const dim3 grid((unsigned)((2 * H + 63) / 64), (unsigned)((H + 63) / 64), (unsigned)split);
-        k_score_bwd_dw<<<grid, 256, 0, s>>>(dh, emb_dev, B, H, kper, split > 1 ? partial : d_fc1_w_dev);
+        const dim3 grid(pl.grid_dw[0], pl.grid_dw[1], pl.grid_dw[2]);
+        k_score_bwd_dw<<<grid, 256, 0, s>>>(dh, emb_dev, B, H, pl.kper, split > 1 ? partial : d_fc1_w_dev);
     }
-    if (split > 1 || d_fc1_b_dev != nullptr || d_fc2_w_dev != nullptr || d_fc2_b_dev != nullptr) {
+    if (pl.grid_fin > 0) {
         const int cb = (H + 63) / 64;
-        const size_t n4 = (size_t)H * 2 * H / 4;
-        const unsigned rb = split > 1 ? (unsigned)((n4 + ST_THREADS - 1) / ST_THREADS) : 0u;
-        k_score_bwd_fin<<<cb + rb, ST_THREADS, 0, s>>>(B, H, dh, ds, hid_dev, partial, split, cb, d_fc1_w_dev, d_fc1_b_dev, d_fc2_w_dev,
-                                                       d_fc2_b_dev);
+        k_score_bwd_fin<<<pl.grid_fin, ST_THREADS, 0, s>>>(B, H, dh, ds, hid_dev, partial, split, cb, d_fc1_w_dev, d_fc1_b_dev,
+                                                          d_fc2_w_dev, d_fc2_b_dev);
     }
     ZT_LAUNCH_CHECK();
     return ZT_OK;
