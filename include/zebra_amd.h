@@ -742,6 +742,55 @@ int zt_temporal_attention(const float *src_dev, const float *src_time_dev,
                           float *out_dev, float *attn_w_dev, void *workspace_dev,
                           void *stream);
 
+/* The layer in a training step (csrc/attention_train.hip): the same forward with the dropout of
+ * nn.MultiheadAttention inside -- the softmax weights times a keep-mask that is a hash of drop_seed and the
+ * element (n * n_head + h) * k + j, 1 / (1 - drop_p) or 0; attn_w is the head mean of the weights AFTER dropout,
+ * as torch returns them -- and its backward.  With drop_p = 0 out and attn_w are zt_temporal_attention's bit for bit.
+ * No float atomics: two calls on the same inputs give the same bits.  attn_w is not differentiated through.
+ *
+ * zt_attention_train_plan (host code only): out[8] = supported (0 / 1), rq (query rows per workgroup), mt (16-row
+ *   M-tiles of key rows), dynamic LDS bytes of the forward and of the backward, workspace bytes per row, workspace
+ *   bytes fixed, saved bytes per row; all 0 where the shape is refused.  The shapes are zt_temporal_attention's (the
+ *   backward runs in the forward's LDS tile).
+ * workspace: fixed + N * per row bytes, 16-byte aligned -- fixed holds the zero-padded weights of the forward (the
+ *   only part the forward touches) and the transposed padded merger.fc2, merger.fc1 and out_proj; per row
+ *   4 (hidden + 2 E + 2 k E) bytes: the row deltas d_hid, d_y, d_q / sqrt(hd), d_K, d_V.
+ * saved: N * 4 (k n_head + 2 E + hidden) bytes -- the softmax weights before dropout, the concatenated heads, the
+ *   out_proj output and relu(merger.fc1); q, K and V are recomputed by the backward.
+ * The two size queries return -1 where the plan refuses (or N < 0).  Both calls: ZT_ERR_ARG for a NULL required
+ * buffer, a negative size or drop_p outside [0, 1); ZT_ERR_UNSUPPORTED for a refused shape; N == 0 is ZT_OK and
+ * launches nothing -- all before any device call. */
+typedef struct {
+    float *d_src, *d_src_time;                  /* [N][D], [N][T]                       */
+    float *d_nbr_feat, *d_edge_feat, *d_nbr_time; /* [N][k][D], [N][k][F], [N][k][T]    */
+    float *d_q_w, *d_k_w, *d_v_w, *d_in_b;      /* as zt_attn_weights                   */
+    float *d_out_w, *d_out_b;
+    float *d_m1_w, *d_m1_b, *d_m2_w, *d_m2_b;
+} zt_attn_grads;                 /* device pointers; any may be NULL: that gradient is not computed */
+int zt_attention_train_plan(int32_t D, int32_t F, int32_t T, int32_t n_head, int32_t hidden,
+                            int32_t out_dim, int32_t k, int64_t *out);
+int64_t zt_attention_train_workspace_bytes(int64_t N, int32_t D, int32_t F, int32_t T,
+                                           int32_t n_head, int32_t hidden, int32_t out_dim,
+                                           int32_t k);
+int64_t zt_attention_train_saved_bytes(int64_t N, int32_t D, int32_t F, int32_t T, int32_t n_head,
+                                       int32_t hidden, int32_t out_dim, int32_t k);
+int zt_attention_train_forward(const float *src_dev, const float *src_time_dev,
+                               const float *nbr_feat_dev, const float *edge_feat_dev,
+                               const float *nbr_time_dev, const uint8_t *mask_dev, int64_t N,
+                               int32_t k, int32_t D, int32_t F, int32_t T, int32_t n_head,
+                               int32_t hidden, int32_t out_dim, const zt_attn_weights *weights,
+                               float drop_p, uint64_t drop_seed, float *out_dev, float *attn_w_dev,
+                               float *saved_dev, void *workspace_dev, void *stream);
+/* d_out [N][out_dim]; saved as the forward of the same inputs, weights, drop_p and drop_seed left it. */
+int zt_attention_train_backward(const float *src_dev, const float *src_time_dev,
+                                const float *nbr_feat_dev, const float *edge_feat_dev,
+                                const float *nbr_time_dev, const uint8_t *mask_dev, int64_t N,
+                                int32_t k, int32_t D, int32_t F, int32_t T, int32_t n_head,
+                                int32_t hidden, int32_t out_dim, const zt_attn_weights *weights,
+                                float drop_p, uint64_t drop_seed, const float *saved_dev,
+                                const float *d_out_dev, const zt_attn_grads *grads,
+                                void *workspace_dev, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Link scoring and link-prediction metrics      */
 /* ------------------------------------------------------------------------ */

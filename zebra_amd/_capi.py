@@ -43,6 +43,8 @@ SYMBOLS = [
     "zt_rank_loss_forward", "zt_rank_loss_backward",
     "zt_neg_sample_plan", "zt_neg_sample",
     "zt_affinity_count_workspace_bytes", "zt_affinity_count", "zt_affinity_count_plan", "zt_rank_metrics_counts",
+    "zt_attention_train_plan", "zt_attention_train_workspace_bytes", "zt_attention_train_saved_bytes",
+    "zt_attention_train_forward", "zt_attention_train_backward",
 ]
 
 
@@ -76,6 +78,7 @@ NEG_MAX_K, NEG_MAX_ROUNDS = 4096, 8                             # zt_neg_sample
 NEG_FILTER, NEG_DISTINCT, NEG_EXCLUDE_SOURCE = 1, 2, 4
 NEG_FORM_REFUSED, NEG_FORM_WAVE, NEG_FORM_WORKGROUP = 0, 1, 2   # zt_neg_sample_plan
 COUNT_MAX_SKIP = 4                                              # zt_affinity_count
+ATTN_TRAIN_PLAN_FIELDS = ("supported", "rq", "mt", "lds_fwd", "lds_bwd", "ws_row", "ws_fixed", "saved_row")
 COUNT_PLAN_FIELDS = ("q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid", "h_chunks", "pc_offset", "min_bytes")
 TOPK_PLAN_FIELDS = ("form", "wave_queries", "q_tiles", "slab_rows", "n_slabs", "span_cols", "n_spans", "grid_pairs", "grid_merge",
                     "lists_offset", "pc_offset", "min_bytes")
@@ -107,6 +110,11 @@ class EmbedWeights(C.Structure):
 
 class AttnWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("q_w", "k_w", "v_w", "in_b", "out_w", "out_b", "m1_w", "m1_b", "m2_w", "m2_b")]
+
+
+class AttnGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("d_src", "d_src_time", "d_nbr_feat", "d_edge_feat", "d_nbr_time", "d_q_w", "d_k_w",
+                                          "d_v_w", "d_in_b", "d_out_w", "d_out_b", "d_m1_w", "d_m1_b", "d_m2_w", "d_m2_b")]
 
 
 class AffinityWeights(C.Structure):
@@ -177,7 +185,8 @@ def lib():
         for name in ("zt_embed_workspace_bytes", "zt_gru_workspace_bytes", "zt_gru_rows_offset", "zt_gru_train_workspace_bytes", "zt_attention_workspace_bytes", "zt_project_table_bytes", "zt_agg_backward_workspace_bytes", "zt_affinity_workspace_bytes",
                      "zt_affinity_train_workspace_bytes", "zt_affinity_rank_workspace_bytes", "zt_affinity_topk_workspace_bytes",
                      "zt_node_decoder_train_workspace_bytes", "zt_affinity_rank_train_workspace_bytes",
-                     "zt_affinity_count_workspace_bytes"):
+                     "zt_affinity_count_workspace_bytes", "zt_attention_train_workspace_bytes",
+                     "zt_attention_train_saved_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib
@@ -238,6 +247,15 @@ def count_plan(Q, Nc, H, workspace_bytes):
     check(lib().zt_affinity_count_plan(C.c_int64(Q), C.c_int64(Nc), C.c_int32(H), C.c_int64(workspace_bytes), out),
           "zt_affinity_count_plan")
     return {name: int(out[i]) for i, name in enumerate(COUNT_PLAN_FIELDS)}
+
+
+def attention_train_plan(D, F, T, heads, hidden, out_dim, k):
+    """zt_attention_train_plan: whether the attention layer's training kernels take the shape, the tile, the dynamic LDS of the
+    forward and the backward, and the workspace and saved-state sizes (host code only)."""
+    out = (C.c_int64 * len(ATTN_TRAIN_PLAN_FIELDS))()
+    check(lib().zt_attention_train_plan(*[C.c_int32(v) for v in (D, F, T, heads, hidden, out_dim, k)], out),
+          "zt_attention_train_plan")
+    return {name: int(out[i]) for i, name in enumerate(ATTN_TRAIN_PLAN_FIELDS)}
 
 
 def neg_sample_plan(K):

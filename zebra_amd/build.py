@@ -32,6 +32,7 @@ SOURCES = {
     "memory_update.hip": [],
     "train_ops.hip": [],
     "attention.hip": [],
+    "attention_train.hip": [],
     "scoring.hip": [],
     "scoring_train.hip": [],
     "rank.hip": [],

@@ -224,6 +224,16 @@ constexpr size_t ATT_LDS_BOUND = 158 * 1024;
 // weights' offsets in the workspace of `ws` bytes
 bool attention_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, AttnDims &d, size_t &lds, size_t off[8],
                     size_t &ws);
+// The layer's training pair (attention_train.hip; published by zt_attention_train_plan).  The tile (rq, mt) and the forward's
+// LDS and padded weights are attention_plan's; the backward runs in the same LDS carve-up, so it refuses nothing more.
+//   workspace = fixed + N * ws_row:  the forward's padded weights [0, fwd_ws), the transposed padded merger.fc2, merger.fc1
+//     and out_proj at off_t[0 .. 2], then from `fixed` the row deltas d_hid [N][hidden], d_y [N][E], d_q / sqrt(hd) [N][E],
+//     d_K [N k][E], d_V [N k][E], one after the other
+//   saved = N * saved_row:  p [N][k][heads], o [N][E], y [N][E], relu(fc1) [N][hidden], one after the other
+struct AttnTrainPlan {
+    size_t lds_fwd, lds_bwd, fwd_ws, off[8], off_t[3], fixed, ws_row, saved_row;
+};
+bool attention_train_plan(int D, int F, int T, int heads, int hidden, int out_dim, int k, AttnDims &d, AttnTrainPlan &p);
 // zt_link_metrics with a second destination: row (or NULL) receives the batch's three values whatever `accumulate` does to out
 // (the metrics tail of the native step, pipeline.hip: the running sum and the per-batch table from one launch)
 int link_metrics_launch(const float *pos_dev, const float *neg_dev, int64_t B, double *out_dev, int accumulate, double *row_dev,

@@ -945,8 +945,16 @@ class GraphDiffusionEmbedding(nn.Module):
 class TemporalAttentionLayer(nn.Module):
     """model/temporal_attention.py:7-68.  Dead code in the reference (only GraphAttentionEmbedding builds it
     and train.py can never reach that class); provided because the north star names it.
-    Without grad (eval) the forward runs in libzebra_amd.so; with grad it is the torch restatement below,
-    which is also what the HIP kernel is tested against (no reference outputs exist)."""
+    Without grad (eval) the forward runs in libzebra_amd.so (k_temporal_attention).  With grad in training mode it is
+    the torch restatement below (forward_torch, which is also what the HIP kernels are tested against: no reference outputs
+    exist) unless ``fused_training`` is set: then forward and backward run in the library too (_HipTemporalAttention,
+    csrc/attention_train.hip) wherever attention_train_plan answers "hip", and forward_torch elsewhere.  The fused path
+    draws its dropout mask from a hash of one seed per forward (``_last_drop_seed``; drawn from torch's CPU generator, or
+    taken from ``drop_seed_override`` when that is not None), so its numbers differ from a seeded torch run's: the default
+    is False.  attn_w of the fused path carries no gradient."""
+
+    fused_training = False
+    drop_seed_override = None
 
     def __init__(self, n_node_features, n_neighbors_features, n_edge_features, time_dim, output_dimension,
                  n_head=2, dropout=0.1):
@@ -978,6 +986,12 @@ class TemporalAttentionLayer(nn.Module):
     def forward(self, src_node_features, src_time_features, neighbors_features, neighbors_time_features,
                 edge_features, neighbors_padding_mask):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and self.training:
+            N, k, D = neighbors_features.shape
+            if attention_train_plan(src_node_features.device.type, src_node_features.dtype, D, edge_features.shape[2],
+                                    self.time_dim, self.n_head, self.feat_dim, self.output_dimension, k,
+                                    fused=self.fused_training) == "hip":
+                return self._forward_fused(src_node_features, src_time_features, neighbors_features,
+                                           neighbors_time_features, edge_features, neighbors_padding_mask)
             return self.forward_torch(src_node_features, src_time_features, neighbors_features,
                                       neighbors_time_features, edge_features, neighbors_padding_mask)
         N, k, D = neighbors_features.shape
@@ -1010,6 +1024,109 @@ class TemporalAttentionLayer(nn.Module):
                                           C.c_int32(self.output_dimension), C.byref(aw), ptr(out), ptr(attn_w),
                                           ptr(self._ws), stream_ptr()), "zt_temporal_attention")
         return out, attn_w
+
+    def _qkv(self):
+        # F = 0: kdim == embed_dim, and nn.MultiheadAttention then keeps one packed in_proj_weight [3E][E] instead of the three
+        mha = self.multi_head_target
+        return mha.in_proj_weight.chunk(3) if mha._qkv_same_embed_dim else (mha.q_proj_weight, mha.k_proj_weight,
+                                                                            mha.v_proj_weight)
+
+    def _forward_fused(self, src_node_features, src_time_features, neighbors_features, neighbors_time_features,
+                       edge_features, neighbors_padding_mask):
+        mha = self.multi_head_target
+        drop_p = float(mha.dropout)
+        if self.drop_seed_override is not None:
+            drop_seed = int(self.drop_seed_override)
+        else:
+            drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0
+        self._last_drop_seed = drop_seed
+        N = src_node_features.shape[0]
+        q_w, k_w, v_w = self._qkv()
+        packed = mha.in_proj_weight if mha._qkv_same_embed_dim else None
+        return _HipTemporalAttention.apply(
+            src_node_features, src_time_features.reshape(N, self.time_dim), neighbors_features, edge_features,
+            neighbors_time_features, neighbors_padding_mask, self.n_head, drop_p, drop_seed, packed,
+            q_w if packed is None else None, k_w if packed is None else None, v_w if packed is None else None,
+            mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, self.merger.fc1.weight, self.merger.fc1.bias,
+            self.merger.fc2.weight, self.merger.fc2.bias)
+
+
+def attention_train_plan(device_type, dtype, D, F, T, heads, hidden, out_dim, k, fused=True):
+    """Which path a training forward of TemporalAttentionLayer takes (pure host code, in the style of tgn.link_score_plan):
+    "hip" -- _HipTemporalAttention -- when ``fused`` is on, the inputs are float32 on the GPU and zt_attention_train_plan takes
+    the shape (zt_temporal_attention's shapes: 1 <= heads <= 4 dividing E, k <= 80, the row tile within 158 KB of LDS); else
+    "torch", forward_torch."""
+    if not fused or device_type != "cuda" or dtype != torch.float32:
+        return "torch"
+    return "hip" if _capi.attention_train_plan(D, F, T, heads, hidden, out_dim, k)["supported"] else "torch"
+
+
+class _HipTemporalAttention(torch.autograd.Function):
+    """(out, attn_w) of TemporalAttentionLayer with forward and backward on the HIP kernels of csrc/attention_train.hip
+    (zt_attention_train_forward / zt_attention_train_backward), the dropout of the attention weights inside (a hash of
+    drop_seed, modules.dropout_mask(seed, p, (1, N, heads), k) in numpy).  The projection weights come either packed
+    (in_proj_weight [3E][E], F = 0) or as the three matrices.  attn_w is not differentiable; no double backward."""
+
+    @staticmethod
+    def forward(ctx, src, src_t, nbr, edge, nbr_t, pad_mask, heads, drop_p, drop_seed, in_w, q_w, k_w, v_w, in_b, out_w,
+                out_b, m1_w, m1_b, m2_w, m2_b):
+        N, k, D = nbr.shape
+        F, T = edge.shape[2], src_t.shape[1]
+        hidden, out_dim = m1_w.shape[0], m2_w.shape[0]
+        c = lambda t: t.detach().contiguous().float()
+        qkv = in_w.detach().chunk(3) if in_w is not None else (q_w, k_w, v_w)
+        ten = [c(src), c(src_t), c(nbr), c(edge), c(nbr_t), pad_mask.detach().to(torch.uint8).contiguous()]
+        wts = [c(qkv[0]), c(qkv[1]), c(qkv[2]), c(in_b), c(out_w), c(out_b), c(m1_w), c(m1_b), c(m2_w), c(m2_b)]
+        dims = [C.c_int32(v) for v in (D, F, T, heads, hidden, out_dim, k)]
+        plan = _capi.attention_train_plan(D, F, T, heads, hidden, out_dim, k)
+        if not plan["supported"]:
+            raise ValueError("zt_attention_train_forward: unsupported shape")
+        dev = src.device
+        ws = torch.empty(max(plan["ws_fixed"], 16), dtype=torch.uint8, device=dev)       # the forward: the padded weights only
+        saved = torch.empty(max(N * plan["saved_row"] // 4, 1), dtype=torch.float32, device=dev)
+        out = torch.empty((N, out_dim), dtype=torch.float32, device=dev)
+        attn_w = torch.empty((N, k), dtype=torch.float32, device=dev)
+        aw = _capi.AttnWeights(*[ptr(t) for t in wts])
+        check(lib().zt_attention_train_forward(*[ptr(t) for t in ten], C.c_int64(N), C.c_int32(k), C.c_int32(D), C.c_int32(F),
+                                               C.c_int32(T), C.c_int32(heads), C.c_int32(hidden), C.c_int32(out_dim),
+                                               C.byref(aw), C.c_float(drop_p), C.c_uint64(drop_seed), ptr(out), ptr(attn_w),
+                                               ptr(saved), ptr(ws), stream_ptr()), "zt_attention_train_forward")
+        ctx.save_for_backward(saved, *ten, *wts)
+        ctx.cfg = (N, k, D, F, T, heads, hidden, out_dim, float(drop_p), int(drop_seed), in_w is not None, plan)
+        ctx.mark_non_differentiable(attn_w)
+        return out, attn_w
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, _d_attn_w):
+        saved, ten, wts = ctx.saved_tensors[0], ctx.saved_tensors[1:7], ctx.saved_tensors[7:]
+        N, k, D, F, T, heads, hidden, out_dim, drop_p, drop_seed, packed, plan = ctx.cfg
+        dev, E = saved.device, D + T
+        need = ctx.needs_input_grad
+        new = lambda want, *shape: (torch.zeros if N == 0 else torch.empty)(shape, dtype=torch.float32, device=dev) if want else None
+        # inputs 0 .. 4; parameters from index 9: in_w, q_w, k_w, v_w, in_b, out_w, out_b, m1_w, m1_b, m2_w, m2_b
+        g_in = [new(need[0], N, D), new(need[1], N, T), new(need[2], N, k, D), new(need[3] and F > 0, N, k, F), new(need[4], N, k, T)]
+        d_in_w = new(packed and need[9], 3 * E, E)                 # F = 0: Ek = E, the three gradients are its row blocks
+        if packed:
+            g_qkv = list(d_in_w.chunk(3)) if d_in_w is not None else [None, None, None]
+        else:
+            g_qkv = [new(need[10], E, E), new(need[11], E, D + F + T), new(need[12], E, D + F + T)]
+        g_rest = [new(need[13], 3 * E), new(need[14], E, E), new(need[15], E), new(need[16], hidden, E + D), new(need[17], hidden),
+                  new(need[18], out_dim, hidden), new(need[19], out_dim)]
+        grads = g_in + g_qkv + g_rest
+        if N and any(g is not None for g in grads):
+            ws = torch.empty(plan["ws_fixed"] + N * plan["ws_row"], dtype=torch.uint8, device=dev)
+            aw = _capi.AttnWeights(*[ptr(t) for t in wts])
+            gs = _capi.AttnGrads(*[ptr(g) for g in grads])
+            check(lib().zt_attention_train_backward(*[ptr(t) for t in ten], C.c_int64(N), C.c_int32(k), C.c_int32(D),
+                                                    C.c_int32(F), C.c_int32(T), C.c_int32(heads), C.c_int32(hidden),
+                                                    C.c_int32(out_dim), C.byref(aw), C.c_float(drop_p), C.c_uint64(drop_seed),
+                                                    ptr(saved), ptr(d_out.contiguous().float()), C.byref(gs), ptr(ws),
+                                                    stream_ptr()), "zt_attention_train_backward")
+        d_edge = g_in[3] if (g_in[3] is not None or not need[3]) else torch.zeros((N, k, 0), dtype=torch.float32, device=dev)
+        d_qkv = [None, None, None] if packed else g_qkv
+        return (g_in[0], g_in[1], g_in[2], d_edge, g_in[4], None, None, None, None, d_in_w, d_qkv[0], d_qkv[1], d_qkv[2],
+                *g_rest)
 
 
 def get_embedding_module(module_type, **kw):
